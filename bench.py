@@ -13,6 +13,13 @@ the launch stream.  Multi-GPU: games shard across ranks (no data-path
 collective) -> "scaling": "weak"; the learner leg all-reduces its gradient
 bucket over RCCL.
 
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N
+searches and prints the headline line; `--dump-outputs DIR` also writes what
+the last timed search returned (child visits, root values, actions) as
+DIR/<name>.npy.  Every other leg — the per-launch roofline pass, the self-play
+pipeline, the learner / corrected-learner / actor-learner legs and the CPU
+baselines — runs only with `--full`.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -233,6 +240,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg: the per-launch roofline pass, the self-play pipeline, the "
+                         "learner, corrected-learner and actor-learner legs and the CPU baselines (the leg options "
+                         "below apply to these); without it only the timed searches run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed search returned (child_visits, root_values, actions; float32) "
+                         "as DIR/<name>.npy (ranks > 0: <name>_rank<r>.npy); the inputs are seeded, so two builds "
+                         "can be compared output for output")
     ap.add_argument("--game", choices=["tictactoe", "connect4", "atari"], default="tictactoe")
     ap.add_argument("--net", choices=["fc", "resnet"], default="fc")
     ap.add_argument("--games", type=int, default=None,
@@ -259,6 +274,8 @@ def main():
                     help="(tests) ranks join a gloo group, all-reduce their rank ids on the CPU and rank 0 prints "
                          "one JSON line; no GPU call")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -333,7 +350,7 @@ def main():
     # the timed region carries no per-launch events: an event pair around every
     # launch puts marker packets between the searches (~14 us per step measured
     # against the rocprof kernel time); the per-launch duration for the roofline
-    # comes from a second, instrumented pass of the same K launches below
+    # comes from a second, instrumented pass of the same K launches below (--full)
     t0 = time.perf_counter()
     for k in range(args.steps):
         step(args.warmup + k)
@@ -342,14 +359,21 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-    for k in range(args.steps):
-        evs[k][0].record(stream)
-        step(args.warmup + k)
-        evs[k][1].record(stream)
-    torch.cuda.synchronize()
-    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
-    if resnet:
+    if args.dump_outputs:                                 # the last timed search's results, before any later pass
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = f"_rank{rank}" if rank else ""
+        for name, d in (("child_visits", d_cv), ("root_values", d_rv), ("actions", d_act)):
+            np.save(os.path.join(args.dump_outputs, f"{name}{sfx}.npy"), d.cpu().numpy().astype(np.float32))
+    if args.full:
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+               for _ in range(args.steps)]
+        for k in range(args.steps):
+            evs[k][0].record(stream)
+            step(args.warmup + k)
+            evs[k][1].record(stream)
+        torch.cuda.synchronize()
+        kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
+    if args.full and resnet:
         # the dominant kernel is the network launch (S per search): time it
         # with the engine's events on the launch stream over 3 more searches
         eng.debug_enable(2)
@@ -369,6 +393,33 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    B = args.batch or conf.batch_size
+    head = {
+        "metric": METRIC, "value": round(world * G * S * args.steps / elapsed, 1), "unit": "node-expansions/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "full": args.full,
+        "data": (("synthetic: 84x84x4 U[0,1) Philox observations for the timed searches, random glorot weights"
+                  if game is atari else
+                  f"synthetic: random-play {game.__name__.split('.')[-1]} positions, random glorot weights") +
+                 ("" if not args.full else
+                  "; learner batches sampled on the device from the self-play shard of the synthetic Atari-like "
+                  "env (games/atari_synth.py)" if game is atari else
+                  "; learner batches sampled on the device from the self-play replay shard")),
+        "config": {"workload": workload(game, resnet, G, S),
+                   "games_per_gpu": G, "sims_per_move": S, "global_games": G * world,
+                   "parallelism": f"games sharded x{world}" + ("" if not args.full else
+                                  f", learner dp{world} (global batch {B}, "
+                                  f"{B // world}{'+' if B % world else ''} samples per rank)")},
+    }
+    if not args.full:                                     # a plain run ends here
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        eng.close()
+        return
 
     # ---- device self-play pipeline: the whole move loop on the
     # device — observation/stacked planes, search, env step, GameHistory and
@@ -411,7 +462,7 @@ def main():
     # ---- learner leg: ref_semantics learner step at B = batch_size (32) on
     # batches sampled on the device from this rank's replay shard (§8f-2),
     # gradient bucket all-reduced over RCCL when world > 1
-    B, K = args.batch or conf.batch_size, conf.num_unroll_steps
+    K = conf.num_unroll_steps
     # the global batch B is split over the ranks, each drawing B/world samples from its own shard
     Br = B // world + (1 if rank < B % world else 0)
     learner_sps = lstep_ms = lkern = learner_1step = None
@@ -629,8 +680,6 @@ def main():
                               "with B/world samples per rank" if world > 1 else "")}
 
     if rank == 0:
-        total_exp = world * G * S * args.steps
-        value = total_exp / elapsed
         f_exp = 2 * (net_macs(conf, hyper, 1) + net_macs(conf, hyper, 2))   # prediction + dynamics
         f_root = 2 * (net_macs(conf, hyper, 0) + net_macs(conf, hyper, 1))  # representation + prediction
         # FC: one launch is the whole search; ResNet: one network launch = one
@@ -687,19 +736,7 @@ def main():
                                batch=1 if game is atari else 32, threads=nt)
             cpu1 = cpu_baseline(conf, hyper, nets, obs, legal, tp, args.cpu_budget, resnet,
                                 batch=1 if game is atari else 32, threads=1)
-        out = {
-            "metric": METRIC, "value": round(value, 1), "unit": "node-expansions/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": ("synthetic: 84x84x4 U[0,1) Philox observations for the timed searches, random glorot weights; "
-                     "learner batches sampled on the device from the self-play shard of the synthetic Atari-like "
-                     "env (games/atari_synth.py)" if game is atari else
-                     f"synthetic: random-play {game.__name__.split('.')[-1]} positions, random glorot weights; "
-                     "learner batches sampled on the device from the self-play replay shard"),
-            "config": {"workload": workload(game, resnet, G, S),
-                       "games_per_gpu": G, "sims_per_move": S, "global_games": G * world,
-                       "parallelism": f"games sharded x{world}, learner dp{world} (global batch {B}, "
-                                      f"{B // world}{'+' if B % world else ''} samples per rank)"},
+        out = dict(head, **{
             "learner_steps_per_s": round(learner_sps, 1) if learner_sps else None,
             "learner_steps_per_s_1step": round(learner_1step, 1) if learner_1step else None,
             "learner_multi": multi,
@@ -735,7 +772,7 @@ def main():
                          "mfma_util_chip": search_pmc.get("mfma_util_chip")},
             "cpu_baseline": cpu,
             "cpu_baseline_1thread": cpu1,    # the reference's single self-play worker (main.jl:2)
-        }
+        })
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -36,6 +36,12 @@ def test_gpus1_runs_in_process():
     assert json.loads(r.stdout.strip().splitlines()[-1])["n_gpus"] == 1
 
 
+def test_full_and_dump_outputs_are_options(tmp_path):
+    r = _run(["--gpus", "1", "--full", "--dump-outputs", str(tmp_path), "--launcher-selftest"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1])["n_gpus"] == 1
+
+
 def test_world_size_mismatch_fails():
     r = _run(["--gpus", "2", "--launcher-selftest"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr

@@ -2,14 +2,14 @@
 # FETCH_SIZE / WRITE_SIZE of mz_learn_small1 with the XCD-affine placement (MZ_LEARN_XCD=1)
 # and without, each counter in its own rocprofv3 pass.
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
-cd "$R" && mkdir -p gpurun_out/lxp && export TMPDIR=/tmp
-O=$R/gpurun_out/lxp
+R=$(cd "$(dirname "$0")/.." && pwd)
+cd "$R" && mkdir -p bench_out/lxp && export TMPDIR=/tmp
+O=$R/bench_out/lxp
 B="--no-cpu --steps 2 --warmup 1 --pipeline-moves 0 --train-moves 0 --learner-steps 50"
 for v in xcd plain; do
   if [ $v = xcd ]; then export MZ_LEARN_XCD=1; else unset MZ_LEARN_XCD; fi
   for c in FETCH_SIZE WRITE_SIZE; do
-    timeout -k 10 180 rocprofv3 --pmc $c --output-format csv -d $O/${v}_$c -o run -- python bench.py $B > $O/${v}_$c.log 2>&1 || { echo FAILED $v $c; tail -5 $O/${v}_$c.log; exit 1; }
+    timeout -k 10 180 rocprofv3 --pmc $c --output-format csv -d $O/${v}_$c -o run -- python bench.py --full $B > $O/${v}_$c.log 2>&1 || { echo FAILED $v $c; tail -5 $O/${v}_$c.log; exit 1; }
   done
   python - "$O" "$v" <<'PY'
 import csv, glob, sys
