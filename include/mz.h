@@ -387,7 +387,8 @@ int mz_learner_train_dev(mz_handle* h, int32_t B, uint32_t step, double eta, flo
  * 1 <= L <= 256.  FC: chain launches (mz_learn_chain: the ADAM iterations,
  * each step's θ scattered into its own image in a bank, Σθ² per step, the
  * batches) of up to 32 steps, each followed by unroll launches
- * (mz_learn_multi*) of up to 16 steps side by side; ResNet: the same chain
+ * (mz_learn_multi*) of up to 32 steps side by side (mz_learn_multi4; 16 on
+ * the one- and two-sample kernels); ResNet: the same chain
  * launches feeding the mz_runroll_* launches with the steps on gridDim.z
  * (rlearner_multi).  The corrected mode and PER run the L steps one after
  * another.  Replaces L iterations of the learner loop.                      */
@@ -417,6 +418,35 @@ int mz_replay_get_priorities(mz_handle* h, int32_t i, float* priorities, float* 
 int mz_replay_get_game(mz_handle* h, int32_t i, int32_t* T, uint8_t* obs, int32_t* actions,
                        float* rewards, int32_t* to_play, float* child_visits, float* root_values);
 int mz_selfplay_slots(mz_handle* h, int32_t* history_len, uint8_t* board, int32_t* player);
+
+/* Reanalyse (ReplayBuffer.jl:8, 56-67; muzero.jl:15-19): games first ..
+ * first+count-1 of the shard (0 = oldest held, as mz_replay_get_game;
+ * count < 0 = all held; games past the held range are skipped on the device)
+ * get reanalysed_predicted_root_values = value head of prediction(
+ * representation(stacked obs)) at every position, with the weights
+ * mz_net_forward would use at this point of the stream.  Stream-ordered, no
+ * host synchronisation.  Targets drawn afterwards (mz_replay_sample and
+ * every learner call that samples) bootstrap from them instead of the
+ * search's root_values; a game stored into a slot later (self-play or
+ * mz_replay_save_game) starts as `nothing` again, and PER's initial
+ * priorities stay on root_values (save_game runs before any reanalysis).
+ * FC engines: one launch (mz_reanalyse_fc); ResNet board engines: gather /
+ * representation / prediction / scatter launches per chunk of positions.
+ * The frame-stack env (MZ_ENV_ATARI) is refused.
+ * Ordering is the caller's: reanalyse reads the shard and the weights, so it
+ * and mz_selfplay_move / the learner calls on DIFFERENT streams must be
+ * ordered by the caller (events); on one stream nothing is needed.  In the
+ * split actor-learner loop the place for the call is between mz_train_move
+ * and mz_train_learn, on their stream; mz_train_run never reanalyses (the
+ * reference's loop has no reanalyse worker).
+ * _clear_reanalysed: every held game back to `nothing`.  _reanalysed_count:
+ * num_reanalysed_games, one per game per mz_replay_reanalyse since
+ * mz_selfplay_init; synchronises.  _get_reanalysed (parity): game i's flag
+ * and, if set, its T values (buffer sized for max_moves + 1); synchronises. */
+int mz_replay_reanalyse(mz_handle* h, int32_t first, int32_t count, void* stream);
+int mz_replay_clear_reanalysed(mz_handle* h, void* stream);
+int mz_replay_reanalysed_count(mz_handle* h, int64_t* n);
+int mz_replay_get_reanalysed(mz_handle* h, int32_t i, int32_t* is_set, float* values);
 
 /* ---- Actor–learner loop (self_play! ‖ learning!) -----
  * The reference runs self_play! (SelfPlay.jl:384-419) and learning!

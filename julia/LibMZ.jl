@@ -178,6 +178,25 @@ learner_train_multi!(e::Engine, B, step0, etas::Vector{Float64}; losses=C_NULL) 
                    (Ptr{Cvoid}, Int32, UInt32, Int32, Ptr{Float64}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
                    e.h, B, step0, length(etas), etas, losses, C_NULL, C_NULL))
 
+# Reanalyze (src/ReplayBuffer.jl:8, 56-67; the worker src/muzero.jl:15-19 leaves unbuilt) on the device shard:
+# games first .. first+count-1 (0 = oldest held, count < 0 = all held) get reanalysed_predicted_root_values from
+# the current networks, stream-ordered; targets drawn afterwards bootstrap from them.  In the split loop call it
+# between train_move! and train_learn!.
+reanalyse!(e::Engine; first=0, count=-1) =
+    check(e, ccall((:mz_replay_reanalyse, libmz), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}), e.h, first, count, C_NULL))
+clear_reanalysed!(e::Engine) =                 # every held game back to `nothing`
+    check(e, ccall((:mz_replay_clear_reanalysed, libmz), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), e.h, C_NULL))
+function reanalysed_count(e::Engine)           # num_reanalysed_games
+    n = Ref{Int64}(0)
+    check(e, ccall((:mz_replay_reanalysed_count, libmz), Cint, (Ptr{Cvoid}, Ref{Int64}), e.h, n))
+    n[]
+end
+function get_reanalysed(e::Engine, i, max_moves)   # shard game i: `nothing`, or max_moves + 1 values (the game's first T hold)
+    set = Ref{Int32}(0); v = zeros(Float32, max_moves + 1)
+    check(e, ccall((:mz_replay_get_reanalysed, libmz), Cint, (Ptr{Cvoid}, Int32, Ref{Int32}, Ptr{Float32}), e.h, i, set, v))
+    set[] == 0 ? nothing : v
+end
+
 """The actor–learner loop of self_play! ‖ learning! (src/SelfPlay.jl:384-419,
 src/Learning.jl:306-438; quirk Q16) on one GPU: `moves` self-play moves with the
 actors' nets, one learner step per finished game, the actors one checkpoint behind.

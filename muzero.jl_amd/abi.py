@@ -82,6 +82,10 @@ SIGNATURES = {
     "mz_replay_get_priorities": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP]),
     "mz_replay_get_game": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mz_selfplay_slots": (ctypes.c_int, [_VP, _VP, _VP, _VP]),
+    "mz_replay_reanalyse": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, _VP]),
+    "mz_replay_clear_reanalysed": (ctypes.c_int, [_VP, _VP]),
+    "mz_replay_reanalysed_count": (ctypes.c_int, [_VP, _VP]),
+    "mz_replay_get_reanalysed": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP]),
     "mz_learner_set_mode": (ctypes.c_int, [_VP, ctypes.c_int]),
     "mz_train_init": (ctypes.c_int, [_VP, ctypes.c_int32]),
     "mz_train_init_at": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int64]),
@@ -498,6 +502,32 @@ class Engine:
         gp = np.zeros(1, np.float32)
         self._check(self.lib.mz_replay_get_priorities(self.h, i, _p(pr), _p(gp)), "mz_replay_get_priorities")
         return pr, float(gp[0])
+
+    # ---- Reanalyse (ReplayBuffer.jl:8, 56-67) on the device shard
+    def replay_reanalyse(self, first=0, count=-1, stream=None):
+        """reanalysed_predicted_root_values of shard games first .. first+count-1 (0 = oldest held,
+        count < 0 = all held) from the current weights; stream-ordered, no host synchronisation.
+        Targets sampled afterwards bootstrap from them."""
+        self._check(self.lib.mz_replay_reanalyse(self.h, first, count, stream), "mz_replay_reanalyse")
+
+    def replay_clear_reanalysed(self, stream=None):
+        """Every held game back to `nothing` (targets bootstrap from root_values again)."""
+        self._check(self.lib.mz_replay_clear_reanalysed(self.h, stream), "mz_replay_clear_reanalysed")
+
+    def replay_reanalysed_count(self):
+        """num_reanalysed_games: one per game per replay_reanalyse since selfplay_init."""
+        n = ctypes.c_int64()
+        self._check(self.lib.mz_replay_reanalysed_count(self.h, ctypes.byref(n)), "mz_replay_reanalysed_count")
+        return int(n.value)
+
+    def replay_get_reanalysed(self, i):
+        """Shard game i (0 = oldest held): its reanalysed values (T,) float32, or None if `nothing`."""
+        v = np.zeros(self.conf.max_moves + 1, np.float32)
+        s = ctypes.c_int32()
+        self._check(self.lib.mz_replay_get_reanalysed(self.h, i, ctypes.byref(s), _p(v)), "mz_replay_get_reanalysed")
+        if not s.value:
+            return None
+        return v[:len(self.replay_get_game(i).action_history)].copy()
 
     def selfplay_slots(self):
         G = self.sp_G

@@ -74,6 +74,10 @@ extern "C" __global__ void mz_rp_per_prep(SpHist ring, const long long* counters
 extern "C" __global__ void mz_rp_per_norm(float* w, int B);
 extern "C" __global__ void mz_rp_per_update(SpHist ring, const long long* counters, int cap, int Tmax, int B, int K,
                                             int alpha, const int32_t* index, const float* pv, const float* tv);
+extern "C" __global__ void mz_reanalyse_fc(ReanParams Q);
+extern "C" __global__ void mz_reanalyse_gather(ReanParams Q);
+extern "C" __global__ void mz_reanalyse_scatter(ReanParams Q);
+extern "C" __global__ void mz_reanalyse_clear(int32_t* rean, int cap);
 extern "C" __global__ void mz_search_small1(SmallParams P);
 extern "C" __global__ void mz_search_small2(SmallParams P);
 extern "C" __global__ void mz_search_small4(SmallParams P);
@@ -309,6 +313,10 @@ struct mz_handle {
     int pf_cap = 0, pf_cur = 0;
     long long* d_pf_hdr = nullptr;          // [2][4]
     long long pf_epoch = 1;
+    // mz_replay_reanalyse on ResNet engines: staging of one chunk (in sp_allocs)
+    float *d_rn_x = nullptr, *d_rn_h = nullptr, *d_rn_v = nullptr, *d_rn_p = nullptr;
+    int rn_cap = 0;
+    size_t rean_lds = 0;                    // mz_reanalyse_fc's dynamic-LDS attribute
     // L learner steps per launch pair (mz_learner_train_multi_dev, ChainParams): the bank of
     // MZ_MULTI_MAX small-kernel images (θ_t .. θ_{t+L-1}), per-step batches, read-outs,
     // loss terms, Σθ² partials, fold counters and losses, for batches up to ml_cap
@@ -3250,6 +3258,10 @@ int mz_selfplay_init(mz_handle* h, int env_kind, int G, int replay_games) {
     MZ_TRY(h, spalloc(h, &h->d_sp_ekey, (size_t)G));
     if (sp_alloc_hist(h, h->sp_hist, (size_t)G)) return -1;
     if (sp_alloc_hist(h, h->sp_ring, (size_t)replay_games)) return -1;
+    // reanalysed_predicted_root_values of the shard's games (mz_replay_reanalyse); rean zeroed = `nothing`
+    MZ_TRY(h, spalloc(h, &h->sp_ring.rrv, (size_t)replay_games * h->sp_T));
+    MZ_TRY(h, spalloc(h, &h->sp_ring.rean, (size_t)replay_games));
+    h->rn_cap = 0;                              // the ResNet staging buffers were in sp_allocs
     MZ_TRY(h, spalloc(h, &h->d_sp_counters, 4));
     MZ_TRY(h, spalloc(h, &h->d_sp_done, (size_t)G));
     MZ_TRY(h, spalloc(h, &h->d_sp_rpos, (size_t)G));
@@ -3377,6 +3389,7 @@ int mz_replay_save_game(mz_handle* h, int32_t T, const uint8_t* obs, const int32
     MZ_TRY(h, hipMemcpy(r.cv + base * A, child_visits, (size_t)T * A * 4, hipMemcpyHostToDevice));
     MZ_TRY(h, hipMemcpy(r.rv + base, root_values, (size_t)T * 4, hipMemcpyHostToDevice));
     MZ_TRY(h, hipMemcpy(r.len + slot, &T, 4, hipMemcpyHostToDevice));
+    MZ_TRY(h, hipMemset(r.rean + slot, 0, 4));      // a new game: reanalysed values = `nothing`
     MZ_TRY(h, hipMemcpy(h->d_sp_counters, c, sizeof(c), hipMemcpyHostToDevice));
     if (h->conf.PER) {                              // initial priorities (:136-143)
         hipLaunchKernelGGL(mz_rp_per_init, dim3(1), dim3(64), 0, h->stream, h->sp_ring, slot, (int)T, h->sp_T,
@@ -4144,6 +4157,120 @@ int mz_replay_get_game(mz_handle* h, int32_t i, int32_t* T, uint8_t* obs, int32_
     if (to_play) MZ_TRY(h, hipMemcpy(to_play, r.tp + base, (size_t)len * 4, hipMemcpyDeviceToHost));
     if (child_visits) MZ_TRY(h, hipMemcpy(child_visits, r.cv + base * A, (size_t)len * A * 4, hipMemcpyDeviceToHost));
     if (root_values) MZ_TRY(h, hipMemcpy(root_values, r.rv + base, (size_t)len * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- Reanalyse (mz_reanalyse.hip): reanalysed_predicted_root_values on the shard
+static const int kReanChunk = 4096;     // ResNet engines: positions per gather / nets / scatter round
+
+int mz_replay_reanalyse(mz_handle* h, int32_t first, int32_t count, void* stream) {
+    if (!h) return -2;
+    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
+    if (h->sp_frames > 0 || h->ds) return fail(h, "reanalyse: frame-stack env not built");
+    if (first < 0) return fail(h, "reanalyse: first must be >= 0");
+    if ((long long)h->sp_cap * h->sp_T > 0x7fffffffLL) return fail(h, "reanalyse: shard too large");
+    MZ_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    // how many games are held is only known on the device: the grid covers the
+    // selection clipped to the capacity, the kernels clip it to the held range
+    const int gmax = count < 0 ? h->sp_cap - first : std::min<int>(count, h->sp_cap - first);
+    ++h->pf_epoch;                                  // a batch drawn ahead has the old targets
+    if (gmax <= 0) return 0;
+    ReanParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.first = first; Q.count = count;
+    Q.T = h->sp_T; Q.osz = h->sp_osz; Q.P = h->plane; Q.F = h->obs_feat; Q.stacked = h->conf.stacked_observations;
+    Q.cap = h->sp_cap; Q.ring = h->sp_ring; Q.counters = h->d_sp_counters;
+    const int npos = gmax * h->sp_T;
+    if (h->kind != 1) {
+        Q.plan_root = h->d_plan[3]; Q.Wp = h->d_Wp; Q.Bp = h->d_Bp;
+        Q.x_rep = h->lay.x_rep; Q.v_out = h->lay.v_out; Q.v_act = h->lay.v_act; Q.lds_total = h->lay.total;
+        const size_t lds = ((size_t)h->lay.total + (size_t)MZ_TILE * h->obs_feat) * 4;
+        if (lds > kLdsMax) return fail(h, "reanalyse: the tile's activations and observations exceed the LDS");
+        if (lds > h->rean_lds) {
+            MZ_TRY(h, hipFuncSetAttribute((const void*)mz_reanalyse_fc, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)lds));
+            h->rean_lds = lds;
+        }
+        const int ntiles = (npos + MZ_TILE - 1) / MZ_TILE;
+        void* args[] = {&Q};
+        MZ_TRY(h, hipLaunchKernel((const void*)mz_reanalyse_fc, dim3(std::min(ntiles, 4 * h->n_cu)), dim3(MZ_THREADS),
+                                  args, lds, st));
+        return 0;
+    }
+    const RPlan& Rr = h->rplan[MZ_NET_REPR];
+    const RPlan& Rp = h->rplan[MZ_NET_PRED];
+    if (Rr.in_feat != h->obs_feat || Rp.in_feat != Rr.out0_n || Rp.out0_n != 1)
+        return fail(h, "reanalyse: unexpected ResNet plan shapes");
+    const int chunk = std::min(npos, kReanChunk);
+    if (chunk > h->rn_cap) {
+        MZ_TRY(h, spalloc(h, &h->d_rn_x, (size_t)chunk * h->obs_feat, false));
+        MZ_TRY(h, spalloc(h, &h->d_rn_h, (size_t)chunk * Rr.out0_n, false));
+        MZ_TRY(h, spalloc(h, &h->d_rn_v, (size_t)chunk * Rp.out0_n, false));
+        MZ_TRY(h, spalloc(h, &h->d_rn_p, (size_t)chunk * std::max(Rp.out1_n, 1), false));
+        h->rn_cap = chunk;
+    }
+    for (int p0 = 0; p0 < npos; p0 += chunk) {
+        const int pn = std::min(chunk, npos - p0);
+        Q.p0 = p0; Q.pn = pn; Q.stage_x = h->d_rn_x; Q.stage_v = h->d_rn_v;
+        hipLaunchKernelGGL(mz_reanalyse_gather, dim3((pn + 3) / 4), dim3(256), 0, st, Q);
+        MZ_TRY(h, hipGetLastError());
+        for (int net = MZ_NET_REPR; net <= MZ_NET_PRED; ++net) {
+            RNetParams N;
+            N.ng = h->rn_ng; N.W = h->rconf.observation_shape[0]; N.H = h->rconf.observation_shape[1];
+            N.P = N.W * N.H; N.n_items = pn; N.softmax1 = net == MZ_NET_PRED; N.bn_s = h->bn_s;
+            N.plan = h->d_rplan + net; N.Wimg = h->d_Wp; N.flat = h->d_flat;
+            N.x = net == MZ_NET_REPR ? h->d_rn_x : h->d_rn_h;
+            N.out0 = net == MZ_NET_REPR ? h->d_rn_h : h->d_rn_v;
+            N.out1 = h->d_rn_p;
+            void* args[] = {&N};
+            MZ_TRY(h, hipLaunchKernel((const void*)mz_rnet_forward_kernel, dim3((pn + N.ng - 1) / N.ng),
+                                      dim3(RN_THREADS), args, h->rn_lds[net], st));
+        }
+        hipLaunchKernelGGL(mz_reanalyse_scatter, dim3((pn + 255) / 256), dim3(256), 0, st, Q);
+        MZ_TRY(h, hipGetLastError());
+    }
+    return 0;
+}
+
+int mz_replay_clear_reanalysed(mz_handle* h, void* stream) {
+    if (!h) return -2;
+    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
+    MZ_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    ++h->pf_epoch;
+    hipLaunchKernelGGL(mz_reanalyse_clear, dim3((h->sp_cap + 255) / 256), dim3(256), 0, st, h->sp_ring.rean, h->sp_cap);
+    MZ_TRY(h, hipGetLastError());
+    return 0;
+}
+
+int mz_replay_reanalysed_count(mz_handle* h, int64_t* n) {
+    if (!h || !n) return -2;
+    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);
+    long long c = 0;
+    MZ_TRY(h, hipMemcpy(&c, h->d_sp_counters + 3, sizeof(c), hipMemcpyDeviceToHost));
+    *n = c;
+    return 0;
+}
+
+int mz_replay_get_reanalysed(mz_handle* h, int32_t i, int32_t* is_set, float* values) {
+    if (!h) return -2;
+    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);
+    long long played = 0;
+    MZ_TRY(h, hipMemcpy(&played, h->d_sp_counters, sizeof(played), hipMemcpyDeviceToHost));
+    const long long held = std::min<long long>(played, h->sp_cap);
+    if (i < 0 || i >= held) return fail(h, "game index out of range");
+    const int slot = (int)((played - held + i) % h->sp_cap);
+    int32_t set = 0, len = 0;
+    MZ_TRY(h, hipMemcpy(&set, h->sp_ring.rean + slot, 4, hipMemcpyDeviceToHost));
+    MZ_TRY(h, hipMemcpy(&len, h->sp_ring.len + slot, 4, hipMemcpyDeviceToHost));
+    if (is_set) *is_set = set != 0;
+    if (values && set)
+        MZ_TRY(h, hipMemcpy(values, h->sp_ring.rrv + (size_t)slot * h->sp_T, (size_t)len * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -152,7 +152,8 @@ __device__ __forceinline__ void rp_sample_one(const RpSampleParams& Q, int b, in
         pos = (int)mz_rng_below(rp, (uint32_t)T) + 1;              // :80
     }
     const int K1 = Q.K + 1, A = Q.A;
-    const float* rv = Q.ring.rv + base;
+    // the bootstrap values: reanalysed_predicted_root_values unless `nothing` (ReplayBuffer.jl:8)
+    const float* rv = (Q.ring.rean[slot] ? Q.ring.rrv : Q.ring.rv) + base;
     const int32_t* tp = Q.ring.tp + base;
     const float* rew = Q.ring.rew + base;
     const int32_t* act = Q.ring.act + base;

@@ -297,7 +297,8 @@ extern "C" __global__ __launch_bounds__(256) void mz_sp_store(SpParams S) {
         __syncthreads();
         if (tid == 0) per_game_max(ring, slot, len, S.T);
     }
-    if (tid == 0) { S.ring.len[slot] = len; S.hist.len[g] = 0; S.done[g] = 0; }
+    // the game that held the slot may have been reanalysed: this one starts as `nothing`
+    if (tid == 0) { S.ring.len[slot] = len; S.ring.rean[slot] = 0; S.hist.len[g] = 0; S.done[g] = 0; }
     if (tid < 64) env_reset(S, g, tid);
 }
 

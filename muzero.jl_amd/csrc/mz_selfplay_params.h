@@ -26,6 +26,25 @@ struct SpHist {                 // a set of game records: [n][T] ...
     int32_t* len;               // [n] moves
     float* prio;                // [n][T] PER position priorities (ring only, conf.PER)
     float* gprio;               // [n] PER game priority = max(prio) (ring only)
+    // Reanalyse (ReplayBuffer.jl:8, 56-67; mz_reanalyse.hip), ring only (null in `hist`)
+    float* rrv;                 // [n][T] reanalysed_predicted_root_values
+    int32_t* rean;              // [n] 0 = `nothing`, else rrv holds the slot's whole game
+};
+
+// mz_replay_reanalyse on the shard's games first .. first+count-1 (0 = oldest
+// held; games past the held range are skipped on the device)
+struct ReanParams {
+    int first, count;           // count < 0: every held game
+    int T, osz, P, F, stacked, cap;
+    SpHist ring;
+    long long* counters;        // [0] num_played_games (read), [3] num_reanalysed_games (bumped once per game)
+    // FC engines (mz_reanalyse_fc): the root plan on the tile16 images
+    const int* plan_root; const float* Wp; const float* Bp;
+    int x_rep, v_out, v_act, lds_total;
+    // ResNet engines: positions [p0, p0 + pn) of the flattened (game, pos) grid, T per game
+    int p0, pn;
+    float* stage_x;             // [pn][F] gathered stacked observations
+    const float* stage_v;       // [pn] value-head outputs
 };
 
 struct SpParams {

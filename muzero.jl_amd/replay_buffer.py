@@ -24,12 +24,14 @@ def disc_pow(g, n):
 
 
 def compute_target_value(conf, h, index):
-    """ReplayBuffer.jl:5-20 (Q9); index is 1-based.  Float32 arithmetic."""
+    """ReplayBuffer.jl:5-20 (Q9); index is 1-based.  Float32 arithmetic.  The
+    bootstrap value is the reanalysed one unless that field is None (:8)."""
     f32 = np.float32
     T = len(h.root_values)
     bi = index + conf.td_steps
     if bi < T:
-        rv = f32(h.root_values[bi - 1])
+        rvs = h.root_values if h.reanalysed_predicted_root_values is None else h.reanalysed_predicted_root_values
+        rv = f32(rvs[bi - 1])
         last = rv if h.to_play_history[bi - 1] == h.to_play_history[index - 1] else -rv
         value = f32(last * disc_pow(conf.discount, conf.td_steps))
         for i in range(1, conf.td_steps + 2):
@@ -116,6 +118,7 @@ class ReplayBuffer:
         self.num_played_games = 0
         self.num_played_steps = 0
         self.total_samples = 0
+        self.num_reanalysed_games = 0
 
     def __len__(self):
         return len(self.buffer)
@@ -187,6 +190,33 @@ class ReplayBuffer:
         if per:
             out["weights"] = (wts / wts.max()).astype(np.float32)                 # :215
         return index_batch, out
+
+    def reanalyse(self, value_fn, game_ids=None):
+        """Reanalyze (ReplayBuffer.jl:8, 56-67; the worker muzero.jl:15-19 leaves
+        unbuilt): reanalysed_predicted_root_values of each game = value_fn(stacked
+        observations (T, feat)) -> (T,) values of the current networks.  game_ids
+        None = every held game; an id that has left the buffer since it was
+        chosen is skipped (update_history!'s check).  Returns the ids updated."""
+        c = self.conf
+        plane = c.observation_shape[0] * c.observation_shape[1]
+        done = []
+        for gid in (list(self.buffer.keys()) if game_ids is None else game_ids):
+            h = self.buffer.get(gid)
+            if h is None:
+                continue
+            T = len(h.root_values)
+            if self.frame_stack:
+                x = np.stack([frame_stack_obs(h.observation_history, i, self.frame_stack) for i in range(1, T + 1)])
+            else:
+                x = np.stack([get_stacked_observations(h.observation_history, h.action_history, i,
+                                                       c.stacked_observations, plane) for i in range(1, T + 1)])
+            v = np.asarray(value_fn(x), np.float32).reshape(-1)
+            if v.shape[0] != T:
+                raise ValueError(f"value_fn returned {v.shape[0]} values for {T} positions")
+            h.reanalysed_predicted_root_values = [np.float32(t) for t in v]
+            self.num_reanalysed_games += 1
+            done.append(gid)
+        return done
 
     def update_priorities(self, index_batch, predicted_values, target_values):
         """update_priorities! (ReplayBuffer.jl:168-183, Learning.jl:400-404) in its

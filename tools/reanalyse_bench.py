@@ -1,0 +1,109 @@
+"""Reanalyse throughput at the configs[1] shard: the TicTacToe FC engine, the
+shard filled by device self-play (512 slots, 50 simulations per move).
+
+Two routes to reanalysed_predicted_root_values of every held game, timed
+alternately in one process:
+  device  mz_replay_reanalyse over all held games (one mz_reanalyse_fc
+          launch), device events around enough repeats to run >= 0.5 s (the
+          host's issue time of the same passes is reported next to it: a pass
+          is not launch-bound while it is the smaller);
+  host    what there was before it: replay_get_game for every game, the
+          stacked observations in numpy, two net_forward calls (wall clock,
+          synchronised; the values then have nowhere to go on the device).
+Prints ONE JSON line: positions/s of both routes, the kernel's FLOP per
+position from the layer shapes (2 x MACs of representation + prediction, the
+policy head included: the root plan runs it) and the share of the f32 peak.
+"""
+import argparse
+import dataclasses
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402  (one HIP runtime)
+import _mzpkg  # noqa: E402
+
+_mzpkg.load()
+from muzero_jl_amd import abi  # noqa: E402
+from muzero_jl_amd.games import tictactoe as ttt  # noqa: E402
+from muzero_jl_amd.networks import init_nets, net_macs  # noqa: E402
+from muzero_jl_amd.selfplay import get_stacked_observations  # noqa: E402
+
+PEAK_F32 = 157.3                     # TFLOP/s, as bench.py
+
+
+def host_route(eng, conf, held):
+    plane = conf.observation_shape[0] * conf.observation_shape[1]
+    t0 = time.perf_counter()
+    games = [eng.replay_get_game(i) for i in range(held)]
+    x = np.stack([get_stacked_observations(h.observation_history, h.action_history, i, conf.stacked_observations, plane)
+                  for h in games for i in range(1, len(h.root_values) + 1)])
+    v = eng.forward(1, eng.forward(0, x))[0][:, 0]
+    return time.perf_counter() - t0, v, games
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--games", type=int, default=512)
+    ap.add_argument("--cap", type=int, default=4096)
+    ap.add_argument("--moves", type=int, default=80)
+    ap.add_argument("--rounds", type=int, default=3)
+    a = ap.parse_args()
+    conf = dataclasses.replace(ttt.conf, replay_buffer_size=a.cap)
+    eng = abi.Engine(conf, ttt.hyper, device=0, max_games=a.games, rng_seed=1)
+    for n, w in enumerate(init_nets(conf, ttt.hyper, seed=1234)):
+        eng.set_weights(n, w)
+    eng.selfplay_init(abi.ENV_TICTACTOE, a.games, a.cap)
+    for m in range(a.moves):
+        eng.selfplay_move(m, game_offset=0)
+    counts, held = eng.replay_counts()
+    eng.sync()
+    ts = torch.cuda.Stream()              # its own stream: the events and the launches share it (a null handle
+    st = ts.cuda_stream                   # would send the launches to the engine's stream, past the events)
+    for _ in range(5):                                        # warm-up
+        eng.replay_reanalyse(stream=st)
+    torch.cuda.synchronize()
+    dev_s, host_s, issue_s, reps = [], [], [], 10
+    positions = None
+    for r in range(a.rounds):
+        while True:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(ts)
+            t_issue = time.perf_counter()
+            for _ in range(reps):
+                eng.replay_reanalyse(stream=st)
+            issued = time.perf_counter() - t_issue
+            e1.record(ts)
+            e1.synchronize()
+            ms = e0.elapsed_time(e1)
+            print(f"round {r}: {reps} passes, {ms:.3f} ms on the device, issued in {issued * 1e3:.3f} ms", file=sys.stderr)
+            if ms >= 500.0:
+                break
+            reps = int(reps * min(100.0, max(2.0, 650.0 / max(ms, 1e-3))))
+        dev_s.append(ms * 1e-3 / reps)
+        issue_s.append(issued / reps)
+        t, v, games = host_route(eng, conf, held)
+        host_s.append(t)
+        positions = int(v.shape[0])
+        got = np.concatenate([eng.replay_get_reanalysed(i) for i in range(held)])
+        assert np.array_equal(got, v), "the two routes disagree"
+    flop = 2 * (net_macs(conf, ttt.hyper, 0) + net_macs(conf, ttt.hyper, 1))
+    d, h = float(np.median(dev_s)), float(np.median(host_s))
+    print(json.dumps({
+        "tool": "reanalyse_bench", "engine": "tictactoe fc", "games_held": int(held), "positions": positions,
+        "ring_rows": int(held) * (conf.max_moves + 1), "repeats": reps, "rounds": a.rounds,
+        "device_s_per_pass": round(d, 9), "device_positions_per_s": round(positions / d, 1),
+        "host_issue_s_per_pass": round(float(np.median(issue_s)), 9),
+        "host_s_per_pass": round(h, 6), "host_positions_per_s": round(positions / h, 1),
+        "speedup": round(h / d, 1), "flop_per_position": flop,
+        "device_tflops": round(positions * flop / d / 1e12, 5),
+        "frac_f32_peak": round(positions * flop / d / 1e12 / PEAK_F32, 6)}))
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
