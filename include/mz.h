@@ -448,6 +448,40 @@ int mz_replay_clear_reanalysed(mz_handle* h, void* stream);
 int mz_replay_reanalysed_count(mz_handle* h, int64_t* n);
 int mz_replay_get_reanalysed(mz_handle* h, int32_t i, int32_t* is_set, float* values);
 
+/* Reanalyse by search — the other half of MuZero Reanalyze, the worker the
+ * reference leaves as a TODO (muzero.jl:15-19): the stored positions of games
+ * first .. first+count-1 (selected as above) are searched again with the
+ * current networks.  Their child_visits become the games' policy targets and
+ * the search's root values their bootstrap values (they replace what
+ * mz_replay_reanalyse wrote; a later mz_replay_reanalyse keeps the policies
+ * and overwrites the values).  The selection is flattened as p = gi*T + pos
+ * (gi = index inside the selection, T = max_moves + 1); position p is searched
+ * exactly as mz_mcts_search_dev searches the game with Philox id
+ * game_offset + p: obs = the stacked observation at pos, to_play = the stored
+ * to_play, legal_mask = the env's legal actions on the stored board for that
+ * player (what self-play's search saw), `exploration` and rng_step as given,
+ * temperature 0 with the action discarded.  The result does not depend on how
+ * the rows are cut into launches: max_games rows per round of mz_reanalyse_sgather
+ * -> the engine's search launches -> mz_reanalyse_sscatter; rows with
+ * pos >= len and rows past the held range ride along as dummy games whose
+ * outputs are dropped.  A stored position with no legal action, or a to_play
+ * outside 1..players (only mz_replay_save_game can store either), is not
+ * searched: it keeps copies of its stored child_visits and root_values.
+ * Stream-ordered, no host synchronisation; num_reanalysed_games goes up by
+ * one per game.  The search's io buffers and the shard's reanalysed
+ * child_visits are allocated by the first call that has work.  Ordering and
+ * the place in the split loop are as for mz_replay_reanalyse: between
+ * mz_train_move and mz_train_learn, on their stream (the search uses the
+ * engine's one set of tree buffers, as mz_selfplay_move does); mz_train_run
+ * never reanalyses.  The frame-stack env is refused.
+ * _get_reanalysed_policies (parity): game i's policy flag and, if set, its
+ * (A, T) child_visits in mz_replay_get_game's layout (buffer sized for
+ * max_moves + 1 positions); synchronises.  mz_replay_clear_reanalysed and a
+ * game stored into the slot reset both fields.                              */
+int mz_replay_reanalyse_search(mz_handle* h, int32_t first, int32_t count, int exploration, uint32_t rng_step,
+                               uint32_t game_offset, void* stream);
+int mz_replay_get_reanalysed_policies(mz_handle* h, int32_t i, int32_t* is_set, float* child_visits);
+
 /* ---- Actor–learner loop (self_play! ‖ learning!) -----
  * The reference runs self_play! (SelfPlay.jl:384-419) and learning!
  * (Learning.jl:306-438) as two processes coupled by RemoteChannels (quirk

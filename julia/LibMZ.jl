@@ -197,6 +197,20 @@ function get_reanalysed(e::Engine, i, max_moves)   # shard game i: `nothing`, or
     set[] == 0 ? nothing : v
 end
 
+# The other half of Reanalyze: the selected games' stored positions are searched again with the current networks;
+# their child_visits become the policy targets and the search's root values the bootstrap values.  Position pos of
+# selected game gi is searched as the game with Philox id game_offset + gi*(max_moves+1) + pos at rng_step.
+reanalyse_search!(e::Engine; first=0, count=-1, exploration=false, rng_step=0, game_offset=0) =
+    check(e, ccall((:mz_replay_reanalyse_search, libmz), Cint,
+                   (Ptr{Cvoid}, Int32, Int32, Cint, UInt32, UInt32, Ptr{Cvoid}),
+                   e.h, first, count, exploration ? 1 : 0, rng_step, game_offset, C_NULL))
+function get_reanalysed_policies(e::Engine, i, A, max_moves)   # shard game i: `nothing`, or (A, max_moves + 1) child_visits
+    set = Ref{Int32}(0); cv = zeros(Float32, A, max_moves + 1)
+    check(e, ccall((:mz_replay_get_reanalysed_policies, libmz), Cint, (Ptr{Cvoid}, Int32, Ref{Int32}, Ptr{Float32}),
+                   e.h, i, set, cv))
+    set[] == 0 ? nothing : cv
+end
+
 """The actor–learner loop of self_play! ‖ learning! (src/SelfPlay.jl:384-419,
 src/Learning.jl:306-438; quirk Q16) on one GPU: `moves` self-play moves with the
 actors' nets, one learner step per finished game, the actors one checkpoint behind.

@@ -86,6 +86,9 @@ SIGNATURES = {
     "mz_replay_clear_reanalysed": (ctypes.c_int, [_VP, _VP]),
     "mz_replay_reanalysed_count": (ctypes.c_int, [_VP, _VP]),
     "mz_replay_get_reanalysed": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP]),
+    "mz_replay_reanalyse_search": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_uint32,
+                                                  ctypes.c_uint32, _VP]),
+    "mz_replay_get_reanalysed_policies": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP]),
     "mz_learner_set_mode": (ctypes.c_int, [_VP, ctypes.c_int]),
     "mz_train_init": (ctypes.c_int, [_VP, ctypes.c_int32]),
     "mz_train_init_at": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int64]),
@@ -528,6 +531,25 @@ class Engine:
         if not s.value:
             return None
         return v[:len(self.replay_get_game(i).action_history)].copy()
+
+    def replay_reanalyse_search(self, first=0, count=-1, exploration=False, rng_step=0, game_offset=0, stream=None):
+        """The stored positions of shard games first .. first+count-1 searched again with the current
+        networks (position pos of selected game gi as mcts_search's game with Philox id
+        game_offset + gi*(max_moves+1) + pos); stream-ordered, no host synchronisation.  Targets sampled
+        afterwards take their policies from the new child_visits and bootstrap from the new root values."""
+        self._check(self.lib.mz_replay_reanalyse_search(self.h, first, count, int(exploration),
+                                                        rng_step & 0xffffffff, game_offset & 0xffffffff, stream),
+                    "mz_replay_reanalyse_search")
+
+    def replay_get_reanalysed_policies(self, i):
+        """Shard game i (0 = oldest held): its reanalysed child_visits (T, A) float32, or None if unset."""
+        cv = np.zeros((self.conf.max_moves + 1, self.A), np.float32)
+        s = ctypes.c_int32()
+        self._check(self.lib.mz_replay_get_reanalysed_policies(self.h, i, ctypes.byref(s), _p(cv)),
+                    "mz_replay_get_reanalysed_policies")
+        if not s.value:
+            return None
+        return cv[:len(self.replay_get_game(i).action_history)].copy()
 
     def selfplay_slots(self):
         G = self.sp_G

@@ -78,6 +78,8 @@ extern "C" __global__ void mz_reanalyse_fc(ReanParams Q);
 extern "C" __global__ void mz_reanalyse_gather(ReanParams Q);
 extern "C" __global__ void mz_reanalyse_scatter(ReanParams Q);
 extern "C" __global__ void mz_reanalyse_clear(int32_t* rean, int cap);
+extern "C" __global__ void mz_reanalyse_sgather(ReanParams Q);
+extern "C" __global__ void mz_reanalyse_sscatter(ReanParams Q);
 extern "C" __global__ void mz_search_small1(SmallParams P);
 extern "C" __global__ void mz_search_small2(SmallParams P);
 extern "C" __global__ void mz_search_small4(SmallParams P);
@@ -317,6 +319,11 @@ struct mz_handle {
     float *d_rn_x = nullptr, *d_rn_h = nullptr, *d_rn_v = nullptr, *d_rn_p = nullptr;
     int rn_cap = 0;
     size_t rean_lds = 0;                    // mz_reanalyse_fc's dynamic-LDS attribute
+    // mz_replay_reanalyse_search: the io of one batched search of max_games rows (in sp_allocs,
+    // allocated with sp_ring.rcv at the first call that has work)
+    float *d_rq_obs = nullptr, *d_rq_cv = nullptr, *d_rq_rv = nullptr;
+    uint8_t* d_rq_legal = nullptr;
+    int32_t *d_rq_tp = nullptr, *d_rq_act = nullptr, *d_rq_state = nullptr;
     // L learner steps per launch pair (mz_learner_train_multi_dev, ChainParams): the bank of
     // MZ_MULTI_MAX small-kernel images (θ_t .. θ_{t+L-1}), per-step batches, read-outs,
     // loss terms, Σθ² partials, fold counters and losses, for batches up to ml_cap
@@ -3262,6 +3269,7 @@ int mz_selfplay_init(mz_handle* h, int env_kind, int G, int replay_games) {
     MZ_TRY(h, spalloc(h, &h->sp_ring.rrv, (size_t)replay_games * h->sp_T));
     MZ_TRY(h, spalloc(h, &h->sp_ring.rean, (size_t)replay_games));
     h->rn_cap = 0;                              // the ResNet staging buffers were in sp_allocs
+    h->sp_ring.rcv = nullptr; h->d_rq_obs = nullptr;    // so were rcv and the reanalyse search's io
     MZ_TRY(h, spalloc(h, &h->d_sp_counters, 4));
     MZ_TRY(h, spalloc(h, &h->d_sp_done, (size_t)G));
     MZ_TRY(h, spalloc(h, &h->d_sp_rpos, (size_t)G));
@@ -4268,9 +4276,82 @@ int mz_replay_get_reanalysed(mz_handle* h, int32_t i, int32_t* is_set, float* va
     int32_t set = 0, len = 0;
     MZ_TRY(h, hipMemcpy(&set, h->sp_ring.rean + slot, 4, hipMemcpyDeviceToHost));
     MZ_TRY(h, hipMemcpy(&len, h->sp_ring.len + slot, 4, hipMemcpyDeviceToHost));
+    set &= MZ_REAN_VALUES;
     if (is_set) *is_set = set != 0;
     if (values && set)
         MZ_TRY(h, hipMemcpy(values, h->sp_ring.rrv + (size_t)slot * h->sp_T, (size_t)len * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- Reanalyse by search: gather -> the batched search -> scatter per max_games rows
+int mz_replay_reanalyse_search(mz_handle* h, int32_t first, int32_t count, int exploration, uint32_t rng_step,
+                               uint32_t game_offset, void* stream) {
+    if (!h) return -2;
+    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
+    if (h->sp_frames > 0 || h->ds) return fail(h, "reanalyse: frame-stack env not built");
+    if (first < 0) return fail(h, "reanalyse: first must be >= 0");
+    if ((long long)h->sp_cap * h->sp_T > 0x7fffffffLL) return fail(h, "reanalyse: shard too large");
+    MZ_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    // as mz_replay_reanalyse: the rows cover the selection clipped to the capacity, the kernels
+    // clip it to the held range
+    const int gmax = count < 0 ? h->sp_cap - first : std::min<int>(count, h->sp_cap - first);
+    ++h->pf_epoch;                                  // a batch drawn ahead has the old targets
+    if (gmax <= 0) return 0;
+    const size_t Gc = (size_t)h->max_games, A = (size_t)h->A;
+    if (!h->d_rq_obs) {
+        MZ_TRY(h, spalloc(h, &h->sp_ring.rcv, (size_t)h->sp_cap * h->sp_T * A, false));
+        MZ_TRY(h, spalloc(h, &h->d_rq_legal, Gc * A, false));
+        MZ_TRY(h, spalloc(h, &h->d_rq_tp, Gc, false));
+        MZ_TRY(h, spalloc(h, &h->d_rq_cv, Gc * A, false));
+        MZ_TRY(h, spalloc(h, &h->d_rq_rv, Gc, false));
+        MZ_TRY(h, spalloc(h, &h->d_rq_act, Gc, false));
+        MZ_TRY(h, spalloc(h, &h->d_rq_state, Gc, false));
+        MZ_TRY(h, spalloc(h, &h->d_rq_obs, Gc * h->obs_feat, false));
+    }
+    ReanParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.first = first; Q.count = count;
+    Q.T = h->sp_T; Q.osz = h->sp_osz; Q.P = h->plane; Q.F = h->obs_feat; Q.stacked = h->conf.stacked_observations;
+    Q.cap = h->sp_cap; Q.ring = h->sp_ring; Q.counters = h->d_sp_counters;
+    Q.env = h->sp_env; Q.W = h->conf.observation_shape[0]; Q.H = h->conf.observation_shape[1]; Q.A = h->A;
+    Q.players = h->conf.players;
+    Q.stage_x = h->d_rq_obs; Q.stage_legal = h->d_rq_legal; Q.stage_tp = h->d_rq_tp; Q.stage_state = h->d_rq_state;
+    Q.stage_cv = h->d_rq_cv; Q.stage_rv = h->d_rq_rv;
+    const int npos = gmax * h->sp_T;
+    for (int p0 = 0; p0 < npos; p0 += (int)Gc) {
+        const int pn = std::min<int>((int)Gc, npos - p0);
+        Q.p0 = p0; Q.pn = pn;
+        hipLaunchKernelGGL(mz_reanalyse_sgather, dim3((pn + 3) / 4), dim3(256), 0, st, Q);
+        MZ_TRY(h, hipGetLastError());
+        // row i is game i of this batch: its Philox id game_offset + p0 + i depends on (selection, position) only
+        int rc = search_dev(h, pn, h->d_rq_obs, h->d_rq_legal, h->d_rq_tp, exploration, rng_step,
+                            game_offset + (uint32_t)p0, 0.0f, h->d_rq_cv, h->d_rq_rv, h->d_rq_act, st, nullptr);
+        if (rc) return rc;
+        hipLaunchKernelGGL(mz_reanalyse_sscatter, dim3((pn * (int)A + 255) / 256), dim3(256), 0, st, Q);
+        MZ_TRY(h, hipGetLastError());
+    }
+    return 0;
+}
+
+int mz_replay_get_reanalysed_policies(mz_handle* h, int32_t i, int32_t* is_set, float* child_visits) {
+    if (!h) return -2;
+    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);
+    long long played = 0;
+    MZ_TRY(h, hipMemcpy(&played, h->d_sp_counters, sizeof(played), hipMemcpyDeviceToHost));
+    const long long held = std::min<long long>(played, h->sp_cap);
+    if (i < 0 || i >= held) return fail(h, "game index out of range");
+    const int slot = (int)((played - held + i) % h->sp_cap);
+    int32_t set = 0, len = 0;
+    MZ_TRY(h, hipMemcpy(&set, h->sp_ring.rean + slot, 4, hipMemcpyDeviceToHost));
+    MZ_TRY(h, hipMemcpy(&len, h->sp_ring.len + slot, 4, hipMemcpyDeviceToHost));
+    set = (set & MZ_REAN_POLICIES) && h->sp_ring.rcv;
+    if (is_set) *is_set = set;
+    if (child_visits && set)
+        MZ_TRY(h, hipMemcpy(child_visits, h->sp_ring.rcv + (size_t)slot * h->sp_T * h->A, (size_t)len * h->A * 4,
+                            hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -8,8 +8,16 @@
 //
 // The selected games' positions are flattened as p = game · T + pos
 // (T = max_moves + 1, the ring's row length); pos >= len is dead.
+//
+// The second half (mz_replay_reanalyse_search, at the end of this file)
+// searches the same rows again: mz_reanalyse_sgather builds the inputs of one
+// batched search per max_games rows, the engine's search launches run, and
+// mz_reanalyse_sscatter writes child_visits to ring.rcv and the search's root
+// values to ring.rrv.  ring.rean is a bit mask: MZ_REAN_VALUES (rrv valid),
+// MZ_REAN_POLICIES (rcv valid).
 #include "mz_mlp_device.h"
 #include "mz_replay_device.h"
+#include "mz_env_device.h"
 
 // The held range and the selection, from the device counter (no host sync):
 // returns the number of selected games that are held, *oldest = game number
@@ -31,9 +39,11 @@ __device__ __forceinline__ bool rean_pos(const ReanParams& Q, long long oldest, 
     return *pos < Q.ring.len[*slot];
 }
 
-// pos 0 of a live game marks it (every stored game has len >= 1)
-__device__ __forceinline__ void rean_mark(const ReanParams& Q, int slot) {
-    Q.ring.rean[slot] = 1;
+// pos 0 of a live game marks it (every stored game has len >= 1): ORs `bits`
+// (MZ_REAN_VALUES / MZ_REAN_POLICIES) into the slot's mask, so a value-only
+// pass keeps the policies an earlier search pass left
+__device__ __forceinline__ void rean_mark(const ReanParams& Q, int slot, int bits) {
+    atomicOr(Q.ring.rean + slot, bits);
     atomicAdd(reinterpret_cast<unsigned long long*>(Q.counters + 3), 1ull);
 }
 
@@ -86,7 +96,7 @@ extern "C" __global__ __launch_bounds__(MZ_THREADS) void mz_reanalyse_fc(ReanPar
         run_plan(Q.plan_root, Q.Wp, Q.Bp, act);
         if (live && wave == 0) {          // run_plan ended in a barrier
             Q.ring.rrv[(size_t)slot * Q.T + pos] = mz_post_act(Q.v_act, act[Q.v_out + lane]);
-            if (pos == 0) rean_mark(Q, slot);
+            if (pos == 0) rean_mark(Q, slot, MZ_REAN_VALUES);
         }
     }
 }
@@ -119,11 +129,72 @@ extern "C" __global__ __launch_bounds__(256) void mz_reanalyse_scatter(ReanParam
     int slot = 0, pos = 0;
     if (cnt <= 0 || !rean_pos(Q, oldest, cnt, Q.p0 + i, &slot, &pos)) return;
     Q.ring.rrv[(size_t)slot * Q.T + pos] = Q.stage_v[i];
-    if (pos == 0) rean_mark(Q, slot);
+    if (pos == 0) rean_mark(Q, slot, MZ_REAN_VALUES);
 }
 
 // every held or stale slot back to `nothing`
 extern "C" __global__ void mz_reanalyse_clear(int32_t* rean, int cap) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < cap) rean[i] = 0;
+}
+
+// ---- Reanalyse by search (mz_replay_reanalyse_search): rows [p0, p0 + pn) of
+// the flattened grid become the games of one batched search, gather -> the
+// engine's search launches -> scatter.
+//
+// One wave per row: the inputs mz_sp_prepare gave the search when the move was
+// played — the stacked observation, to_play = tp[pos], the legal mask of the
+// stored board for that player (env_legal_board, over = 0: a stored position
+// was played from) — or the dummy (zero observation, every action legal,
+// to_play 1) for a dead row and for a row the search must not see: an empty
+// mask, or a to_play outside 1..players (both only from mz_replay_save_game
+// with arbitrary bytes).
+extern "C" __global__ __launch_bounds__(256) void mz_reanalyse_sgather(ReanParams Q) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= Q.pn) return;
+    long long oldest;
+    const int cnt = rean_games(Q, &oldest);
+    float* out = Q.stage_x + (size_t)i * Q.F;
+    int slot = 0, pos = 0, state = MZ_REAN_DEAD, tp = 1;
+    uint32_t m = Q.A >= 32 ? 0xFFFFFFFFu : (1u << Q.A) - 1u;
+    if (cnt > 0 && rean_pos(Q, oldest, cnt, Q.p0 + i, &slot, &pos)) {
+        const size_t base = (size_t)slot * Q.T;
+        const int t = Q.ring.tp[base + pos];
+        uint32_t lm = 0;
+        if (t >= 1 && t <= Q.players)
+            lm = env_legal_board(Q.env, Q.ring.obs + (base + pos) * Q.osz, t, 0, Q.W, Q.H, Q.A) & m;
+        state = lm ? MZ_REAN_LIVE : MZ_REAN_EMPTY;
+        if (lm) { m = lm; tp = t; }
+    }
+    if (state == MZ_REAN_LIVE) {
+        const size_t base = (size_t)slot * Q.T;
+        stacked_obs(out, Q.ring.obs + (base + pos) * Q.osz, Q.ring.obs + base * Q.osz, Q.ring.act + base, pos + 1,
+                    Q.osz, Q.P, Q.stacked, lane);
+    } else {
+        for (int k = lane; k < Q.F; k += 64) out[k] = 0.0f;
+    }
+    for (int a = lane; a < Q.A; a += 64) Q.stage_legal[(size_t)i * Q.A + a] = (m >> a) & 1u;
+    if (lane == 0) { Q.stage_tp[i] = tp; Q.stage_state[i] = state; }
+}
+
+// One thread per (row, action): a searched row's child_visits and root value
+// go to rcv / rrv, an unsearched stored position keeps copies of its originals,
+// a dead row writes nothing; pos 0 sets both flag bits and counts the game.
+extern "C" __global__ __launch_bounds__(256) void mz_reanalyse_sscatter(ReanParams Q) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= Q.pn * Q.A) return;
+    const int i = e / Q.A, a = e - i * Q.A;
+    const int state = Q.stage_state[i];
+    if (state == MZ_REAN_DEAD) return;
+    long long oldest;
+    const int cnt = rean_games(Q, &oldest);
+    int slot = 0, pos = 0;
+    if (cnt <= 0 || !rean_pos(Q, oldest, cnt, Q.p0 + i, &slot, &pos)) return;
+    const size_t r = (size_t)slot * Q.T + pos;
+    const bool live = state == MZ_REAN_LIVE;
+    Q.ring.rcv[r * Q.A + a] = live ? Q.stage_cv[(size_t)i * Q.A + a] : Q.ring.cv[r * Q.A + a];
+    if (a == 0) {
+        Q.ring.rrv[r] = live ? Q.stage_rv[i] : Q.ring.rv[r];
+        if (pos == 0) rean_mark(Q, slot, MZ_REAN_VALUES | MZ_REAN_POLICIES);
+    }
 }

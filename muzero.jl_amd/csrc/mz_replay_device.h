@@ -152,12 +152,14 @@ __device__ __forceinline__ void rp_sample_one(const RpSampleParams& Q, int b, in
         pos = (int)mz_rng_below(rp, (uint32_t)T) + 1;              // :80
     }
     const int K1 = Q.K + 1, A = Q.A;
-    // the bootstrap values: reanalysed_predicted_root_values unless `nothing` (ReplayBuffer.jl:8)
-    const float* rv = (Q.ring.rean[slot] ? Q.ring.rrv : Q.ring.rv) + base;
+    // the bootstrap values: reanalysed_predicted_root_values unless `nothing` (ReplayBuffer.jl:8);
+    // the policy targets: the reanalyse search's child_visits if the game has them
+    const int rean = Q.ring.rean[slot];
+    const float* rv = (rean & MZ_REAN_VALUES ? Q.ring.rrv : Q.ring.rv) + base;
     const int32_t* tp = Q.ring.tp + base;
     const float* rew = Q.ring.rew + base;
     const int32_t* act = Q.ring.act + base;
-    const float* cv = Q.ring.cv + base * A;
+    const float* cv = (rean & MZ_REAN_POLICIES ? Q.ring.rcv : Q.ring.cv) + base * A;
     const float uni = 1.0f / (float)A;
     for (int k = lane; k < K1; k += 64) {                          // make_target (:25-50)
         const int ci = pos + k;

@@ -17,20 +17,10 @@
 #include "mz_internal.h"
 #include "mz_selfplay_params.h"
 #include "mz_replay_device.h"
+#include "mz_env_device.h"
 
 // ------------------------------------------------------------------- envs
-__constant__ int8_t c_ttt_lines[8][3] = {{0, 3, 6}, {1, 4, 7}, {2, 5, 8}, {0, 1, 2},
-                                          {3, 4, 5}, {6, 7, 8}, {0, 4, 8}, {6, 4, 2}};
-
-// TicTacToe (game.jl:102-115, Q14): a line on the plane of player p
-__device__ __forceinline__ bool ttt_line(const uint8_t* b, int p) {
-    const uint8_t* pl = b + 9 * (p - 1);
-    bool any = false;
-#pragma unroll
-    for (int l = 0; l < 8; ++l) any |= pl[c_ttt_lines[l][0]] && pl[c_ttt_lines[l][1]] && pl[c_ttt_lines[l][2]];
-    return any;
-}
-
+// (ttt_line and the legal-action rule on a board: mz_env_device.h)
 __device__ __forceinline__ bool c4_wins(const uint8_t* stones, int w, int h, int W, int H) {
     const int dw[4] = {1, 0, 1, 1}, dh[4] = {0, 1, 1, -1};
     for (int d = 0; d < 4; ++d) {
@@ -67,18 +57,8 @@ __device__ void atari_reset(const SpParams& S, int g, uint32_t step, int lane) {
 
 // legal actions (1..A) as a bit mask
 __device__ uint32_t env_legal(const SpParams& S, int g) {
-    const uint8_t* b = S.board + (size_t)g * S.osz;
-    uint32_t m = 0;
-    if (S.env == MZ_ENV_ATARI) return S.A >= 32 ? 0xFFFFFFFFu : (1u << S.A) - 1u;
-    if (S.env == MZ_ENV_TICTACTOE) {                    // game.jl:37-43
-        if (ttt_line(b, S.player[g])) return 0;
-        for (int c = 0; c < 9; ++c) m |= (uint32_t)b[18 + c] << c;
-    } else {
-        if (S.over[g]) return 0;
-        const int cells = S.W * S.H;
-        for (int h = 0; h < S.H; ++h) m |= (uint32_t)b[2 * cells + (S.W - 1) + S.W * h] << h;
-    }
-    return m;
+    return env_legal_board(S.env, S.board + (size_t)g * S.osz, S.player[g], S.env == MZ_ENV_CONNECT4 ? S.over[g] : 0,
+                           S.W, S.H, S.A);
 }
 
 // env(action) (game.jl:45-52) + is_terminated / reward (:85-100): returns the

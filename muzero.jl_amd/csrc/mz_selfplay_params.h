@@ -28,8 +28,12 @@ struct SpHist {                 // a set of game records: [n][T] ...
     float* gprio;               // [n] PER game priority = max(prio) (ring only)
     // Reanalyse (ReplayBuffer.jl:8, 56-67; mz_reanalyse.hip), ring only (null in `hist`)
     float* rrv;                 // [n][T] reanalysed_predicted_root_values
-    int32_t* rean;              // [n] 0 = `nothing`, else rrv holds the slot's whole game
+    int32_t* rean;              // [n] bit mask, 0 = `nothing`: bit 1 = rrv, bit 2 = rcv hold the slot's whole game
+    float* rcv;                 // [n][T][A] reanalysed child_visits (mz_replay_reanalyse_search; null before its first call)
 };
+
+enum { MZ_REAN_VALUES = 1, MZ_REAN_POLICIES = 2 };                  // SpHist.rean bits
+enum { MZ_REAN_DEAD = 0, MZ_REAN_LIVE = 1, MZ_REAN_EMPTY = 2 };     // ReanParams.stage_state
 
 // mz_replay_reanalyse on the shard's games first .. first+count-1 (0 = oldest
 // held; games past the held range are skipped on the device)
@@ -45,6 +49,14 @@ struct ReanParams {
     int p0, pn;
     float* stage_x;             // [pn][F] gathered stacked observations
     const float* stage_v;       // [pn] value-head outputs
+    // mz_replay_reanalyse_search: rows [p0, p0 + pn) of the same grid are the games of one batched
+    // search (stage_x = its obs); the env rules of mz_env_device.h rebuild each row's legal mask
+    int env, W, H, A, players;
+    uint8_t* stage_legal;       // [pn][A]
+    int32_t* stage_tp;          // [pn]
+    int32_t* stage_state;       // [pn] MZ_REAN_DEAD (pos >= len, or past the held range), _LIVE, _EMPTY (no legal action)
+    const float* stage_cv;      // [pn][A] the search's child_visits
+    const float* stage_rv;      // [pn] the search's root_value
 };
 
 struct SpParams {

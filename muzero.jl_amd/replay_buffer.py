@@ -52,12 +52,14 @@ def make_target(conf, h, state_index, seed=0, sample=0, step=0):
     tp = np.zeros((K + 1, A), np.float32)
     ta = np.zeros(K + 1, np.float32)
     uni = np.float32(1.0) / np.float32(A)
+    # the policy targets: the reanalyse search's child_visits unless that field is None
+    cvs = h.child_visits if h.reanalysed_child_visits is None else h.reanalysed_child_visits
     for k in range(K + 1):
         ci = state_index + k
         if ci < T:
             tv[k] = compute_target_value(conf, h, ci)
             tr[k] = h.reward_history[ci - 1]
-            tp[k] = h.child_visits[ci - 1]
+            tp[k] = cvs[ci - 1]
             ta[k] = h.action_history[ci - 1]
         elif ci == T:
             tr[k] = h.reward_history[ci - 1]
@@ -67,6 +69,29 @@ def make_target(conf, h, state_index, seed=0, sample=0, step=0):
             tp[k] = uni
             ta[k] = rng_below(rng_u32(seed, MZ_RNG_ABSORB, sample, step, k), A) + 1
     return tv, tr, tp, ta
+
+
+_TTT_LINES = np.array([[0, 3, 6], [1, 4, 7], [2, 5, 8], [0, 1, 2], [3, 4, 5], [6, 7, 8], [0, 4, 8], [6, 4, 2]])
+
+
+def stored_legal_mask(conf, obs, to_play):
+    """Legal actions (A,) uint8 of `to_play` on a stored board (planes [p1, p2,
+    empty], col-major cells) — env_legal_board of the kernels with over = 0:
+    TicTacToe (3, 3, 3): the empty cells, none if to_play holds a line (Q14);
+    Connect4 (6, 7, 3): the top cell of each column.  A to_play outside the
+    players gives the empty mask."""
+    W, H, C = conf.observation_shape
+    b = np.asarray(obs).reshape(-1) != 0
+    if C != 3 or (W, H) not in ((3, 3), (6, 7)):
+        raise ValueError("stored_legal_mask: a TicTacToe or Connect4 board is needed")
+    if to_play not in conf.players:
+        return np.zeros(len(conf.action_space), np.uint8)
+    cells = W * H
+    if (W, H) == (3, 3):
+        if b[9 * (to_play - 1): 9 * to_play][_TTT_LINES].all(axis=1).any():
+            return np.zeros(9, np.uint8)
+        return b[18:27].astype(np.uint8)
+    return b[2 * cells + (W - 1) + W * np.arange(H)].astype(np.uint8)
 
 
 def per_priority(x, alpha):
@@ -214,6 +239,49 @@ class ReplayBuffer:
             if v.shape[0] != T:
                 raise ValueError(f"value_fn returned {v.shape[0]} values for {T} positions")
             h.reanalysed_predicted_root_values = [np.float32(t) for t in v]
+            self.num_reanalysed_games += 1
+            done.append(gid)
+        return done
+
+    def reanalyse_search(self, search_fn, game_ids=None):
+        """The other half of Reanalyze (mz_replay_reanalyse_search's mirror): every
+        stored position of each game is searched again.  search_fn(obs (T, feat),
+        legal (T, A) uint8, to_play (T,), p0) -> (child_visits (T, A), root_values
+        (T,)); p0 = gi * (max_moves + 1) is the game's first row in the flattened
+        selection (gi counts the ids as given, skipped ones included), the offset
+        of its Philox game ids.  legal comes from the stored board: the empty
+        plane's cells (TicTacToe, none if the player to move holds a line, Q14)
+        or the top cell of each column (Connect4).  A position with no legal
+        action is not searched and keeps its stored child_visits / root_values.
+        An id that has left the buffer is skipped (update_history!'s check).
+        Returns the ids updated."""
+        c = self.conf
+        if self.frame_stack:
+            raise ValueError("reanalyse: frame-stack env not built")
+        plane = c.observation_shape[0] * c.observation_shape[1]
+        done = []
+        for gi, gid in enumerate(list(self.buffer.keys()) if game_ids is None else game_ids):
+            h = self.buffer.get(gid)
+            if h is None:
+                continue
+            T = len(h.root_values)
+            x = np.stack([get_stacked_observations(h.observation_history, h.action_history, i,
+                                                   c.stacked_observations, plane) for i in range(1, T + 1)])
+            legal = np.stack([stored_legal_mask(c, h.observation_history[i], h.to_play_history[i]) for i in range(T)])
+            live = legal.any(axis=1)
+            cv = np.array(h.child_visits, np.float32)
+            rv = np.array(h.root_values, np.float32)
+            if live.any():
+                # unsearched rows go to search_fn as the dummy: zero observation, all legal, to_play 1
+                xs, ls = np.where(live[:, None], x, np.float32(0)), np.where(live[:, None], legal, np.uint8(1))
+                tps = np.where(live, np.array(h.to_play_history, np.int32), 1).astype(np.int32)
+                ncv, nrv = search_fn(xs, ls, tps, gi * (c.max_moves + 1))
+                ncv, nrv = np.asarray(ncv, np.float32), np.asarray(nrv, np.float32).reshape(-1)
+                if ncv.shape != cv.shape or nrv.shape != rv.shape:
+                    raise ValueError(f"search_fn returned {ncv.shape}, {nrv.shape} for {T} positions")
+                cv[live], rv[live] = ncv[live], nrv[live]
+            h.reanalysed_child_visits = [r for r in cv]
+            h.reanalysed_predicted_root_values = [np.float32(t) for t in rv]
             self.num_reanalysed_games += 1
             done.append(gid)
         return done

@@ -47,6 +47,7 @@ class GameHistory:                                               # Constructors.
     reanalysed_predicted_root_values: Optional[list] = None
     priorities: Optional[np.ndarray] = None
     game_priority: Optional[float] = None
+    reanalysed_child_visits: Optional[list] = None            # (A,) per move, from the reanalyse search
 
     def as_arrays(self):
         return dict(observation=np.array(self.observation_history, np.float32),

@@ -13,6 +13,16 @@ alternately in one process:
 Prints ONE JSON line: positions/s of both routes, the kernel's FLOP per
 position from the layer shapes (2 x MACs of representation + prediction, the
 policy head included: the root plan runs it) and the share of the f32 peak.
+
+--search times the other half, mz_replay_reanalyse_search over all held games
+(ceil(rows / games) rounds of gather -> batched search -> scatter, rows = cap x
+(max_moves + 1): dead rows are searched too), against its host route:
+replay_get_game + one mcts_search per game (wall clock, over the first
+--host-games games; the results stay on the host).  Its JSON line carries the
+fraction of searched rows that were live and, given --search-ms (ms_per_step
+of a plain bench.py run of the parent commit on the same machine, i.e. one
+batched search of `games` games), the figure to judge the pass against:
+rounds x that launch time, and the gap to it.
 """
 import argparse
 import dataclasses
@@ -46,14 +56,90 @@ def host_route(eng, conf, held):
     return time.perf_counter() - t0, v, games
 
 
+def host_search_route(eng, conf, n_games):
+    """replay_get_game + mcts_search per game; returns (seconds, positions, [(child_visits, root_values)])."""
+    plane = conf.observation_shape[0] * conf.observation_shape[1]
+    Tm = conf.max_moves + 1
+    t0 = time.perf_counter()
+    out, positions = [], 0
+    for gi in range(n_games):
+        h = eng.replay_get_game(gi)
+        T = len(h.root_values)
+        x = np.stack([get_stacked_observations(h.observation_history, h.action_history, i, conf.stacked_observations,
+                                               plane) for i in range(1, T + 1)])
+        legal = np.stack(h.observation_history)[:, 2 * plane:].astype(np.uint8)
+        cv, rv, _ = eng.mcts_search(x, legal, np.array(h.to_play_history, np.int32), exploration=False, rng_step=0,
+                                    game_offset=gi * Tm, temperature=0.0)
+        out.append((cv, rv))
+        positions += T
+    return time.perf_counter() - t0, positions, out
+
+
+def search_mode(a, eng, conf, held, ts, st):
+    Tm = conf.max_moves + 1
+    rows = a.cap * Tm                       # the selection clipped to the capacity: what the pass searches
+    rounds_per_pass = -(-rows // a.games)
+    for _ in range(2):                                        # warm-up (the first call allocates)
+        eng.replay_reanalyse_search(stream=st)
+    torch.cuda.synchronize()
+    dev_s, issue_s, reps = [], [], 2
+    for r in range(a.rounds):
+        while True:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(ts)
+            t_issue = time.perf_counter()
+            for _ in range(reps):
+                eng.replay_reanalyse_search(stream=st)
+            issued = time.perf_counter() - t_issue
+            e1.record(ts)
+            e1.synchronize()
+            ms = e0.elapsed_time(e1)
+            print(f"round {r}: {reps} passes, {ms:.3f} ms on the device, issued in {issued * 1e3:.3f} ms", file=sys.stderr)
+            if ms >= 500.0:
+                break
+            reps = int(reps * min(100.0, max(2.0, 650.0 / max(ms, 1e-3))))
+        dev_s.append(ms * 1e-3 / reps)
+        issue_s.append(issued / reps)
+    n_host = min(a.host_games, held)
+    host_t, host_pos, host_out = host_search_route(eng, conf, n_host)
+    agree = all(np.array_equal(eng.replay_get_reanalysed_policies(gi), cv) and
+                np.array_equal(eng.replay_get_reanalysed(gi), rv) for gi, (cv, rv) in enumerate(host_out))
+    positions = sum(len(eng.replay_get_game(i).root_values) for i in range(held))
+    d = float(np.median(dev_s))
+    out = {
+        "tool": "reanalyse_bench", "mode": "search", "engine": "tictactoe fc", "games_held": int(held),
+        "sims_per_move": conf.num_iters, "rows_per_round": a.games, "positions": positions, "rows_searched": rows,
+        "live_fraction": round(positions / rows, 6), "rounds_per_pass": rounds_per_pass, "repeats": reps,
+        "rounds": a.rounds, "device_s_per_pass": round(d, 9), "device_positions_per_s": round(positions / d, 1),
+        "device_s_per_round": round(d / rounds_per_pass, 9),
+        "host_issue_s_per_pass": round(float(np.median(issue_s)), 9),
+        "host_games": n_host, "host_positions": host_pos, "host_s": round(host_t, 6),
+        "host_positions_per_s": round(host_pos / host_t, 1),
+        "speedup": round((host_t / host_pos) / (d / positions), 1), "routes_agree": bool(agree)}
+    if a.search_ms:
+        ref = rounds_per_pass * a.search_ms * 1e-3
+        out.update({"parent_search_ms_per_launch": a.search_ms, "reference_s_per_pass": round(ref, 9),
+                    "gap_s_per_pass": round(d - ref, 9), "gap_us_per_round": round((d - ref) / rounds_per_pass * 1e6, 3)})
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--search", action="store_true", help="time mz_replay_reanalyse_search instead of the value pass")
+    ap.add_argument("--host-games", type=int, default=512, help="--search: games of the host route")
+    ap.add_argument("--search-ms", type=float, default=None,
+                    help="--search: the parent commit's ms_per_step of a plain bench.py run on the same machine")
     ap.add_argument("--games", type=int, default=512)
     ap.add_argument("--cap", type=int, default=4096)
     ap.add_argument("--moves", type=int, default=80)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--sims", type=int, default=None,
+                    help="simulations per move of the self-play that fills the shard and of the reanalyse search "
+                         "(default: the game's num_iters; --search: 50, bench.py's configs[1])")
     a = ap.parse_args()
     conf = dataclasses.replace(ttt.conf, replay_buffer_size=a.cap)
+    if a.sims or a.search:
+        conf = dataclasses.replace(conf, num_iters=a.sims or 50)
     eng = abi.Engine(conf, ttt.hyper, device=0, max_games=a.games, rng_seed=1)
     for n, w in enumerate(init_nets(conf, ttt.hyper, seed=1234)):
         eng.set_weights(n, w)
@@ -64,6 +150,10 @@ def main():
     eng.sync()
     ts = torch.cuda.Stream()              # its own stream: the events and the launches share it (a null handle
     st = ts.cuda_stream                   # would send the launches to the engine's stream, past the events)
+    if a.search:
+        search_mode(a, eng, conf, held, ts, st)
+        eng.close()
+        return
     for _ in range(5):                                        # warm-up
         eng.replay_reanalyse(stream=st)
     torch.cuda.synchronize()
