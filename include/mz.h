@@ -193,6 +193,13 @@ int mz_debug_enable(mz_handle* h, int flags);
 int mz_debug_tree(mz_handle* h, int G, int32_t* edge_N, float* edge_W, float* edge_P,
                   float* edge_R, int32_t* edge_child, int32_t* node_to_play);
 
+/* Debug/parity: with mz_debug_enable(h, 1) the small-batch search kernels
+ * (mz_search_small*) count, per game of the last search, the simulations whose
+ * leaf the constant-depth ballot select found (fast) and those that entered
+ * the serial level walk (walked); fast + walked = num_iters.  Any other search
+ * kernel leaves both at 0.  Either pointer may be NULL.                    */
+int mz_debug_select_stats(mz_handle* h, int G, int32_t* fast, int32_t* walked);
+
 /* Measurement: with mz_debug_enable(h, 2) every network launch of the
  * ResNet search (mz_rsearch_nets, its dominant kernel), with flag 4 every
  * learner unroll launch (mz_runroll_kernel, mz_learn_multi*), is bracketed by HIP events on

@@ -124,6 +124,18 @@ function mcts_search!(e::Engine, obs::Array{Float32,4}, legal::Matrix{UInt8}, to
     return child_visits, root_value, action
 end
 
+"""debug_select_stats(e, G) — per game of the last small-kernel search (after
+mz_debug_enable flag 1): simulations whose leaf the ballot select found, and
+simulations that entered the serial walk."""
+debug_enable!(e::Engine, flags::Integer=1) =
+    check(e, ccall((:mz_debug_enable, libmz), Cint, (Ptr{Cvoid}, Cint), e.h, flags))
+function debug_select_stats(e::Engine, G::Integer)
+    fast = Vector{Int32}(undef, G); walked = Vector{Int32}(undef, G)
+    check(e, ccall((:mz_debug_select_stats, libmz), Cint, (Ptr{Cvoid}, Cint, Ptr{Int32}, Ptr{Int32}),
+                   e.h, G, fast, walked))
+    return fast, walked
+end
+
 # ParameterSchedulers 0.2.3 Cos(λ0=1e-4, λ1=1e-1, period=10) under Stateful (src/Learning.jl:319, 382);
 # the caller keeps the schedule (`next!(schedule)`) and passes eta
 cos_eta(t) = abs(1e-4 - 1e-1) * (1 + cos(2π * (t - 1) / 10)) / 2 + min(1e-4, 1e-1)

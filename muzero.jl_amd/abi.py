@@ -57,6 +57,7 @@ SIGNATURES = {
     "mz_set_sync_stream": (ctypes.c_int, [_VP, _VP, ctypes.c_int]),
     "mz_debug_tree": (ctypes.c_int, [_VP, ctypes.c_int, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mz_debug_unroll": (ctypes.c_int, [_VP, ctypes.c_int, _VP, _VP, _VP]),
+    "mz_debug_select_stats": (ctypes.c_int, [_VP, ctypes.c_int, _VP, _VP]),
     "mz_debug_kernel_time": (ctypes.c_int, [_VP, _VP, _VP]),
     "mz_learner_step": (ctypes.c_int, [_VP, ctypes.POINTER(MzBatch), ctypes.c_double, _VP]),
     "mz_grad_count": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_size_t)]),
@@ -270,6 +271,14 @@ class Engine:
         self._check(self.lib.mz_debug_tree(self.h, G, _p(eN), _p(eW), _p(eP), _p(eR), _p(eC), _p(ntp)),
                     "mz_debug_tree")
         return dict(N=eN, W=eW, P=eP, R=eR, C=eC, to_play=ntp)
+
+    def debug_select_stats(self, G):
+        """Per game of the last small-kernel search: (simulations whose leaf the
+        ballot select found, simulations that entered the serial walk)."""
+        fast = np.empty(G, np.int32)
+        walked = np.empty(G, np.int32)
+        self._check(self.lib.mz_debug_select_stats(self.h, G, _p(fast), _p(walked)), "mz_debug_select_stats")
+        return fast, walked
 
     def debug_kernel_time(self):
         """(summed ms, launches) of the timed network launches since the last call."""

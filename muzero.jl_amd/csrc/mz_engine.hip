@@ -283,6 +283,7 @@ struct mz_handle {
     unsigned* d_counter = nullptr;          // last-block counter of mz_learner_grad_kernel
     float* d_lterm = nullptr;               // [2][B(K+1)] loss terms
     unsigned long long* d_stamps = nullptr;
+    int32_t* d_sel_stats = nullptr;         // mz_debug_enable flag 1: [max_games][2] select counters of the small kernel
     // device self-play + replay shard (mz_selfplay.hip); own allocation list (re-init frees it)
     int sp_env = -1, sp_G = 0, sp_T = 0, sp_osz = 0, sp_cap = 0;
     uint8_t* d_sp_board = nullptr; int32_t* d_sp_player = nullptr; uint8_t* d_sp_over = nullptr;
@@ -831,6 +832,8 @@ static int build_small(mz_handle* h) {
         h->sm_lds[ti] = ints * 4 + (size_t)T * h->tree_game_bytes + pbterm_count(S) * 8 +
                         // the cached select: entries, path levels, N per slot, tags
                         (size_t)T * (8 * NN + 8 * (S + 2) + 4 * NN) + 16 + 4 * 16 + 4 * 8 + 4 * 4 +
+                        // the ballot select's node statics (trees of at most 64 nodes)
+                        (size_t)T * 16 * (NN <= 64 ? NN : 0) +
                         (any_bn ? nri * 8 : 0);                          // BatchNorm (γ, β) per record row
     }
     return 1;
@@ -1988,6 +1991,10 @@ static int search_dev(mz_handle* h, int G, const float* obs, const uint8_t* lega
         Q.pbc_tab = h->d_pbc; Q.sqrt_tab = h->d_sqrt; Q.aval_tab = h->d_aval;
         Q.pbterm = h->d_pbterm;
         Q.tree = h->d_tree; Q.tree_game_bytes = h->tree_game_bytes; Q.dump_tree = h->dump_tree;
+        if (h->dump_tree) {
+            if (!h->d_sel_stats) MZ_TRY(h, dalloc(h, &h->d_sel_stats, (size_t)2 * h->max_games));
+            Q.sel_stats = h->d_sel_stats;
+        }
 #ifdef MZ_STAMPS
         Q.stamps = h->d_stamps;
 #endif
@@ -2095,6 +2102,23 @@ int mz_debug_tree(mz_handle* h, int G, int32_t* eN, float* eW, float* eP, float*
                 if (eC) eC[k] = c;
             }
         }
+    }
+    return 0;
+}
+
+int mz_debug_select_stats(mz_handle* h, int G, int32_t* fast, int32_t* walked) {
+    if (!h) return -2;
+    if (G < 0 || G > h->max_games) return fail(h, "G exceeds max_games");
+    if (!h->dump_tree) return fail(h, "mz_debug_select_stats needs mz_debug_enable(h, 1) before the search");
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);
+    // only the small kernels count: any other search leaves both at 0
+    const bool small = h->d_sel_stats && h->last_variant.rfind("mz_search_small", 0) == 0;
+    std::vector<int32_t> buf((size_t)2 * G, 0);
+    if (small && G > 0) MZ_TRY(h, hipMemcpy(buf.data(), h->d_sel_stats, buf.size() * 4, hipMemcpyDeviceToHost));
+    for (int g = 0; g < G; ++g) {
+        if (fast) fast[g] = buf[2 * (size_t)g];
+        if (walked) walked[g] = buf[2 * (size_t)g + 1];
     }
     return 0;
 }

@@ -289,7 +289,12 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
     // [4] per game: the select's start level (the last path's prefix the
     // recompute found unchanged; 0 = from the root)
     int* c_skip = reinterpret_cast<int*>(c_mmx + 4);
-    float2* bnl = reinterpret_cast<float2*>(c_skip + 4);          // [nrec][slot][64] BatchNorm (γ, β) (P.bn)
+    // the ballot select's node statics (mz_tree_device.h select_path_ballot):
+    // [T][NN] 16-byte records while the tree fits one wave (NN <= 64), else none
+    const bool sel_ballot = NN <= 64;
+    const int NNS = sel_ballot ? NN : 0;
+    uint4* c_stat = reinterpret_cast<uint4*>(c_skip + 4);
+    float2* bnl = reinterpret_cast<float2*>(c_stat + T * NNS);    // [nrec][slot][64] BatchNorm (γ, β) (P.bn)
 
     const int tid = threadIdx.x;
     const int g = tid >> 4, a = tid & 15, lane = tid & 63;
@@ -332,6 +337,7 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
     }
     for (int i = tid; i < T * NN; i += SM_THREADS) c_cache[i] = make_uint2(0u, 0u);
     if (tid < 4) { c_hdr[tid] = make_int4(0, -1, 1, 0); c_mmx[tid] = make_float2(0.0f, 0.0f); c_skip[tid] = 0; }
+    if (tid < T && sel_ballot) c_stat[tid * NNS] = node_static(0, 0, 0, 1ull);   // the root: anc[0] = 1
     int ver = 1;                                                  // wave 0: the tag of this lane's game
     if (tree_thread && a == 0) {
         uint32_t m = 0;
@@ -379,10 +385,13 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
     SM_STAMP(0);
 
     const SmFusedIn fin{hid, sg_leaf_e, sg_leaf_a, l_aval, NN, H, P.plane, P.x_pred, P.x_dyn};
+    int n_fast = 0;      // wave w < T (uniform): simulations whose leaf the ballot pass found
     // Per simulation, three workgroup barriers besides the 8 network stages:
-    // wave 0 owns the trees (T <= 4 games x 16 lanes), so select -> gather and
-    // backup -> next select need only wave-local ordering.
+    // wave 0 owns the trees' updates (T <= 4 games x 16 lanes); wave w < T
+    // selects for game w, behind the recompute's barrier (the last simulation's
+    // backup and entries are visible) and in front of the one before stage 0.
     for (int s = 0; s < S; ++s) {
+#ifdef MZ_SELECT_WALK   // A/B: the serial walk on wave 0 for all T games
         if (tid < 64) {
             // ---- select (:256-268)
             if (active) {
@@ -402,15 +411,61 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
             }
             __builtin_amdgcn_wave_barrier();
             SM_STAMP(1);
-#ifdef MZ_STAMPS
-            if (threadIdx.x == 0) {             // slot 7: select levels walked (max over the T games)
-                int md = 0;
-                for (int gl = 0; gl < T; ++gl) md = md > sg_depth[gl] ? md : sg_depth[gl];
-                st_acc[7] += (unsigned long long)md;
-            }
-#endif
         }
+#else
+        if (tid < 64 * T) {
+            // ---- select (:256-268): wave w selects for game w.  The ballot pass
+            // reads the path off the cache in constant depth; when it stops at a
+            // tied or stale entry, lanes 0..15 of the same wave walk on from there.
+            const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+            if (tile0 + w < P.G) {
+                const TreeView tw = tree_view(lds_tree + (size_t)w * P.tree_game_bytes, E, NN);
+                int* pw = sg_path + w * PS;
+                const uint2* cw = c_cache + w * NN;
+                const uint32_t verw = (uint32_t)c_hdr[w].z;
+                const int rtp = sg_root_tp[w];
+                SelectOut so{0, 0, 1, 0};
+                int D, e0;
+                uint32_t npc0;
+                bool found = false;
+                if (sel_ballot) {
+                    found = select_path_ballot(tw, cw, c_stat + w * NNS, verw, pw, s + 1, s + 1, rtp, lane, A,
+                                               P.players, so, D, e0, npc0);
+                } else {                       // the tree outgrows one wave: the walk, from the skip-ahead level
+#ifdef MZ_NO_SKIP
+                    D = 0;
+#else
+                    D = c_skip[w];
+#endif
+                    e0 = D > 0 ? pw[2 * D + 1] : 0;
+                    npc0 = D > 0 ? tw.nc(pw[2 * D]) : 0u;
+                }
+                if (!found && lane < 16) {
+                    so = select_path_cached(tw, cw, verw, pw, sg_rootN[w], rtp, sg_legal[w], sg_mmin[w], sg_mmax[w],
+                                            lane, lane, A, P.players, l_pbterm, P.seed,
+                                            P.game_offset + (uint32_t)(tile0 + w), P.rng_step, s, nullptr, nullptr, D,
+                                            e0, npc0);
+                    if (sel_ballot && lane == 0) {          // the new node's statics (the walk outcome)
+                        const uint4 ps = c_stat[w * NNS + so.leaf_e];
+                        c_stat[w * NNS + s + 1] = node_static(so.leaf_e, so.depth, so.leaf_a,
+                                                              ((uint64_t)ps.y | ((uint64_t)ps.z << 32)) | (1ull << (s + 1)));
+                    }
+                }
+                if (lane == 0) { sg_leaf_e[w] = so.leaf_e; sg_leaf_a[w] = so.leaf_a; sg_vtp[w] = so.vtp; sg_depth[w] = so.depth; }
+                n_fast += found ? 1 : 0;
+            }
+            __builtin_amdgcn_wave_barrier();
+            SM_STAMP(1);
+        }
+#endif
         __syncthreads();
+#ifdef MZ_STAMPS
+        if (threadIdx.x == 0) {                 // slot 7: select levels walked (max over the T games)
+            int md = 0;
+            for (int gl = 0; gl < T; ++gl) md = md > sg_depth[gl] ? md : sg_depth[gl];
+            st_acc[7] += (unsigned long long)md;
+        }
+#endif
         SM_STAMP(2);
         // ---- prediction(parent.h) ‖ dynamics(2h ⊕ a/|A|): the first stage
         // reads the parent's h from the hidden-state store (gather fused)
@@ -521,6 +576,11 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
                               "+v"(l0.y), "+v"(n0));   // all issued together, one wait
             const bool full = hd.x != 0;
             const int n = full ? s + 2 : hd.y + 1;
+#ifdef MZ_NO_SKIP_MIN   // A/B: no skip-ahead bound while the ballot select runs (it does not read c_skip)
+            const bool skip_min = !sel_ballot;
+#else
+            const bool skip_min = true;
+#endif
             const bool lgl = a < A && (((uint32_t)hd.w >> a) & 1u);
             const TreeView tq = tree_view(lds_tree + (size_t)gq * P.tree_game_bytes, E, NN);
             uint2* cq = c_cache + gq * NN;
@@ -531,14 +591,14 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
             if (j0 < n) {
                 const int ch = cache_row(tq, cq, (uint32_t)hd.z, full ? j0 : (int)l0.x, full ? n0 : (int)l0.y, lgl,
                                          a, A, mm.x, mm.y, l_pbterm, lane);
-                if (!full && a == 0 && (j0 >= hd.y || ch != pe0 - (int)l0.x * A)) atomicMin(c_skip + gq, j0);
+                if (skip_min && !full && a == 0 && (j0 >= hd.y || ch != pe0 - (int)l0.x * A)) atomicMin(c_skip + gq, j0);
             }
             for (int j = j0 + SM_THREADS / 16 / T; j < n; j += SM_THREADS / 16 / T) {   // deep paths, large trees
                 int slot, Np;
                 if (full) { slot = j; Np = c_nN[gq * NN + j]; }
                 else { const uint2 l = c_lvl[gq * (S + 2) + j]; slot = (int)l.x; Np = (int)l.y; }
                 const int ch = cache_row(tq, cq, (uint32_t)hd.z, slot, Np, lgl, a, A, mm.x, mm.y, l_pbterm, lane);
-                if (!full && a == 0 && (j >= hd.y || ch != pq[2 * (j + 1)] - slot * A)) atomicMin(c_skip + gq, j);
+                if (skip_min && !full && a == 0 && (j >= hd.y || ch != pq[2 * (j + 1)] - slot * A)) atomicMin(c_skip + gq, j);
             }
             __syncthreads();
             SM_STAMP(6);                           // stamp build: slot 6 = the cache recompute (+ finish)
@@ -563,6 +623,10 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
             TreeView dst = tree_view(P.tree + (size_t)gg * P.tree_game_bytes, E, NN);
             dump_tree(tree, dst, E, NN, a);
         }
+    }
+    if (P.sel_stats && tid < 64 * T && lane == 0 && tile0 + (tid >> 6) < P.G) {   // (debug flag 1 only)
+        P.sel_stats[2 * (tile0 + (tid >> 6))] = n_fast;
+        P.sel_stats[2 * (tile0 + (tid >> 6)) + 1] = S - n_fast;
     }
 #ifdef MZ_STAMPS
     SM_STAMP(6);

@@ -72,6 +72,7 @@ struct SmallParams {
     const float4* zero16;    // 16 zero bytes: the address of a skipped chunk's load
     uint32_t nzm[SM_NZM_ALLOC];  // nonzero-chunk masks [wave][stage]: sim stages, then root stages (+ pad)
     int bn;                  // BatchNorm FC layers: `bias` has γ and β sections after the biases
+    int32_t* sel_stats;      // NULL or [G][2]: simulations whose leaf the ballot select found / that walked (debug)
 };
 
 // Learner unroll on the small-kernel schedule (mz_unroll_small*): T samples

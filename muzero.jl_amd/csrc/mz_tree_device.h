@@ -617,6 +617,69 @@ __device__ __forceinline__ SelectOut select_path_cached(const TreeView& t, const
     return SelectOut{e, lach, vtp, dg};
 }
 
+// ---------------------------------------------------------------------------
+// Ballot select (the small kernel, trees of at most 64 expanded nodes): the
+// cache says, for every expanded node, which child select would take, so the
+// selected path is a property of the whole table and one wave reads it off in
+// constant depth, one node per lane, instead of chasing it level by level.
+// Per node n its statics, fixed when n is created (one 16-byte record):
+//   .x  parent slot | depth << 8 | action into n << 16
+//   .y/.z  ancestor mask anc[n] = anc[par[n]] | 1 << n, anc[0] = 1
+// ok[n] = "n's parent has a current entry that chooses n"; with OK = ballot(ok)
+// | 1, node n lies on the selected path iff anc[n] is a subset of OK.  A parent
+// chooses one child, so the on-path nodes form a chain from the root; a child's
+// slot is larger than its parent's, so the chain's end L is the highest lane.
+// Every on-path lane writes its own path level.  When L's entry is current its
+// chosen child is unexpanded (an expanded one would be on the path, below L):
+// the leaf is found.  Otherwise (a tie, a stale entry, the root before the
+// first backup) the caller continues with select_path_cached from level
+// D = dep[L], node e0 = L, npc0 = the nc word of the edge into L.
+__device__ __forceinline__ uint4 node_static(int par, int dep, int act, uint64_t anc) {
+    return make_uint4((uint32_t)par | ((uint32_t)dep << 8) | ((uint32_t)act << 16), (uint32_t)anc,
+                      (uint32_t)(anc >> 32), 0u);
+}
+
+// Called by all 64 lanes of one wave for one game (every argument wave-
+// uniform but `lane`); n_nodes = expanded nodes so far (1..64), e_new the slot
+// the leaf will be expanded into (its statics are written here when the leaf
+// is found).  Returns true with `so` set, or false with (D, e0, npc0).
+__device__ __forceinline__ bool select_path_ballot(const TreeView& t, const uint2* cache, uint4* stat, uint32_t ver,
+                                                   int* path, int n_nodes, int e_new, int root_tp, int lane, int A,
+                                                   int players, SelectOut& so, int& D, int& e0, uint32_t& npc0) {
+    const bool ex = lane < n_nodes;
+    const int ln = ex ? lane : 0;
+    uint2 ce = cache[ln];
+    uint4 st = stat[ln];
+    asm volatile("" : "+v"(ce.x), "+v"(ce.y), "+v"(st.x), "+v"(st.y), "+v"(st.z));   // both reads issued, one wait
+    const int par = (int)(st.x & 0xffu), dep = (int)((st.x >> 8) & 0xffu), act = (int)(st.x >> 16);
+    const uint2 cp = cache[par];                          // the parent's entry (the second LDS round trip)
+    const int ein = (int)__umul24((unsigned)par, (unsigned)A) + act;   // the edge into this node
+    const bool cur = ex && (ce.x >> 5) == ver;
+    const bool okl = ex && lane >= 1 && (cp.x >> 5) == ver && (cp.y >> 16) == (uint32_t)(lane + 1);
+    const uint64_t OK = __builtin_amdgcn_ballot_w64(okl) | 1ull;
+    const uint64_t anc = (uint64_t)st.y | ((uint64_t)st.z << 32);
+    const bool on = ex && (anc & ~OK) == 0;
+    const uint64_t ON = __builtin_amdgcn_ballot_w64(on);  // (bit 0 is always set: anc[0] = 1)
+    const int L = 63 - __builtin_clzll(ON);
+    D = __builtin_popcountll(ON) - 1;                     // = dep[L]
+    if (on && lane >= 1) *reinterpret_cast<int2*>(path + 2 * dep) = make_int2(ein, lane);
+    const bool found = (__builtin_amdgcn_ballot_w64(cur) >> L) & 1u;
+    if (found) {
+        const int la = (int)((uint32_t)__builtin_amdgcn_readlane((int)ce.x, L) & 31u);
+        const int depth = D + 1;
+        if (lane == L) {
+            *reinterpret_cast<int2*>(path + 2 * depth) = make_int2((int)__umul24((unsigned)L, (unsigned)A) + la, -1);
+            stat[e_new] = node_static(L, depth, la, anc | (1ull << e_new));
+        }
+        const int vtp = players == 2 ? ((root_tp - 1 + depth) & 1) + 1 : (root_tp - 1 + depth) % players + 1;
+        so = SelectOut{L, la, vtp, depth};
+    } else {
+        e0 = L;
+        npc0 = D > 0 ? t.nc(__builtin_amdgcn_readlane(ein, L)) : 0u;
+    }
+    return found;
+}
+
 // backpropagate! (SelfPlay.jl:190-217), quirk Q7, for the GW-lane group.
 // Node d of the path (0 = root ... depth = the just-expanded leaf with
 // to_play tl) receives v_in(d): v_in(depth) = the leaf value; otherwise
