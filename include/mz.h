@@ -444,8 +444,10 @@ int mz_selfplay_slots(mz_handle* h, int32_t* history_len, uint8_t* board, int32_
  * and mz_selfplay_move / the learner calls on DIFFERENT streams must be
  * ordered by the caller (events); on one stream nothing is needed.  In the
  * split actor-learner loop the place for the call is between mz_train_move
- * and mz_train_learn, on their stream; mz_train_run never reanalyses (the
- * reference's loop has no reanalyse worker).
+ * and mz_train_learn, on their stream; mz_train_run never makes this call
+ * (the reference's loop has no reanalyse worker) — what it can run every move
+ * is the worker's round, mz_replay_reanalyse_next, once mz_train_set_reanalyse
+ * turns it on.
  * _clear_reanalysed: every held game back to `nothing`.  _reanalysed_count:
  * num_reanalysed_games, one per game per mz_replay_reanalyse since
  * mz_selfplay_init; synchronises.  _get_reanalysed (parity): game i's flag
@@ -480,7 +482,8 @@ int mz_replay_get_reanalysed(mz_handle* h, int32_t i, int32_t* is_set, float* va
  * the place in the split loop are as for mz_replay_reanalyse: between
  * mz_train_move and mz_train_learn, on their stream (the search uses the
  * engine's one set of tree buffers, as mz_selfplay_move does); mz_train_run
- * never reanalyses.  The frame-stack env is refused.
+ * never makes this call either: its reanalysis is the worker's round below
+ * (mz_train_set_reanalyse, off by default).  The frame-stack env is refused.
  * _get_reanalysed_policies (parity): game i's policy flag and, if set, its
  * (A, T) child_visits in mz_replay_get_game's layout (buffer sized for
  * max_moves + 1 positions); synchronises.  mz_replay_clear_reanalysed and a
@@ -488,6 +491,41 @@ int mz_replay_get_reanalysed(mz_handle* h, int32_t i, int32_t* is_set, float* va
 int mz_replay_reanalyse_search(mz_handle* h, int32_t first, int32_t count, int exploration, uint32_t rng_step,
                                uint32_t game_offset, void* stream);
 int mz_replay_get_reanalysed_policies(mz_handle* h, int32_t i, int32_t* is_set, float* child_visits);
+
+/* The Reanalyse worker: rounds whose selection is made on the device, so a
+ * rolling pass needs no read-back of the counters.  The shard keeps a cursor,
+ * the game number (save_game's 1-based numbering) of the next game to
+ * reanalyse; mz_selfplay_init sets it to 1.  One round (kernel
+ * mz_reanalyse_pack), with played = num_played_games, n = min(played,
+ * capacity), oldest = played - n + 1: nothing if played == 0; else a cursor
+ * outside [oldest, played] moves to oldest (the wrap, or the games evicted
+ * since), and games cursor, cursor + 1, ... are taken while they are <= played
+ * and their lengths sum to <= R.  R = max_games rows with MZ_REAN_BY_SEARCH,
+ * 4096 with MZ_REAN_BY_VALUE.  A round never wraps: one that reaches `played`
+ * ends there and the next starts at the oldest game.  The cursor becomes the
+ * first game not taken.  Only the taken games' stored positions become rows,
+ * in (game, position) order; a round that did not end at `played` has fewer
+ * than max_moves + 1 unused rows.
+ * _next: one round, pack -> (mz_reanalyse_fc | gather, nets, scatter) or
+ *   (sgather, the search, sscatter) on the packed rows, stream-ordered, no host
+ *   synchronisation, with the weights and tree buffers an explicit reanalyse
+ *   call would use at this point of the stream; flags, counter and targets as
+ *   for mz_replay_reanalyse / _search.  Search mode: row i is searched exactly
+ *   as mz_mcts_search_dev searches game i of a G = max_games launch with
+ *   Philox id game_offset + i (temperature 0, the action dropped); the rows
+ *   from n_rows on ride along as the dummy game.  Value mode ignores
+ *   exploration, rng_step and game_offset.  Refused: the frame-stack env, and
+ *   search mode with max_games < max_moves + 1 (a round could not hold one
+ *   full game).
+ * _cursor (parity, synchronises): the cursor and the last round's {first game
+ *   number, games taken, rows}; either pointer may be NULL.
+ * _seek: stream-ordered, sets the cursor to any value; the next round
+ *   normalises it as above.                                                  */
+enum { MZ_REAN_OFF = 0, MZ_REAN_BY_VALUE = 1, MZ_REAN_BY_SEARCH = 2 };
+int mz_replay_reanalyse_next(mz_handle* h, int mode, int exploration, uint32_t rng_step,
+                             uint32_t game_offset, void* stream);
+int mz_replay_reanalyse_cursor(mz_handle* h, int64_t* next_game, int64_t* last_round3);
+int mz_replay_reanalyse_seek(mz_handle* h, int64_t game_number, void* stream);
 
 /* ---- Actor–learner loop (self_play! ‖ learning!) -----
  * The reference runs self_play! (SelfPlay.jl:384-419) and learning!
@@ -538,6 +576,20 @@ int mz_replay_get_reanalysed_policies(mz_handle* h, int32_t i, int32_t* is_set, 
  *     Distributed host): mz_train_move plays one move and returns the games it
  *     saved on this rank (*nfin); mz_train_learn takes `steps` learner steps
  *     (capped at training_steps) with the refreshes, state_out as above.
+ *   mz_train_set_reanalyse: the Reanalyse worker inside mz_train_run.  With
+ *     mode MZ_REAN_BY_VALUE or MZ_REAN_BY_SEARCH every move runs
+ *     `rounds_per_move` rounds of mz_replay_reanalyse_next after its self-play
+ *     and before its learner steps, with the learner's nets; round r of move
+ *     key m has rng_step = m and game_offset = (the call's game_offset) +
+ *     r * max_games.  The rounds are issued behind the move's launches and
+ *     before the host waits for the move's finished-game count, so that wait
+ *     overlaps them.  The results are those of the split loop with the same
+ *     mz_replay_reanalyse_next calls between mz_train_move and mz_train_learn;
+ *     mz_train_move / mz_train_learn themselves never reanalyse.  At world > 1
+ *     every rank reanalyses its own shard, nothing is exchanged.  MZ_REAN_OFF
+ *     (the default): no round, every launch as without the call.  Refused:
+ *     rounds_per_move < 0, an unknown mode, and what mz_replay_reanalyse_next
+ *     refuses.  The setting stays with the handle.
  *   mz_train_set_networks_path: conf.networks_path (Constructors.jl:47) for
  *     the periodic checkpoints; NULL or "" (the default) writes none.
  *   mz_train_weights_get: the learner's, actors' or queued nets (Flux order).
@@ -546,6 +598,7 @@ enum { MZ_TRAIN_LEARNER = 0, MZ_TRAIN_ACTOR = 1, MZ_TRAIN_QUEUED = 2 };
 int mz_train_init(mz_handle* h, int32_t batch_size);
 int mz_train_init_at(mz_handle* h, int32_t batch_size, int64_t t0);
 int mz_train_set_networks_path(mz_handle* h, const char* networks_path);
+int mz_train_set_reanalyse(mz_handle* h, int mode, int rounds_per_move, int exploration);
 int mz_train_run(mz_handle* h, int32_t moves, uint32_t move0, uint32_t game_offset, int64_t* state_out,
                  float* losses_dev, void* stream);
 int mz_train_move(mz_handle* h, uint32_t move, uint32_t game_offset, int64_t* nfin, void* stream);

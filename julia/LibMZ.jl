@@ -44,6 +44,7 @@ const ENV_TICTACTOE, ENV_CONNECT4, ENV_ATARI = Cint(0), Cint(1), Cint(2)   # ENV
 const SP_TRAIN, SP_EVAL, OPP_SELF, OPP_RANDOM = Cint(0), Cint(1), Cint(0), Cint(1)
 const LEARN_REF_SEMANTICS, LEARN_CORRECTED = Cint(0), Cint(1)
 const TRAIN_LEARNER, TRAIN_ACTOR, TRAIN_QUEUED = Cint(0), Cint(1), Cint(2)
+const REAN_OFF, REAN_BY_VALUE, REAN_BY_SEARCH = Cint(0), Cint(1), Cint(2)
 
 act_code(f) = f === tanh ? ACT_TANH : f === relu ? ACT_RELU : ACT_IDENTITY
 
@@ -222,6 +223,25 @@ function get_reanalysed_policies(e::Engine, i, A, max_moves)   # shard game i: `
                    e.h, i, set, cv))
     set[] == 0 ? nothing : cv
 end
+
+# The Reanalyse worker: one round of whole games from the shard's cursor (a game number; the device picks as many
+# games as fit max_games rows in search mode, 4096 in value mode, and packs only their stored positions), stream-ordered
+# with no read-back.  Search mode: row i of the round is the game with Philox id game_offset + i at rng_step.
+reanalyse_next!(e::Engine, mode::Cint; exploration=false, rng_step=0, game_offset=0) =
+    check(e, ccall((:mz_replay_reanalyse_next, libmz), Cint, (Ptr{Cvoid}, Cint, Cint, UInt32, UInt32, Ptr{Cvoid}),
+                   e.h, mode, exploration ? 1 : 0, rng_step, game_offset, C_NULL))
+function reanalyse_cursor(e::Engine)           # (next game number, (first game number, games, rows) of the last round)
+    c = Ref{Int64}(0); r = zeros(Int64, 3)
+    check(e, ccall((:mz_replay_reanalyse_cursor, libmz), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}), e.h, c, r))
+    c[], Tuple(r)
+end
+reanalyse_seek!(e::Engine, game_number) =
+    check(e, ccall((:mz_replay_reanalyse_seek, libmz), Cint, (Ptr{Cvoid}, Int64, Ptr{Cvoid}), e.h, game_number, C_NULL))
+# train_run! then runs `rounds_per_move` such rounds every move, after its self-play and before its learner steps
+# (REAN_OFF, the default: none)
+train_set_reanalyse!(e::Engine, mode::Cint; rounds_per_move=1, exploration=false) =
+    check(e, ccall((:mz_train_set_reanalyse, libmz), Cint, (Ptr{Cvoid}, Cint, Cint, Cint),
+                   e.h, mode, rounds_per_move, exploration ? 1 : 0))
 
 """The actor–learner loop of self_play! ‖ learning! (src/SelfPlay.jl:384-419,
 src/Learning.jl:306-438; quirk Q16) on one GPU: `moves` self-play moves with the

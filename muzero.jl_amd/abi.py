@@ -21,6 +21,7 @@ SP_TRAIN, SP_EVAL = 0, 1
 TRAIN_LEARNER, TRAIN_ACTOR, TRAIN_QUEUED = 0, 1, 2
 LEARN_REF_SEMANTICS, LEARN_CORRECTED = 0, 1
 OPP_SELF, OPP_RANDOM = 0, 1
+REAN_OFF, REAN_BY_VALUE, REAN_BY_SEARCH = 0, 1, 2
 
 _lib = None
 
@@ -90,6 +91,10 @@ SIGNATURES = {
     "mz_replay_reanalyse_search": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_uint32,
                                                   ctypes.c_uint32, _VP]),
     "mz_replay_get_reanalysed_policies": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP]),
+    "mz_replay_reanalyse_next": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, _VP]),
+    "mz_replay_reanalyse_cursor": (ctypes.c_int, [_VP, _VP, _VP]),
+    "mz_replay_reanalyse_seek": (ctypes.c_int, [_VP, ctypes.c_int64, _VP]),
+    "mz_train_set_reanalyse": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "mz_learner_set_mode": (ctypes.c_int, [_VP, ctypes.c_int]),
     "mz_train_init": (ctypes.c_int, [_VP, ctypes.c_int32]),
     "mz_train_init_at": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int64]),
@@ -363,6 +368,13 @@ class Engine:
         self._check(self.lib.mz_train_set_networks_path(self.h, path.encode() if path else None),
                     "mz_train_set_networks_path")
 
+    def train_set_reanalyse(self, mode, rounds_per_move=1, exploration=False):
+        """The Reanalyse worker inside train_run: `rounds_per_move` rounds of replay_reanalyse_next(mode)
+        every move, after its self-play and before its learner steps (round r of move key m: rng_step m,
+        game_offset + r * max_games).  REAN_OFF (the default): none."""
+        self._check(self.lib.mz_train_set_reanalyse(self.h, mode, rounds_per_move, int(exploration)),
+                    "mz_train_set_reanalyse")
+
     def train_run(self, moves, move0=0, game_offset=0, losses_ptr=None, stream=None):
         """`moves` self-play moves with the actors' nets, one learner step per
         finished game, actor refresh every checkpoint_interval steps; returns
@@ -559,6 +571,26 @@ class Engine:
         if not s.value:
             return None
         return cv[:len(self.replay_get_game(i).action_history)].copy()
+
+    def replay_reanalyse_next(self, mode, exploration=False, rng_step=0, game_offset=0, stream=None):
+        """One round of the Reanalyse worker: the device takes whole games from the shard's cursor while
+        their stored positions fit the round (max_games rows with REAN_BY_SEARCH, 4096 with REAN_BY_VALUE)
+        and reanalyses exactly those positions; stream-ordered, no host synchronisation.  Search mode: row i
+        of the round as mcts_search's game with Philox id game_offset + i of a max_games batch."""
+        self._check(self.lib.mz_replay_reanalyse_next(self.h, mode, int(exploration), rng_step & 0xffffffff,
+                                                      game_offset & 0xffffffff, stream),
+                    "mz_replay_reanalyse_next")
+
+    def replay_reanalyse_cursor(self):
+        """(the next game number to reanalyse, (first game number, games, rows) of the last round); synchronises."""
+        c = ctypes.c_int64()
+        r = np.zeros(3, np.int64)
+        self._check(self.lib.mz_replay_reanalyse_cursor(self.h, ctypes.byref(c), _p(r)), "mz_replay_reanalyse_cursor")
+        return int(c.value), tuple(int(x) for x in r)
+
+    def replay_reanalyse_seek(self, game_number, stream=None):
+        """Stream-ordered: the cursor := game_number (any value; the next round normalises it)."""
+        self._check(self.lib.mz_replay_reanalyse_seek(self.h, int(game_number), stream), "mz_replay_reanalyse_seek")
 
     def selfplay_slots(self):
         G = self.sp_G

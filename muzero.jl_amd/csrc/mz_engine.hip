@@ -80,6 +80,8 @@ extern "C" __global__ void mz_reanalyse_scatter(ReanParams Q);
 extern "C" __global__ void mz_reanalyse_clear(int32_t* rean, int cap);
 extern "C" __global__ void mz_reanalyse_sgather(ReanParams Q);
 extern "C" __global__ void mz_reanalyse_sscatter(ReanParams Q);
+extern "C" __global__ void mz_reanalyse_pack(ReanParams Q, int32_t* rows);
+extern "C" __global__ void mz_reanalyse_seek(long long* counters, long long game_number);
 extern "C" __global__ void mz_search_small1(SmallParams P);
 extern "C" __global__ void mz_search_small2(SmallParams P);
 extern "C" __global__ void mz_search_small4(SmallParams P);
@@ -325,6 +327,11 @@ struct mz_handle {
     float *d_rq_obs = nullptr, *d_rq_cv = nullptr, *d_rq_rv = nullptr;
     uint8_t* d_rq_legal = nullptr;
     int32_t *d_rq_tp = nullptr, *d_rq_act = nullptr, *d_rq_state = nullptr;
+    // mz_replay_reanalyse_next: the round's packed (slot, pos) rows (in sp_allocs), and
+    // mz_train_set_reanalyse's rounds inside mz_train_run
+    int32_t* d_rean_rows = nullptr;
+    int rean_rows_cap = 0;
+    int tr_rean_mode = 0, tr_rean_rounds = 0, tr_rean_expl = 0;
     // L learner steps per launch pair (mz_learner_train_multi_dev, ChainParams): the bank of
     // MZ_MULTI_MAX small-kernel images (θ_t .. θ_{t+L-1}), per-step batches, read-outs,
     // loss terms, Σθ² partials, fold counters and losses, for batches up to ml_cap
@@ -3294,7 +3301,10 @@ int mz_selfplay_init(mz_handle* h, int env_kind, int G, int replay_games) {
     MZ_TRY(h, spalloc(h, &h->sp_ring.rean, (size_t)replay_games));
     h->rn_cap = 0;                              // the ResNet staging buffers were in sp_allocs
     h->sp_ring.rcv = nullptr; h->d_rq_obs = nullptr;    // so were rcv and the reanalyse search's io
-    MZ_TRY(h, spalloc(h, &h->d_sp_counters, 4));
+    h->d_rean_rows = nullptr; h->rean_rows_cap = 0;     // and the worker's row list
+    MZ_TRY(h, spalloc(h, &h->d_sp_counters, MZ_SP_COUNTERS));
+    const long long cursor0 = 1;                        // the reanalyse cursor: game number 1
+    MZ_TRY(h, hipMemcpy(h->d_sp_counters + MZ_REAN_CURSOR, &cursor0, sizeof(cursor0), hipMemcpyHostToDevice));
     MZ_TRY(h, spalloc(h, &h->d_sp_done, (size_t)G));
     MZ_TRY(h, spalloc(h, &h->d_sp_rpos, (size_t)G));
     MZ_TRY(h, spalloc(h, &h->d_sp_temp, (size_t)G));
@@ -4195,6 +4205,17 @@ int mz_replay_get_game(mz_handle* h, int32_t i, int32_t* T, uint8_t* obs, int32_
 // ---- Reanalyse (mz_reanalyse.hip): reanalysed_predicted_root_values on the shard
 static const int kReanChunk = 4096;     // ResNet engines: positions per gather / nets / scatter round
 
+// what every reanalyse launch reads: the shard, its geometry and the counters
+static ReanParams rean_params(mz_handle* h) {
+    ReanParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.T = h->sp_T; Q.osz = h->sp_osz; Q.P = h->plane; Q.F = h->obs_feat; Q.stacked = h->conf.stacked_observations;
+    Q.cap = h->sp_cap; Q.ring = h->sp_ring; Q.counters = h->d_sp_counters;
+    return Q;
+}
+
+static int rean_values(mz_handle* h, ReanParams& Q, int npos, hipStream_t st);
+
 int mz_replay_reanalyse(mz_handle* h, int32_t first, int32_t count, void* stream) {
     if (!h) return -2;
     if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
@@ -4208,12 +4229,13 @@ int mz_replay_reanalyse(mz_handle* h, int32_t first, int32_t count, void* stream
     const int gmax = count < 0 ? h->sp_cap - first : std::min<int>(count, h->sp_cap - first);
     ++h->pf_epoch;                                  // a batch drawn ahead has the old targets
     if (gmax <= 0) return 0;
-    ReanParams Q;
-    std::memset(&Q, 0, sizeof(Q));
+    ReanParams Q = rean_params(h);
     Q.first = first; Q.count = count;
-    Q.T = h->sp_T; Q.osz = h->sp_osz; Q.P = h->plane; Q.F = h->obs_feat; Q.stacked = h->conf.stacked_observations;
-    Q.cap = h->sp_cap; Q.ring = h->sp_ring; Q.counters = h->d_sp_counters;
-    const int npos = gmax * h->sp_T;
+    return rean_values(h, Q, gmax * h->sp_T, st);
+}
+
+// the value pass over rows [0, npos) of Q's flattened grid or row list
+static int rean_values(mz_handle* h, ReanParams& Q, int npos, hipStream_t st) {
     if (h->kind != 1) {
         Q.plan_root = h->d_plan[3]; Q.Wp = h->d_Wp; Q.Bp = h->d_Bp;
         Q.x_rep = h->lay.x_rep; Q.v_out = h->lay.v_out; Q.v_act = h->lay.v_act; Q.lds_total = h->lay.total;
@@ -4308,6 +4330,28 @@ int mz_replay_get_reanalysed(mz_handle* h, int32_t i, int32_t* is_set, float* va
 }
 
 // ---- Reanalyse by search: gather -> the batched search -> scatter per max_games rows
+// the search's io and the shard's reanalysed child_visits, allocated by the first call that has work,
+// and the search half of the parameters
+static int rean_search_io(mz_handle* h, ReanParams& Q) {
+    const size_t Gc = (size_t)h->max_games, A = (size_t)h->A;
+    if (!h->d_rq_obs) {
+        MZ_TRY(h, spalloc(h, &h->sp_ring.rcv, (size_t)h->sp_cap * h->sp_T * A, false));
+        MZ_TRY(h, spalloc(h, &h->d_rq_legal, Gc * A, false));
+        MZ_TRY(h, spalloc(h, &h->d_rq_tp, Gc, false));
+        MZ_TRY(h, spalloc(h, &h->d_rq_cv, Gc * A, false));
+        MZ_TRY(h, spalloc(h, &h->d_rq_rv, Gc, false));
+        MZ_TRY(h, spalloc(h, &h->d_rq_act, Gc, false));
+        MZ_TRY(h, spalloc(h, &h->d_rq_state, Gc, false));
+        MZ_TRY(h, spalloc(h, &h->d_rq_obs, Gc * h->obs_feat, false));
+    }
+    Q.ring = h->sp_ring;
+    Q.env = h->sp_env; Q.W = h->conf.observation_shape[0]; Q.H = h->conf.observation_shape[1]; Q.A = h->A;
+    Q.players = h->conf.players;
+    Q.stage_x = h->d_rq_obs; Q.stage_legal = h->d_rq_legal; Q.stage_tp = h->d_rq_tp; Q.stage_state = h->d_rq_state;
+    Q.stage_cv = h->d_rq_cv; Q.stage_rv = h->d_rq_rv;
+    return 0;
+}
+
 int mz_replay_reanalyse_search(mz_handle* h, int32_t first, int32_t count, int exploration, uint32_t rng_step,
                                uint32_t game_offset, void* stream) {
     if (!h) return -2;
@@ -4323,25 +4367,9 @@ int mz_replay_reanalyse_search(mz_handle* h, int32_t first, int32_t count, int e
     ++h->pf_epoch;                                  // a batch drawn ahead has the old targets
     if (gmax <= 0) return 0;
     const size_t Gc = (size_t)h->max_games, A = (size_t)h->A;
-    if (!h->d_rq_obs) {
-        MZ_TRY(h, spalloc(h, &h->sp_ring.rcv, (size_t)h->sp_cap * h->sp_T * A, false));
-        MZ_TRY(h, spalloc(h, &h->d_rq_legal, Gc * A, false));
-        MZ_TRY(h, spalloc(h, &h->d_rq_tp, Gc, false));
-        MZ_TRY(h, spalloc(h, &h->d_rq_cv, Gc * A, false));
-        MZ_TRY(h, spalloc(h, &h->d_rq_rv, Gc, false));
-        MZ_TRY(h, spalloc(h, &h->d_rq_act, Gc, false));
-        MZ_TRY(h, spalloc(h, &h->d_rq_state, Gc, false));
-        MZ_TRY(h, spalloc(h, &h->d_rq_obs, Gc * h->obs_feat, false));
-    }
-    ReanParams Q;
-    std::memset(&Q, 0, sizeof(Q));
+    ReanParams Q = rean_params(h);
     Q.first = first; Q.count = count;
-    Q.T = h->sp_T; Q.osz = h->sp_osz; Q.P = h->plane; Q.F = h->obs_feat; Q.stacked = h->conf.stacked_observations;
-    Q.cap = h->sp_cap; Q.ring = h->sp_ring; Q.counters = h->d_sp_counters;
-    Q.env = h->sp_env; Q.W = h->conf.observation_shape[0]; Q.H = h->conf.observation_shape[1]; Q.A = h->A;
-    Q.players = h->conf.players;
-    Q.stage_x = h->d_rq_obs; Q.stage_legal = h->d_rq_legal; Q.stage_tp = h->d_rq_tp; Q.stage_state = h->d_rq_state;
-    Q.stage_cv = h->d_rq_cv; Q.stage_rv = h->d_rq_rv;
+    if (rean_search_io(h, Q)) return -1;
     const int npos = gmax * h->sp_T;
     for (int p0 = 0; p0 < npos; p0 += (int)Gc) {
         const int pn = std::min<int>((int)Gc, npos - p0);
@@ -4376,6 +4404,89 @@ int mz_replay_get_reanalysed_policies(mz_handle* h, int32_t i, int32_t* is_set, 
     if (child_visits && set)
         MZ_TRY(h, hipMemcpy(child_visits, h->sp_ring.rcv + (size_t)slot * h->sp_T * h->A, (size_t)len * h->A * 4,
                             hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- The Reanalyse worker: one round of whole games from the device cursor, live rows only
+// (mz_reanalyse_pack), through either pass above.  The host knows neither how many games are held
+// nor which the round takes: every launch covers the round's capacity R and reads n_rows on the device.
+static int rean_next_check(mz_handle* h, int mode) {
+    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
+    if (h->sp_frames > 0 || h->ds) return fail(h, "reanalyse: frame-stack env not built");
+    if (mode != MZ_REAN_BY_VALUE && mode != MZ_REAN_BY_SEARCH)
+        return fail(h, "reanalyse: mode must be MZ_REAN_BY_VALUE or MZ_REAN_BY_SEARCH");
+    if ((long long)h->sp_cap * h->sp_T > 0x7fffffffLL) return fail(h, "reanalyse: shard too large");
+    if (mode == MZ_REAN_BY_SEARCH && h->max_games < h->sp_T)
+        return fail(h, "reanalyse: a search round of max_games rows cannot hold one game of max_moves + 1 positions");
+    if (mode == MZ_REAN_BY_VALUE && kReanChunk < h->sp_T)
+        return fail(h, "reanalyse: a value round cannot hold one game of max_moves + 1 positions");
+    return 0;
+}
+
+int mz_replay_reanalyse_next(mz_handle* h, int mode, int exploration, uint32_t rng_step, uint32_t game_offset,
+                             void* stream) {
+    if (!h) return -2;
+    if (rean_next_check(h, mode)) return -1;
+    MZ_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const bool search = mode == MZ_REAN_BY_SEARCH;
+    const int R = search ? h->max_games : kReanChunk;
+    ++h->pf_epoch;                                  // a batch drawn ahead has the old targets
+    if (R > h->rean_rows_cap) {
+        MZ_TRY(h, spalloc(h, &h->d_rean_rows, (size_t)R * 2, false));
+        h->rean_rows_cap = R;
+    }
+    ReanParams Q = rean_params(h);
+    Q.R = R;
+    if (search && rean_search_io(h, Q)) return -1;
+    hipLaunchKernelGGL(mz_reanalyse_pack, dim3(1), dim3(64), 0, st, Q, h->d_rean_rows);
+    MZ_TRY(h, hipGetLastError());
+    Q.rows = h->d_rean_rows;
+    // the shard cannot hold more live rows than cap * T: the launches need not cover more
+    const int npos = (int)std::min<long long>(R, (long long)h->sp_cap * h->sp_T);
+    if (!search) return rean_values(h, Q, npos, st);
+    // one search of G = max_games games: row i has Philox id game_offset + i, rows >= n_rows are the dummy
+    const int G = h->max_games;
+    Q.p0 = 0; Q.pn = G;
+    hipLaunchKernelGGL(mz_reanalyse_sgather, dim3((G + 3) / 4), dim3(256), 0, st, Q);
+    MZ_TRY(h, hipGetLastError());
+    int rc = search_dev(h, G, h->d_rq_obs, h->d_rq_legal, h->d_rq_tp, exploration, rng_step, game_offset, 0.0f,
+                        h->d_rq_cv, h->d_rq_rv, h->d_rq_act, st, nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(mz_reanalyse_sscatter, dim3((G * h->A + 255) / 256), dim3(256), 0, st, Q);
+    MZ_TRY(h, hipGetLastError());
+    return 0;
+}
+
+int mz_replay_reanalyse_cursor(mz_handle* h, int64_t* next_game, int64_t* last_round3) {
+    if (!h) return -2;
+    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);
+    long long c[4];
+    MZ_TRY(h, hipMemcpy(c, h->d_sp_counters + MZ_REAN_CURSOR, sizeof(c), hipMemcpyDeviceToHost));
+    if (next_game) *next_game = c[0];
+    if (last_round3) for (int i = 0; i < 3; ++i) last_round3[i] = c[1 + i];
+    return 0;
+}
+
+int mz_replay_reanalyse_seek(mz_handle* h, int64_t game_number, void* stream) {
+    if (!h) return -2;
+    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
+    MZ_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipLaunchKernelGGL(mz_reanalyse_seek, dim3(1), dim3(64), 0, st, h->d_sp_counters, (long long)game_number);
+    MZ_TRY(h, hipGetLastError());
+    return 0;
+}
+
+int mz_train_set_reanalyse(mz_handle* h, int mode, int rounds_per_move, int exploration) {
+    if (!h) return -2;
+    if (mode != MZ_REAN_OFF && mode != MZ_REAN_BY_VALUE && mode != MZ_REAN_BY_SEARCH)
+        return fail(h, "mz_train_set_reanalyse: mode must be MZ_REAN_OFF, MZ_REAN_BY_VALUE or MZ_REAN_BY_SEARCH");
+    if (rounds_per_move < 0) return fail(h, "mz_train_set_reanalyse: rounds_per_move must be >= 0");
+    if (mode != MZ_REAN_OFF && h->sp_env >= 0 && rean_next_check(h, mode)) return -1;
+    h->tr_rean_mode = mode; h->tr_rean_rounds = rounds_per_move; h->tr_rean_expl = exploration != 0;
     return 0;
 }
 
@@ -4496,12 +4607,26 @@ static int tr_wait_publish(mz_handle* h, long long seq, hipStream_t st) {
     return 0;
 }
 
+// the move's reanalyse rounds (mz_train_set_reanalyse), with the learner's nets: round r has the
+// keys (move, game_offset + r * max_games)
+static int train_rean_rounds(mz_handle* h, uint32_t move, uint32_t game_offset, hipStream_t st) {
+    for (int r = 0; r < h->tr_rean_rounds; ++r)
+        if (mz_replay_reanalyse_next(h, h->tr_rean_mode, h->tr_rean_expl, move,
+                                     game_offset + (uint32_t)r * (uint32_t)h->max_games, st))
+            return -1;
+    return 0;
+}
+
 // 1. one self-play move with the actors' nets (SelfPlay.jl:343-380); temperature
 //    visit_softmax_temperature_fn(t) (:48-56, 396-397) for the games that start on
 //    this move (a game in progress keeps its own).  *nfin = the games save_game
 //    stored (slot order, inside the move).  The fault word rides along with the
 //    counter copy: one stream wait per move, no second blocking copy.
-static int train_move(mz_handle* h, uint32_t move, uint32_t game_offset, int64_t* nfin, hipStream_t st) {
+//    `rean` (mz_train_run): the move's reanalyse rounds go on the stream behind the
+//    hand-back and before the host waits for it, so the wait overlaps them.
+static int train_move(mz_handle* h, uint32_t move, uint32_t game_offset, int64_t* nfin, hipStream_t st,
+                      bool rean = false) {
+    rean = rean && h->tr_rean_mode != MZ_REAN_OFF;
     const float temp = temp_fn(h->tr_t);
     wset_swap(h, h->tr_actor);
     h->sp_latch = true;
@@ -4511,6 +4636,7 @@ static int train_move(mz_handle* h, uint32_t move, uint32_t game_offset, int64_t
     if (rc) return rc;
     static const bool copy_sync = std::getenv("MZ_TRAIN_SYNC") != nullptr;   // A/B: round 6's copies + sync
     if (copy_sync) {
+        if (rean && train_rean_rounds(h, move, game_offset, st)) return -1;
         MZ_TRY(h, hipMemcpyAsync(h->h_tr_cnt, h->d_sp_counters, sizeof(long long), hipMemcpyDeviceToHost, st));
         h->h_tr_cnt[1] = 0;
         if (h->d_fault) MZ_TRY(h, hipMemcpyAsync(h->h_tr_cnt + 1, h->d_fault, 4, hipMemcpyDeviceToHost, st));
@@ -4520,6 +4646,7 @@ static int train_move(mz_handle* h, uint32_t move, uint32_t game_offset, int64_t
         hipLaunchKernelGGL(mz_tr_publish, dim3(1), dim3(64), 0, st, (const long long*)h->d_sp_counters,
                            (const unsigned*)h->d_fault, h->h_tr_pub, seq);
         MZ_TRY(h, hipGetLastError());
+        if (rean && train_rean_rounds(h, move, game_offset, st)) return -1;
         if (tr_wait_publish(h, seq, st)) return -1;
         h->h_tr_cnt[0] = h->h_tr_pub[0];
         h->h_tr_cnt[1] = h->h_tr_pub[1];
@@ -4664,7 +4791,7 @@ int mz_train_run(mz_handle* h, int32_t moves, uint32_t move0, uint32_t game_offs
     int64_t steps = 0;
     for (int32_t mv = 0; mv < moves; ++mv) {
         int64_t nfin = 0, done = 0;
-        if (train_move(h, move0 + (uint32_t)mv, game_offset, &nfin, st)) return -1;
+        if (train_move(h, move0 + (uint32_t)mv, game_offset, &nfin, st, true)) return -1;
         // data parallel (mz_dp_init): every rank takes the learner steps of the games all
         // ranks finished, so the replicas stay identical
         if (h->dp_comm && h->dp_world > 1 && dp_sum_count(h, &nfin, st)) return -1;

@@ -15,25 +15,42 @@
 // mz_reanalyse_sscatter writes child_visits to ring.rcv and the search's root
 // values to ring.rrv.  ring.rean is a bit mask: MZ_REAN_VALUES (rrv valid),
 // MZ_REAN_POLICIES (rcv valid).
+//
+// The worker (mz_replay_reanalyse_next) runs either half on one round of rows
+// that mz_reanalyse_pack chose on the device: whole games from a cursor that
+// lives behind the counters, only their live positions, as a list of (slot,
+// pos) pairs the five kernels read in place of the flattened grid.
 #include "mz_mlp_device.h"
 #include "mz_replay_device.h"
 #include "mz_env_device.h"
 
 // The held range and the selection, from the device counter (no host sync):
-// returns the number of selected games that are held, *oldest = game number
-// of shard game 0.
-__device__ __forceinline__ int rean_games(const ReanParams& Q, long long* oldest) {
+// returns the number of rows of the flattened grid that can be live (T per
+// selected game that is held), *oldest = game number of shard game 0.  With a
+// row list (mz_replay_reanalyse_next) the rows are the round's packed ones and
+// their number is the header's n_rows.
+__device__ __forceinline__ int rean_rows(const ReanParams& Q, long long* oldest) {
+    if (Q.rows) {
+        *oldest = 0;
+        const long long n = Q.counters[MZ_REAN_HDR + 2];
+        return (int)(n < 0 ? 0 : n > Q.R ? Q.R : n);
+    }
     const long long played = Q.counters[0];
     const int n = (int)(played < Q.cap ? played : Q.cap);
     *oldest = played - n + 1;
     const int left = n - Q.first;
-    return Q.count < 0 || Q.count > left ? left : Q.count;        // <= 0: nothing selected is held
+    return (Q.count < 0 || Q.count > left ? left : Q.count) * Q.T;    // <= 0: nothing selected is held
 }
 
 // flattened position p -> ring slot and 0-based pos; false if dead
-__device__ __forceinline__ bool rean_pos(const ReanParams& Q, long long oldest, int cnt, int p, int* slot, int* pos) {
+__device__ __forceinline__ bool rean_pos(const ReanParams& Q, long long oldest, int nrows, int p, int* slot, int* pos) {
+    if (p < 0 || p >= nrows) return false;
+    if (Q.rows) {                         // a packed row: live by construction
+        const int2 r = reinterpret_cast<const int2*>(Q.rows)[p];
+        *slot = r.x; *pos = r.y;
+        return true;
+    }
     const int gi = p / Q.T;
-    if (p < 0 || gi >= cnt) return false;
     *pos = p - gi * Q.T;
     *slot = (int)((oldest + Q.first + gi - 1) % Q.cap);
     return *pos < Q.ring.len[*slot];
@@ -45,6 +62,66 @@ __device__ __forceinline__ bool rean_pos(const ReanParams& Q, long long oldest, 
 __device__ __forceinline__ void rean_mark(const ReanParams& Q, int slot, int bits) {
     atomicOr(Q.ring.rean + slot, bits);
     atomicAdd(reinterpret_cast<unsigned long long*>(Q.counters + 3), 1ull);
+}
+
+// One round of the worker, one wave.  With played = counters[0], n = min(played,
+// cap) and oldest = played - n + 1: a cursor outside [oldest, played] goes to
+// oldest (a wrap, or the games evicted since), then games cursor, cursor + 1, ...
+// are taken while they are <= played and the running sum of len stays <= R; no
+// wrap inside a round.  Lane l of chunk c looks at game cursor + 64 c + l: the
+// lanes form an inclusive prefix sum of len, the total so far rides in a
+// register every lane holds, and a ballot finds the first lane that is past
+// `played` or over R.  Every stored game has 1 <= len <= T <= R, so a round on a
+// non-empty shard takes a game, at most R games are looked at and the loop ends
+// within R/64 + 1 chunks whatever the ring holds.  A taken game's rows go to
+// rows[start .. start + len): start + len <= R.  The cursor moves to the first
+// game not taken; the header {first game number, games, n_rows} is what the
+// kernels above (n_rows) and mz_replay_reanalyse_cursor read.
+extern "C" __global__ __launch_bounds__(64) void mz_reanalyse_pack(ReanParams Q, int32_t* rows) {
+    const int lane = threadIdx.x;
+    const long long played = Q.counters[0];
+    long long first = Q.counters[MZ_REAN_CURSOR];
+    int total = 0, games = 0;
+    if (played > 0) {
+        const long long n = played < Q.cap ? played : Q.cap;
+        const long long oldest = played - n + 1;
+        if (first < oldest || first > played) first = oldest;
+        const int chunks = Q.R / 64 + 1;
+        for (int c = 0; c < chunks; ++c) {
+            const long long g = first + (long long)c * 64 + lane;
+            const bool held = g <= played;
+            const int slot = held ? (int)((g - 1) % Q.cap) : 0;
+            int len = held ? Q.ring.len[slot] : 0;
+            len = len < 0 ? 0 : len > Q.T ? Q.T : len;
+            int inc = len;
+            for (int d = 1; d < 64; d <<= 1) {
+                const int t = __shfl_up(inc, d);
+                if (lane >= d) inc += t;
+            }
+            const int tot = total + inc;
+            const unsigned long long stop = __ballot(!held || tot > Q.R);
+            const int take = stop ? __ffsll((long long)stop) - 1 : 64;     // the lanes below are taken
+            if (lane < take)
+                for (int pos = 0; pos < len; ++pos) {
+                    rows[2 * (tot - len + pos)] = slot;
+                    rows[2 * (tot - len + pos) + 1] = pos;
+                }
+            if (take > 0) total = __shfl(tot, take - 1);
+            games += take;
+            if (take < 64) break;
+        }
+    }
+    if (lane == 0) {
+        Q.counters[MZ_REAN_CURSOR] = first + games;
+        Q.counters[MZ_REAN_HDR] = first;
+        Q.counters[MZ_REAN_HDR + 1] = games;
+        Q.counters[MZ_REAN_HDR + 2] = total;
+    }
+}
+
+// stream-ordered mz_replay_reanalyse_seek
+extern "C" __global__ void mz_reanalyse_seek(long long* counters, long long game_number) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) counters[MZ_REAN_CURSOR] = game_number;
 }
 
 // FC engines.  Workgroups walk 16-position tiles in a grid-stride loop; per
@@ -65,14 +142,14 @@ extern "C" __global__ __launch_bounds__(MZ_THREADS) void mz_reanalyse_fc(ReanPar
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     long long oldest;
-    const int cnt = rean_games(Q, &oldest);
-    if (cnt <= 0) return;
-    const int ntiles = (cnt * Q.T + MZ_TILE - 1) / MZ_TILE;
+    const int nrows = rean_rows(Q, &oldest);
+    if (nrows <= 0) return;
+    const int ntiles = (nrows + MZ_TILE - 1) / MZ_TILE;
     float* xs = act + Q.lds_total;
     for (int i = tid; i < Q.lds_total; i += MZ_THREADS) act[i] = 0.0f;     // padded input rows stay 0
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         int slot = 0, pos = 0;
-        const bool live = lane < MZ_TILE && rean_pos(Q, oldest, cnt, tile * MZ_TILE + lane, &slot, &pos);
+        const bool live = lane < MZ_TILE && rean_pos(Q, oldest, nrows, tile * MZ_TILE + lane, &slot, &pos);
         const unsigned mask = (unsigned)__ballot(live) & 0xffffu;          // the same in every wave
         if (!mask) continue;                                               // a dead tile: no networks
         __syncthreads();                  // the zero fill / the previous tile is done with the LDS
@@ -107,10 +184,10 @@ extern "C" __global__ __launch_bounds__(256) void mz_reanalyse_gather(ReanParams
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= Q.pn) return;
     long long oldest;
-    const int cnt = rean_games(Q, &oldest);
+    const int nrows = rean_rows(Q, &oldest);
     float* out = Q.stage_x + (size_t)i * Q.F;
     int slot = 0, pos = 0;
-    if (cnt > 0 && rean_pos(Q, oldest, cnt, Q.p0 + i, &slot, &pos)) {
+    if (rean_pos(Q, oldest, nrows, Q.p0 + i, &slot, &pos)) {
         const size_t base = (size_t)slot * Q.T;
         stacked_obs(out, Q.ring.obs + (base + pos) * Q.osz, Q.ring.obs + base * Q.osz, Q.ring.act + base, pos + 1,
                     Q.osz, Q.P, Q.stacked, lane);
@@ -125,9 +202,9 @@ extern "C" __global__ __launch_bounds__(256) void mz_reanalyse_scatter(ReanParam
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= Q.pn) return;
     long long oldest;
-    const int cnt = rean_games(Q, &oldest);
+    const int nrows = rean_rows(Q, &oldest);
     int slot = 0, pos = 0;
-    if (cnt <= 0 || !rean_pos(Q, oldest, cnt, Q.p0 + i, &slot, &pos)) return;
+    if (!rean_pos(Q, oldest, nrows, Q.p0 + i, &slot, &pos)) return;
     Q.ring.rrv[(size_t)slot * Q.T + pos] = Q.stage_v[i];
     if (pos == 0) rean_mark(Q, slot, MZ_REAN_VALUES);
 }
@@ -153,11 +230,11 @@ extern "C" __global__ __launch_bounds__(256) void mz_reanalyse_sgather(ReanParam
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= Q.pn) return;
     long long oldest;
-    const int cnt = rean_games(Q, &oldest);
+    const int nrows = rean_rows(Q, &oldest);
     float* out = Q.stage_x + (size_t)i * Q.F;
     int slot = 0, pos = 0, state = MZ_REAN_DEAD, tp = 1;
     uint32_t m = Q.A >= 32 ? 0xFFFFFFFFu : (1u << Q.A) - 1u;
-    if (cnt > 0 && rean_pos(Q, oldest, cnt, Q.p0 + i, &slot, &pos)) {
+    if (rean_pos(Q, oldest, nrows, Q.p0 + i, &slot, &pos)) {
         const size_t base = (size_t)slot * Q.T;
         const int t = Q.ring.tp[base + pos];
         uint32_t lm = 0;
@@ -187,9 +264,9 @@ extern "C" __global__ __launch_bounds__(256) void mz_reanalyse_sscatter(ReanPara
     const int state = Q.stage_state[i];
     if (state == MZ_REAN_DEAD) return;
     long long oldest;
-    const int cnt = rean_games(Q, &oldest);
+    const int nrows = rean_rows(Q, &oldest);
     int slot = 0, pos = 0;
-    if (cnt <= 0 || !rean_pos(Q, oldest, cnt, Q.p0 + i, &slot, &pos)) return;
+    if (!rean_pos(Q, oldest, nrows, Q.p0 + i, &slot, &pos)) return;
     const size_t r = (size_t)slot * Q.T + pos;
     const bool live = state == MZ_REAN_LIVE;
     Q.ring.rcv[r * Q.A + a] = live ? Q.stage_cv[(size_t)i * Q.A + a] : Q.ring.cv[r * Q.A + a];

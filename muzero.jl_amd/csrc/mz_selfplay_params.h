@@ -57,7 +57,17 @@ struct ReanParams {
     int32_t* stage_state;       // [pn] MZ_REAN_DEAD (pos >= len, or past the held range), _LIVE, _EMPTY (no legal action)
     const float* stage_cv;      // [pn][A] the search's child_visits
     const float* stage_rv;      // [pn] the search's root_value
+    // mz_replay_reanalyse_next: a round's packed rows.  null: the grid above.  Set: row p is the
+    // (ring slot, 0-based pos) pair rows[p] that mz_reanalyse_pack wrote, dead from n_rows =
+    // counters[MZ_REAN_HDR + 2] on; first / count are not read.  R = the round's capacity in rows.
+    const int32_t* rows;        // [R][2]
+    int R;
 };
+
+// the words behind the shard's four counters: the reanalyse cursor (the game number, in save_game's
+// 1-based numbering, of the next game mz_replay_reanalyse_next takes) and the last round's header
+// {first game number, games taken, n_rows}
+enum { MZ_REAN_CURSOR = 4, MZ_REAN_HDR = 5, MZ_SP_COUNTERS = 8 };
 
 struct SpParams {
     int G, env, W, H, osz, P, A, F, stacked, T, max_moves;

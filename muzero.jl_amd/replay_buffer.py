@@ -130,6 +130,32 @@ def per_categorical(w, u):
     return i, p
 
 
+REAN_BY_VALUE, REAN_BY_SEARCH = 1, 2        # abi.REAN_BY_VALUE / REAN_BY_SEARCH
+REAN_VALUE_ROWS = 4096                      # a value round's capacity (the engine's position chunk)
+
+
+def pack_round(lens_by_game_number, cursor, played, cap, R):
+    """One round of the Reanalyse worker (kernel mz_reanalyse_pack), restated: which games a round of
+    capacity R rows takes from `cursor`, the game number (save_game's 1-based numbering) of the next game
+    to reanalyse.  lens_by_game_number[g] = stored positions of held game g; played = num_played_games;
+    cap = the shard's capacity.  With n = min(played, cap) and oldest = played - n + 1: nothing if
+    played == 0 (the cursor stays); else a cursor outside [oldest, played] goes to oldest, and games
+    cursor, cursor + 1, ... are taken while they are <= played and their lengths sum to <= R — whole
+    games, no wrap inside a round.  Returns (first, games, rows, new_cursor): the first game number
+    taken, how many, the live rows [(game number, 0-based pos)] in (game, pos) order, and the first game
+    not taken."""
+    if played <= 0:
+        return cursor, 0, [], cursor
+    n = min(played, cap)
+    oldest = played - n + 1
+    first = oldest if (cursor < oldest or cursor > played) else cursor
+    rows, g = [], first
+    while g <= played and len(rows) + lens_by_game_number[g] <= R:
+        rows.extend((g, pos) for pos in range(lens_by_game_number[g]))
+        g += 1
+    return first, g - first, rows, g
+
+
 class ReplayBuffer:
     """Per-GPU buffer: Dict{game_id => GameHistory} with FIFO eviction."""
 
@@ -144,6 +170,7 @@ class ReplayBuffer:
         self.num_played_steps = 0
         self.total_samples = 0
         self.num_reanalysed_games = 0
+        self.reanalyse_cursor = 1                               # reanalyse_next: the next game number
 
     def __len__(self):
         return len(self.buffer)
@@ -255,36 +282,71 @@ class ReplayBuffer:
         action is not searched and keeps its stored child_visits / root_values.
         An id that has left the buffer is skipped (update_history!'s check).
         Returns the ids updated."""
-        c = self.conf
         if self.frame_stack:
             raise ValueError("reanalyse: frame-stack env not built")
-        plane = c.observation_shape[0] * c.observation_shape[1]
         done = []
         for gi, gid in enumerate(list(self.buffer.keys()) if game_ids is None else game_ids):
             h = self.buffer.get(gid)
             if h is None:
                 continue
-            T = len(h.root_values)
-            x = np.stack([get_stacked_observations(h.observation_history, h.action_history, i,
-                                                   c.stacked_observations, plane) for i in range(1, T + 1)])
-            legal = np.stack([stored_legal_mask(c, h.observation_history[i], h.to_play_history[i]) for i in range(T)])
-            live = legal.any(axis=1)
-            cv = np.array(h.child_visits, np.float32)
-            rv = np.array(h.root_values, np.float32)
-            if live.any():
-                # unsearched rows go to search_fn as the dummy: zero observation, all legal, to_play 1
-                xs, ls = np.where(live[:, None], x, np.float32(0)), np.where(live[:, None], legal, np.uint8(1))
-                tps = np.where(live, np.array(h.to_play_history, np.int32), 1).astype(np.int32)
-                ncv, nrv = search_fn(xs, ls, tps, gi * (c.max_moves + 1))
-                ncv, nrv = np.asarray(ncv, np.float32), np.asarray(nrv, np.float32).reshape(-1)
-                if ncv.shape != cv.shape or nrv.shape != rv.shape:
-                    raise ValueError(f"search_fn returned {ncv.shape}, {nrv.shape} for {T} positions")
-                cv[live], rv[live] = ncv[live], nrv[live]
-            h.reanalysed_child_visits = [r for r in cv]
-            h.reanalysed_predicted_root_values = [np.float32(t) for t in rv]
-            self.num_reanalysed_games += 1
+            self._search_game(h, search_fn, gi * (self.conf.max_moves + 1))
             done.append(gid)
         return done
+
+    def _search_game(self, h, search_fn, p0):
+        """Game h's positions searched again as rows p0 .. p0 + T - 1 of the selection (reanalyse_search)."""
+        c = self.conf
+        plane = c.observation_shape[0] * c.observation_shape[1]
+        T = len(h.root_values)
+        x = np.stack([get_stacked_observations(h.observation_history, h.action_history, i,
+                                               c.stacked_observations, plane) for i in range(1, T + 1)])
+        legal = np.stack([stored_legal_mask(c, h.observation_history[i], h.to_play_history[i]) for i in range(T)])
+        live = legal.any(axis=1)
+        cv = np.array(h.child_visits, np.float32)
+        rv = np.array(h.root_values, np.float32)
+        if live.any():
+            # unsearched rows go to search_fn as the dummy: zero observation, all legal, to_play 1
+            xs, ls = np.where(live[:, None], x, np.float32(0)), np.where(live[:, None], legal, np.uint8(1))
+            tps = np.where(live, np.array(h.to_play_history, np.int32), 1).astype(np.int32)
+            ncv, nrv = search_fn(xs, ls, tps, p0)
+            ncv, nrv = np.asarray(ncv, np.float32), np.asarray(nrv, np.float32).reshape(-1)
+            if ncv.shape != cv.shape or nrv.shape != rv.shape:
+                raise ValueError(f"search_fn returned {ncv.shape}, {nrv.shape} for {T} positions")
+            cv[live], rv[live] = ncv[live], nrv[live]
+        h.reanalysed_child_visits = [r for r in cv]
+        h.reanalysed_predicted_root_values = [np.float32(t) for t in rv]
+        self.num_reanalysed_games += 1
+
+    def reanalyse_next(self, fn, mode, R=None):
+        """One round of the Reanalyse worker (mz_replay_reanalyse_next's mirror): pack_round from this
+        buffer's cursor, then the taken games through reanalyse (mode REAN_BY_VALUE, fn = its value_fn) or
+        the search of reanalyse_search (REAN_BY_SEARCH, fn = its search_fn; p0 = the game's first row in the
+        packed round, so row i has Philox id game_offset + i).  R: the round's capacity in rows (the
+        engine's: max_games in search mode, REAN_VALUE_ROWS in value mode, the default there).  Returns
+        (first, games, rows, new_cursor) of pack_round."""
+        if self.frame_stack:
+            raise ValueError("reanalyse: frame-stack env not built")
+        if mode not in (REAN_BY_VALUE, REAN_BY_SEARCH):
+            raise ValueError("reanalyse: mode must be REAN_BY_VALUE or REAN_BY_SEARCH")
+        if R is None:
+            if mode == REAN_BY_SEARCH:
+                raise ValueError("reanalyse: a search round needs its capacity R (the engine's max_games)")
+            R = REAN_VALUE_ROWS
+        if R < self.conf.max_moves + 1:
+            raise ValueError("reanalyse: a round of R rows cannot hold one game of max_moves + 1 positions")
+        lens = {g: len(h.root_values) for g, h in self.buffer.items()}
+        first, games, rows, cur = pack_round(lens, self.reanalyse_cursor, self.num_played_games,
+                                             self.conf.replay_buffer_size, R)
+        self.reanalyse_cursor = cur
+        ids = list(range(first, first + games))
+        if mode == REAN_BY_VALUE:
+            self.reanalyse(fn, ids)
+        else:
+            p0 = 0
+            for g in ids:
+                self._search_game(self.buffer[g], fn, p0)
+                p0 += lens[g]
+        return first, games, rows, cur
 
     def update_priorities(self, index_batch, predicted_values, target_values):
         """update_priorities! (ReplayBuffer.jl:168-183, Learning.jl:400-404) in its

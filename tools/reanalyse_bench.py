@@ -23,6 +23,16 @@ fraction of searched rows that were live and, given --search-ms (ms_per_step
 of a plain bench.py run of the parent commit on the same machine, i.e. one
 batched search of `games` games), the figure to judge the pass against:
 rounds x that launch time, and the gap to it.
+
+--next times the worker, mz_replay_reanalyse_next in search mode, on the same
+shard: rounds of whole games from the device cursor, only their live rows
+packed into the `games` rows of one batched search.  One untimed lap with the
+cursor read back after every round counts the rounds of a lap and their live
+rows (no game arrives in between, so every lap is the same); the timed laps
+then run from a seek to the oldest game with device events around them and no
+read-back.  Its JSON line carries rounds, live rows per round, device seconds
+per round, positions/s and, given --search-ms, the gap per round above that
+launch.
 """
 import argparse
 import dataclasses
@@ -123,12 +133,73 @@ def search_mode(a, eng, conf, held, ts, st):
     print(json.dumps(out))
 
 
+def next_mode(a, eng, conf, held, ts, st):
+    counts, _ = eng.replay_counts()
+    played = int(counts[0])
+    oldest = played - held + 1
+
+    def lap(read_back):
+        eng.replay_reanalyse_seek(oldest, stream=st)
+        live = []
+        for _ in range(rounds_per_lap if not read_back else held):
+            eng.replay_reanalyse_next(abi.REAN_BY_SEARCH, exploration=False, rng_step=0, game_offset=0, stream=st)
+            if read_back:
+                cur, (first, n, rows) = eng.replay_reanalyse_cursor()
+                live.append(rows)
+                if cur == played + 1:
+                    break
+        return live
+
+    rounds_per_lap = 0
+    live = lap(True)                                          # warm-up (the first call allocates) and the count
+    rounds_per_lap = len(live)
+    positions = sum(live)
+    assert positions == sum(len(eng.replay_get_game(i).root_values) for i in range(held))
+    assert eng.replay_reanalysed_count() == held
+    torch.cuda.synchronize()
+    dev_s, issue_s, reps = [], [], 1
+    for r in range(a.rounds):
+        while True:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(ts)
+            t_issue = time.perf_counter()
+            for _ in range(reps):
+                lap(False)
+            issued = time.perf_counter() - t_issue
+            e1.record(ts)
+            e1.synchronize()
+            ms = e0.elapsed_time(e1)
+            print(f"round {r}: {reps} laps, {ms:.3f} ms on the device, issued in {issued * 1e3:.3f} ms", file=sys.stderr)
+            if ms >= 500.0:
+                break
+            reps = int(reps * min(100.0, max(2.0, 650.0 / max(ms, 1e-3))))
+        dev_s.append(ms * 1e-3 / reps)
+        issue_s.append(issued / reps)
+    cur, last = eng.replay_reanalyse_cursor()
+    assert cur == played + 1, "a timed lap did not end at the last game"
+    d = float(np.median(dev_s))
+    out = {
+        "tool": "reanalyse_bench", "mode": "next", "engine": "tictactoe fc", "games_held": int(held),
+        "sims_per_move": conf.num_iters, "rows_per_round": a.games, "positions": positions,
+        "rounds_per_lap": rounds_per_lap, "live_rows_per_round_mean": round(positions / rounds_per_lap, 3),
+        "live_rows_per_round_min": int(min(live)), "live_rows_per_round_max": int(max(live)),
+        "live_fraction": round(positions / (rounds_per_lap * a.games), 6), "repeats": reps, "rounds": a.rounds,
+        "device_s_per_lap": round(d, 9), "device_s_per_round": round(d / rounds_per_lap, 9),
+        "device_positions_per_s": round(positions / d, 1),
+        "host_issue_s_per_lap": round(float(np.median(issue_s)), 9)}
+    if a.search_ms:
+        gap = d / rounds_per_lap - a.search_ms * 1e-3
+        out.update({"parent_search_ms_per_launch": a.search_ms, "gap_us_per_round": round(gap * 1e6, 3)})
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--next", action="store_true", help="time rounds of mz_replay_reanalyse_next (search mode) over one lap")
     ap.add_argument("--search", action="store_true", help="time mz_replay_reanalyse_search instead of the value pass")
     ap.add_argument("--host-games", type=int, default=512, help="--search: games of the host route")
     ap.add_argument("--search-ms", type=float, default=None,
-                    help="--search: the parent commit's ms_per_step of a plain bench.py run on the same machine")
+                    help="--search / --next: the parent commit's ms_per_step of a plain bench.py run on the same machine")
     ap.add_argument("--games", type=int, default=512)
     ap.add_argument("--cap", type=int, default=4096)
     ap.add_argument("--moves", type=int, default=80)
@@ -138,7 +209,7 @@ def main():
                          "(default: the game's num_iters; --search: 50, bench.py's configs[1])")
     a = ap.parse_args()
     conf = dataclasses.replace(ttt.conf, replay_buffer_size=a.cap)
-    if a.sims or a.search:
+    if a.sims or a.search or a.next:
         conf = dataclasses.replace(conf, num_iters=a.sims or 50)
     eng = abi.Engine(conf, ttt.hyper, device=0, max_games=a.games, rng_seed=1)
     for n, w in enumerate(init_nets(conf, ttt.hyper, seed=1234)):
@@ -150,8 +221,8 @@ def main():
     eng.sync()
     ts = torch.cuda.Stream()              # its own stream: the events and the launches share it (a null handle
     st = ts.cuda_stream                   # would send the launches to the engine's stream, past the events)
-    if a.search:
-        search_mode(a, eng, conf, held, ts, st)
+    if a.search or a.next:
+        (next_mode if a.next else search_mode)(a, eng, conf, held, ts, st)
         eng.close()
         return
     for _ in range(5):                                        # warm-up
