@@ -543,6 +543,8 @@ int mz_replay_reanalyse_seek(mz_handle* h, int64_t game_number, void* stream);
  *     continue from t0).  Checkpoints hold the learner's nets and ADAM state,
  *     not the actors' or queued sets, so a resume restarts the one-checkpoint
  *     lag: actors and queue start as copies of the loaded learner nets.
+ *     That restart applies to checkpoints; a snapshot (mz_snapshot_save /
+ *     _load, below) holds both sets and resumes exactly, without this call.
  *   mz_train_run: `moves` times: one self-play move of every slot with the
  *     ACTORS' nets (mz_selfplay_move, move key move0 + m); each game plays
  *     at the temperature visit_softmax_temperature_fn(t) of the step t at
@@ -614,6 +616,41 @@ int mz_train_weights_get(mz_handle* h, int which, int net, float* flat, size_t n
  * against this engine and restores weights + optimiser state (resume).      */
 int mz_checkpoint_save(mz_handle* h, const char* path, int64_t training_step);
 int mz_checkpoint_load(mz_handle* h, const char* path, int64_t* training_step);
+
+/* ---- Snapshots: exact resume ----------------------------------
+ * A checkpoint holds the learner only.  A snapshot also holds the replay shard
+ * (the held games' live rows, PER priorities, reanalysed values / policies and
+ * flags, every counter word with the Reanalyse cursor and round header), the
+ * games in progress (histories, boards, players, the Atari-like env's keys,
+ * per-game temperatures, the evaluation tally, a still-pending initial reset)
+ * and, after mz_train_init, the train loop (batch size, learner step, refresh
+ * count, the actors' and the queued weight sets).  Every random draw is keyed
+ * by (seed, step, game id), so a run cut in two by mz_snapshot_save -> any
+ * engine of the same config and rng_seed -> mz_snapshot_load continues bit for
+ * bit as the uncut run.  The reference has no counterpart (its buffer lives in
+ * memory only; games/tictactoe/main.jl:21 leaves saving it as a TODO).
+ *   mz_snapshot_save: one safetensors file (written to path + ".tmp", then
+ *     renamed), a superset of a checkpoint: mz_checkpoint_load reads the
+ *     learner's nets, ADAM state and training_step from it.  Only live rows
+ *     are written: new kernels pack them on the device and the host streams
+ *     them through one bounded staging buffer.  Tensor names: mz_snapshot.hip.
+ *   mz_snapshot_load: parses and validates the whole file first (header, every
+ *     game length, the row tensors' shapes against the lengths' prefix sums,
+ *     the counters, network kind and shapes, env, observation_shape, actions,
+ *     max_moves, PER, rng_seed, G <= max_games); a refused load leaves the
+ *     engine exactly as it was.  Then it performs what mz_selfplay_init(env, G,
+ *     cap) performs with the file's env, G and cap, restores the state and, if
+ *     the file has a train section, what mz_train_init allocates; without one
+ *     mz_train_run is refused until mz_train_init.  *training_step = the value
+ *     given to mz_snapshot_save.
+ * Both synchronise first and are valid between calls only, never inside a move.
+ * Handle settings are NOT state: mz_train_set_reanalyse, mz_selfplay_mode,
+ * mz_train_set_networks_path, mz_learner_set_mode and mz_debug_enable are
+ * written into the metadata for information, and the loading host applies its
+ * own (its mz_selfplay_mode survives the load).  At world > 1 each rank saves
+ * and loads its own file; the host orders the calls.                          */
+int mz_snapshot_save(mz_handle* h, const char* path, int64_t training_step);
+int mz_snapshot_load(mz_handle* h, const char* path, int64_t* training_step);
 
 /* Name of the search kernel variant the last search launched (for profiles):
  * mz_search_small{1,2,4} (T games per workgroup, G <= 4 x #CUs) or the

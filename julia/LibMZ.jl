@@ -300,4 +300,13 @@ function checkpoint_load!(e::Engine, path)
     step[]
 end
 
+# ---- snapshots: the learner, the replay shard, the games in progress and the train loop (exact resume)
+snapshot_save(e::Engine, path, step) =
+    check(e, ccall((:mz_snapshot_save, libmz), Cint, (Ptr{Cvoid}, Cstring, Int64), e.h, path, step))
+function snapshot_load!(e::Engine, path)
+    step = Ref{Int64}(0)
+    check(e, ccall((:mz_snapshot_load, libmz), Cint, (Ptr{Cvoid}, Cstring, Ref{Int64}), e.h, path, step))
+    step[]
+end
+
 end # module

@@ -105,6 +105,8 @@ SIGNATURES = {
     "mz_train_weights_get": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_size_t]),
     "mz_checkpoint_save": (ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.c_int64]),
     "mz_checkpoint_load": (ctypes.c_int, [_VP, ctypes.c_char_p, _VP]),
+    "mz_snapshot_save": (ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.c_int64]),
+    "mz_snapshot_load": (ctypes.c_int, [_VP, ctypes.c_char_p, _VP]),
     "mz_search_variant": (ctypes.c_char_p, [_VP]),
     "mz_learner_variant": (ctypes.c_char_p, [_VP]),
     "mz_sync": (ctypes.c_int, [_VP]),
@@ -608,6 +610,20 @@ class Engine:
         """Restores weights + ADAM state; returns the checkpoint's training step."""
         step = ctypes.c_int64()
         self._check(self.lib.mz_checkpoint_load(self.h, os.fsencode(path), ctypes.byref(step)), "mz_checkpoint_load")
+        return step.value
+
+    # ---- snapshots (DESIGN §16): the shard, the games in progress and the train loop as well
+    def snapshot_save(self, path, training_step):
+        self._check(self.lib.mz_snapshot_save(self.h, os.fsencode(path), int(training_step)), "mz_snapshot_save")
+
+    def snapshot_load(self, path):
+        """Exact resume: replaces the learner, the shard, the slots and the train loop with the file's
+        (a refused file leaves the engine as it was); returns the snapshot's training step."""
+        from . import checkpoint as ck
+        step = ctypes.c_int64()
+        self._check(self.lib.mz_snapshot_load(self.h, os.fsencode(path), ctypes.byref(step)), "mz_snapshot_load")
+        meta = ck.read_metadata(path)                  # the shard geometry the read-outs use
+        self.sp_G, self.osz = int(meta["G"]), int(meta["osz"])
         return step.value
 
     def search_variant(self):

@@ -107,3 +107,62 @@ def nets_from(tensors, conf, hyper):
             parts.append(np.ascontiguousarray(a, np.float32).ravel())
         out.append(np.concatenate(parts))
     return out
+
+
+# ---- snapshots (mz_snapshot_save / _load; layout in muzero.jl_amd/csrc/mz_snapshot.hip)
+SNAPSHOT_FORMAT = "libmz-snapshot-1"
+
+
+def read_metadata(path):
+    """The __metadata__ dict of a safetensors file (the header only, no tensor is read)."""
+    with open(path, "rb") as f:
+        n = int.from_bytes(f.read(8), "little")
+        return json.loads(f.read(n)).get("__metadata__", {})
+
+
+def read_snapshot(path):
+    """A snapshot as host objects, through safetensors' numpy loader:
+    games     the held games, oldest first, as selfplay.GameHistory (with the reanalysed values /
+              child_visits of the games that have them, and with PER the priorities),
+    slots     the games in progress: len, board, player, over, ekey, tgame, eval, reset_pending and
+              `games` (their GameHistory so far),
+    counters  the 8 counter words,
+    train     None, or {batch_size, t, refreshes, actor, queued (flat vectors)},
+    tensors, meta   the raw file."""
+    from .selfplay import GameHistory
+    tensors, meta = read(path)
+    if meta.get("format") != SNAPSHOT_FORMAT:
+        raise ValueError(f"{path}: format {meta.get('format')!r}, expected {SNAPSHOT_FORMAT}")
+
+    def games(prefix, ring):
+        ln = tensors[prefix + ".len"]
+        offs = np.concatenate([[0], np.cumsum(ln)]).astype(np.int64)
+        out = []
+        for i, n in enumerate(ln):
+            a, b = offs[i], offs[i + 1]
+            t = {k: tensors[f"{prefix}.{k}"][a:b] for k in ("obs", "act", "rew", "tp", "cv", "rv")}
+            g = GameHistory(observation_history=[o.astype(np.float32) for o in t["obs"]],
+                            action_history=[int(x) for x in t["act"]], reward_history=[float(x) for x in t["rew"]],
+                            to_play_history=[int(x) for x in t["tp"]], child_visits=[c for c in t["cv"]],
+                            root_values=[float(x) for x in t["rv"]])
+            if ring:
+                flags = int(tensors["shard.rean"][i])
+                if flags & 1:
+                    g.reanalysed_predicted_root_values = [float(x) for x in tensors["shard.rrv"][a:b]]
+                if flags & 2:
+                    g.reanalysed_child_visits = [c for c in tensors["shard.rcv"][a:b]]
+                if "shard.prio" in tensors:
+                    g.priorities = tensors["shard.prio"][a:b].copy()
+                    g.game_priority = float(tensors["shard.gprio"][i])
+            out.append(g)
+        return out
+
+    slots = {k: tensors["slots." + k] for k in ("len", "board", "player", "over", "ekey", "tgame", "eval")}
+    slots["reset_pending"] = bool(int(tensors["slots.flags"][0]) & 1)
+    slots["games"] = games("slots", False)
+    train = None
+    if "train.state" in tensors:
+        B, t, nref = (int(x) for x in tensors["train.state"])
+        train = dict(batch_size=B, t=t, refreshes=nref, actor=tensors["train.actor"], queued=tensors["train.queued"])
+    return dict(games=games("shard", True), slots=slots, counters=tensors["shard.counters"], train=train,
+                tensors=tensors, meta=meta)

@@ -31,6 +31,7 @@ extern "C" __global__ void mz_search_kernel_lds_res(SearchParams P);
 #include "mz_backprop_params.h"
 #include "mz_selfplay_params.h"
 #include "mz_ckpt_iface.h"
+#include "mz_snap_iface.h"
 extern "C" __global__ void mz_rnet_forward_kernel(RNetParams Q);
 extern "C" __global__ void mz_rsearch_root(RSearchParams P);
 extern "C" __global__ void mz_rsearch_tree(RSearchParams P);
@@ -4547,6 +4548,22 @@ int mz_train_set_networks_path(mz_handle* h, const char* networks_path) {
     return 0;
 }
 
+// the actors' weight set, the queued nets and the move's pinned hand-back words (once per handle)
+static int train_alloc(mz_handle* h) {
+    mz_handle::WSet& w = h->tr_actor;
+    if (w.flat) return 0;
+    MZ_TRY(h, dalloc(h, &w.flat, h->nflat));
+    MZ_TRY(h, dalloc(h, &w.Wp, h->packed_w_n));
+    if (h->packed_b_n) MZ_TRY(h, dalloc(h, &w.Bp, h->packed_b_n));
+    if (h->small_ok) { MZ_TRY(h, dalloc(h, &w.smw, h->sm_w_n)); MZ_TRY(h, dalloc(h, &w.smb, h->sm_b_n)); }
+    MZ_TRY(h, dalloc(h, &h->d_tr_queued, h->nflat));
+    MZ_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->h_tr_cnt), 4 * sizeof(long long)));
+    MZ_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->h_tr_pub), 4 * sizeof(long long), hipHostMallocCoherent));
+    std::memset(h->h_tr_pub, 0, 4 * sizeof(long long));
+    h->tr_pub_seq = 0;
+    return 0;
+}
+
 int mz_train_init_at(mz_handle* h, int32_t B, int64_t t0) {
     if (!h) return -2;
     if (t0 < 0) return fail(h, "the starting training step must be >= 0");
@@ -4555,18 +4572,8 @@ int mz_train_init_at(mz_handle* h, int32_t B, int64_t t0) {
     if (h->conf.checkpoint_interval < 1) return fail(h, "checkpoint_interval must be >= 1");
     MZ_TRY(h, hipSetDevice(h->device));
     MZ_SYNC(h);
+    if (train_alloc(h)) return -1;
     mz_handle::WSet& w = h->tr_actor;
-    if (!w.flat) {
-        MZ_TRY(h, dalloc(h, &w.flat, h->nflat));
-        MZ_TRY(h, dalloc(h, &w.Wp, h->packed_w_n));
-        if (h->packed_b_n) MZ_TRY(h, dalloc(h, &w.Bp, h->packed_b_n));
-        if (h->small_ok) { MZ_TRY(h, dalloc(h, &w.smw, h->sm_w_n)); MZ_TRY(h, dalloc(h, &w.smb, h->sm_b_n)); }
-        MZ_TRY(h, dalloc(h, &h->d_tr_queued, h->nflat));
-        MZ_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->h_tr_cnt), 4 * sizeof(long long)));
-        MZ_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->h_tr_pub), 4 * sizeof(long long), hipHostMallocCoherent));
-        std::memset(h->h_tr_pub, 0, 4 * sizeof(long long));
-        h->tr_pub_seq = 0;
-    }
     // actors and the queue start from the learner's current (initial) nets (main.jl:23)
     MZ_TRY(h, hipMemcpyAsync(w.flat, h->d_flat, h->nflat * 4, hipMemcpyDeviceToDevice, h->stream));
     MZ_TRY(h, hipMemcpyAsync(h->d_tr_queued, h->d_flat, h->nflat * 4, hipMemcpyDeviceToDevice, h->stream));
@@ -4828,3 +4835,80 @@ int mz_sync(mz_handle* h) {
 }
 
 }  // extern "C"
+
+// ---- snapshots (mz_snapshot.hip; mz_snap_iface.h): the engine's side
+// `train`: the weight sets of mz_train_init exist and belong to the view
+static void snap_fill_view(mz_handle* h, MzSnapView* v, bool train) {
+    v->device = h->device; v->stream = h->stream;
+    v->env = h->sp_env; v->G = h->sp_G; v->cap = h->sp_cap; v->T = h->sp_T; v->osz = h->sp_osz; v->A = h->A;
+    v->per = h->conf.PER != 0; v->seed = h->seed;
+    v->ring = h->sp_ring; v->hist = h->sp_hist; v->counters = h->d_sp_counters;
+    v->hist.prio = nullptr; v->hist.gprio = nullptr;      // allocated, never used: not state
+    if (!v->per) { v->ring.prio = nullptr; v->ring.gprio = nullptr; }
+    v->board = h->d_sp_board; v->player = h->d_sp_player; v->over = h->d_sp_over; v->ekey = h->d_sp_ekey;
+    v->tgame = h->d_sp_tgame; v->eval = h->d_eval;
+    v->reset_pending = h->sp_reset_pending;
+    v->train = train;
+    v->tr[0] = h->tr_B; v->tr[1] = h->tr_t; v->tr[2] = h->tr_refresh;
+    v->actor = h->tr_actor.flat; v->queued = h->d_tr_queued; v->nflat = h->nflat;
+    v->settings = "{\"reanalyse\":[" + std::to_string(h->tr_rean_mode) + "," + std::to_string(h->tr_rean_rounds) + "," +
+                  std::to_string(h->tr_rean_expl) + "],\"selfplay_mode\":[" + std::to_string(h->sp_eval) + "," +
+                  std::to_string(h->sp_opp) + "," + std::to_string(h->sp_mzp) + "],\"learner_mode\":" +
+                  std::to_string(h->learn_mode) + ",\"debug\":" +
+                  std::to_string(h->dump_tree | h->time_nets << 1 | h->time_unroll << 2) + ",\"networks_path\":" +
+                  (h->tr_ckpt_path.empty() ? "0" : "1") + "}";
+}
+
+int mz_snap_view(mz_handle* h, MzSnapView* v) {
+    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);
+    snap_fill_view(h, v, h->tr_B > 0);
+    return 0;
+}
+
+void mz_snap_engine_geometry(const mz_handle* h, mzsnap::EngineGeometry* e) {
+    const mz_config& c = h->conf;
+    const int W = c.observation_shape[0], H = c.observation_shape[1], C = c.observation_shape[2];
+    e->network = mz_net_kind(h); e->config = mz_describe(h);
+    // the envs mz_selfplay_init accepts for this config, with their record bytes per move
+    e->env_osz[MZ_ENV_TICTACTOE] = W == 3 && H == 3 && C == 3 && h->A == 9 ? 27 : 0;
+    e->env_osz[MZ_ENV_CONNECT4] = W == 6 && H == 7 && C == 3 && h->A == 7 ? 126 : 0;
+    e->env_osz[MZ_ENV_ATARI] = W == 84 && H == 84 && C == 4 && h->A == 18 && c.stacked_observations == 0 ? 84 * 84 : 0;
+    e->max_games = h->max_games; e->T = (long long)c.max_moves + 1; e->A = h->A; e->per = c.PER != 0;
+    e->seed = h->seed;
+}
+
+int mz_snap_restore_begin(mz_handle* h, int env, int G, int cap, bool rcv, bool train, MzSnapView* v) {
+    const bool had = h->sp_env >= 0;
+    const int ev = h->sp_eval, opp = h->sp_opp, mzp = h->sp_mzp;
+    if (int rc = mz_selfplay_init(h, env, G, cap)) return rc;
+    if (had) { h->sp_eval = ev; h->sp_opp = opp; h->sp_mzp = mzp; }   // a setting of the loading host
+    if (rcv) {
+        ReanParams Q = rean_params(h);
+        if (rean_search_io(h, Q)) return -1;
+        MZ_TRY(h, hipMemset(h->sp_ring.rcv, 0, (size_t)h->sp_cap * h->sp_T * h->A * 4));
+    }
+    if (train) {
+        if (h->conf.checkpoint_interval < 1) return fail(h, "checkpoint_interval must be >= 1");
+        if (train_alloc(h)) return -1;       // tr_B stays 0 until mz_snap_restore_end sets the snapshot's
+    }
+    MZ_SYNC(h);
+    snap_fill_view(h, v, train);
+    return 0;
+}
+
+int mz_snap_restore_end(mz_handle* h, const long long* counters, int reset_pending, const long long* tr) {
+    MZ_TRY(h, hipSetDevice(h->device));
+    h->sp_reset_pending = reset_pending != 0;
+    h->sp_has_games = counters[0] > 0;
+    if (tr) {
+        if (wset_repack(h, h->tr_actor, h->stream)) return -1;
+        h->tr_B = (int)tr[0]; h->tr_t = tr[1]; h->tr_refresh = tr[2];
+        h->tr_games = counters[0];
+        h->h_tr_cnt[0] = counters[0];
+    }
+    ++h->pf_epoch;                           // no batch drawn ahead survives: the next step samples in place
+    MZ_SYNC(h);
+    return 0;
+}
