@@ -20,6 +20,7 @@
 // concatenation sa = [2h ; a/|A| plane].  Activations and gradients live in
 // per-tile arenas in HBM ([rows][16] f32 per tensor).
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 enum { BP_DENSE = 0, BP_CONCAT = 1 };
@@ -174,3 +175,12 @@ struct RbpDwParams {
     float* out;                           // Flux-order data term of the gradient (2θ: mz_adam_kernel)
     double* sq;                           // [jobs]: Σθ² of each job's parameter block (f64, fixed order)
 };
+
+// ---- kernel prototypes (mz_backprop.hip)
+extern "C" __global__ void mz_bp_tile(BpParams Q);
+extern "C" __global__ void mz_bp_tile_lv(BpParams Q);
+extern "C" __global__ void mz_bp_tile_lv_nobn(BpParams Q);
+extern "C" __global__ void mz_bp_dw(BpDwParams Q);
+extern "C" __global__ void mz_bp_fold(BpFoldParams Q);
+extern "C" __global__ void mz_rbp_sample(RbpParams Q);
+extern "C" __global__ void mz_rbp_dw(RbpDwParams Q);

@@ -23,108 +23,12 @@
 
 static const size_t kLdsMax = 160 * 1024;   // LDS per workgroup on gfx950
 
-extern "C" __global__ void mz_search_kernel_lds(SearchParams P);
-extern "C" __global__ void mz_search_kernel_hbm(SearchParams P);
-extern "C" __global__ void mz_search_kernel_lds_res(SearchParams P);
 #include "mz_small_params.h"
 #include "mz_resnet_params.h"
 #include "mz_backprop_params.h"
 #include "mz_selfplay_params.h"
 #include "mz_ckpt_iface.h"
 #include "mz_snap_iface.h"
-extern "C" __global__ void mz_rnet_forward_kernel(RNetParams Q);
-extern "C" __global__ void mz_rsearch_root(RSearchParams P);
-extern "C" __global__ void mz_rsearch_tree(RSearchParams P);
-extern "C" __global__ void mz_rsearch_root32(RSearchParams P);
-extern "C" __global__ void mz_downsample_kernel(DsParams Q);
-extern "C" __global__ void mz_dsbp_fwd(DsBpParams Q);
-extern "C" __global__ void mz_dsbp_bwd(DsBpParams Q);
-extern "C" __global__ void mz_dsbp_dw(DsDwParams Q);
-extern "C" __global__ void mz_rsearch_tree32(RSearchParams P);
-extern "C" __global__ void mz_rsearch_tree_lds(RSearchParams P);
-extern "C" __global__ void mz_rsearch_tree_lds32(RSearchParams P);
-extern "C" __global__ void mz_rsearch_nets(RSearchParams P);
-extern "C" __global__ void mz_runroll_kernel(RUnrollParams U);
-extern "C" __global__ void mz_runroll_chain(RUnrollParams U);
-extern "C" __global__ void mz_bp_tile(BpParams Q);
-extern "C" __global__ void mz_bp_tile_lv(BpParams Q);
-extern "C" __global__ void mz_bp_tile_lv_nobn(BpParams Q);
-extern "C" __global__ void mz_bp_dw(BpDwParams Q);
-extern "C" __global__ void mz_rbp_sample(RbpParams Q);
-extern "C" __global__ void mz_rbp_dw(RbpDwParams Q);
-extern "C" __global__ void mz_bp_fold(BpFoldParams Q);
-extern "C" __global__ void mz_runroll_pred(RUnrollParams U);
-extern "C" __global__ void mz_runroll_pred_n(RUnrollParams U);
-extern "C" __global__ void mz_runroll_pred_n1(RUnrollParams U);
-extern "C" __global__ void mz_runroll_chain1(RUnrollParams U);
-extern "C" __global__ void mz_runroll_chain_r(RUnrollParams U);
-extern "C" __global__ void mz_runroll_chain_r3(RUnrollParams U);
-extern "C" __global__ void mz_runroll_pred_r(RUnrollParams U);
-extern "C" __global__ void mz_runroll_fused_r(RUnrollParams U);
-extern "C" __global__ void mz_runroll_fused_r3(RUnrollParams U);
-extern "C" __global__ void mz_sp_prepare(SpParams S);
-extern "C" __global__ void mz_sp_commit(SpParams S);
-extern "C" __global__ void mz_sp_order(SpParams S);
-extern "C" __global__ void mz_sp_store(SpParams S);
-extern "C" __global__ void mz_sp_reset(SpParams S);
-extern "C" __global__ void mz_rp_sample(RpSampleParams Q);
-extern "C" __global__ void mz_rp_per_init(SpHist ring, int slot, int len, int Tmax, int td, const float* disc_pow,
-                                          int alpha);
-extern "C" __global__ void mz_rp_per_prep(SpHist ring, const long long* counters, int cap, float* cum, float* prob,
-                                          long long* total);
-extern "C" __global__ void mz_rp_per_norm(float* w, int B);
-extern "C" __global__ void mz_rp_per_update(SpHist ring, const long long* counters, int cap, int Tmax, int B, int K,
-                                            int alpha, const int32_t* index, const float* pv, const float* tv);
-extern "C" __global__ void mz_reanalyse_fc(ReanParams Q);
-extern "C" __global__ void mz_reanalyse_gather(ReanParams Q);
-extern "C" __global__ void mz_reanalyse_scatter(ReanParams Q);
-extern "C" __global__ void mz_reanalyse_clear(int32_t* rean, int cap);
-extern "C" __global__ void mz_reanalyse_sgather(ReanParams Q);
-extern "C" __global__ void mz_reanalyse_sscatter(ReanParams Q);
-extern "C" __global__ void mz_reanalyse_pack(ReanParams Q, int32_t* rows);
-extern "C" __global__ void mz_reanalyse_seek(long long* counters, long long game_number);
-extern "C" __global__ void mz_search_small1(SmallParams P);
-extern "C" __global__ void mz_search_small2(SmallParams P);
-extern "C" __global__ void mz_search_small4(SmallParams P);
-extern "C" __global__ void mz_search_small1_bn(SmallParams P);
-extern "C" __global__ void mz_search_small2_bn(SmallParams P);
-extern "C" __global__ void mz_search_small4_bn(SmallParams P);
-extern "C" __global__ void mz_unroll_small1(SmallUnrollParams P);
-extern "C" __global__ void mz_unroll_small2(SmallUnrollParams P);
-extern "C" __global__ void mz_unroll_small1_bn(SmallUnrollParams P);
-extern "C" __global__ void mz_unroll_small2_bn(SmallUnrollParams P);
-extern "C" __global__ void mz_learn_small1(SmallUnrollParams P, LearnParams L);
-extern "C" __global__ void mz_learn_small2(SmallUnrollParams P, LearnParams L);
-extern "C" __global__ void mz_learn_small1_bn(SmallUnrollParams P, LearnParams L);
-extern "C" __global__ void mz_learn_small2_bn(SmallUnrollParams P, LearnParams L);
-extern "C" __global__ void mz_learn_chain(ChainParams C);
-extern "C" __global__ void mz_learn_multi1(SmallUnrollParams P, LearnMultiParams M);
-extern "C" __global__ void mz_learn_multi2(SmallUnrollParams P, LearnMultiParams M);
-extern "C" __global__ void mz_learn_multi1_bn(SmallUnrollParams P, LearnMultiParams M);
-extern "C" __global__ void mz_learn_multi4(SmallUnrollParams P, LearnMultiParams M);
-extern "C" __global__ void mz_learn_multi4_bn(SmallUnrollParams P, LearnMultiParams M);
-extern "C" __global__ void mz_learn_multi2_bn(SmallUnrollParams P, LearnMultiParams M);
-extern "C" __global__ void mz_learner_loss_multi(LossMultiParams M);
-extern "C" __global__ void mz_learner_loss_multi32(LossMultiParams M);
-extern "C" __global__ void mz_search_kernel_hbm_res(SearchParams P);
-
-extern "C" __global__ void mz_unroll_kernel(UnrollParams P);
-extern "C" __global__ void mz_forward_kernel(const int* plan, const float* Wp, const float* Bp, int total_lds,
-                                             int in_off, int in_feat, const float* x, int n, int out0_off, int o0,
-                                             float* out0, int out1_off, int o1, float* out1, int sm1, int act0,
-                                             int act1);
-extern "C" __global__ void mz_learner_grad_kernel(int B, int K, int A, int v_act, int r_act, float* pv, float* pp,
-                                                  float* pr, const float* tv, const float* tp, const float* gscale,
-                                                  float* terms, float* flat, const size_t* netoff, float* G,
-                                                  double* part, unsigned* counter, float* out, const float* wts, LgAdam ad);
-extern "C" __global__ void mz_learner_grad_kernel32(int B, int K, int A, int v_act, int r_act, float* pv, float* pp,
-                                                    float* pr, const float* tv, const float* tp, const float* gscale,
-                                                    float* terms, float* flat, const size_t* netoff, float* G,
-                                                    double* part, unsigned* counter, float* out, const float* wts, LgAdam ad);
-extern "C" __global__ void mz_adam_kernel(float* P, float* M, float* V, const float* G, float gscale, size_t n,
-                                          double bp1, double bp2, double eta, float* Wp, float* Bp,
-                                          const int* inv_tile, float* smw, float* smb, const int* inv_small);
-extern "C" __global__ void mz_repack_kernel(const float* flat, const int* src, float* packed, size_t n);
 
 namespace {
 
@@ -401,6 +305,8 @@ struct mz_handle {
     } while (0)
 
 static int fail(mz_handle* h, const std::string& m) { h->err = m; return -2; }
+// the stream of a `_dev` call: the caller's, or the handle's own
+static hipStream_t stream_of(const mz_handle* h, void* stream) { return stream ? (hipStream_t)stream : h->stream; }
 static int timing_events(mz_handle* h, hipEvent_t* e0, hipEvent_t* e1);
 
 // Host-synchronous entry points (weights, state, replay read-outs, debug
@@ -1952,7 +1858,7 @@ static int search_dev(mz_handle* h, int G, const float* obs, const uint8_t* lega
     if (G == 0) return 0;
     if (h->kind == 1)
         return rsearch(h, G, obs, legal_mask, to_play, exploration, rng_step, game_offset, temperature,
-                       child_visits, root_value, action_out, stream ? (hipStream_t)stream : h->stream, temp_g);
+                       child_visits, root_value, action_out, stream_of(h, stream), temp_g);
     SearchParams P;
     std::memset(&P, 0, sizeof(P));
     P.temp_g = temp_g;
@@ -1971,7 +1877,7 @@ static int search_dev(mz_handle* h, int G, const float* obs, const uint8_t* lega
     if (!h->d_stamps) MZ_TRY(h, dalloc(h, &h->d_stamps, (size_t)8 * h->max_games));
     P.stamps = h->d_stamps;
 #endif
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     const bool small = h->small_ok && h->force_kernel != 1 && (h->force_kernel == 2 || G <= 4 * h->n_cu);
     if (small) {
         const int T = h->force_T ? h->force_T : G <= h->n_cu ? 1 : G <= 2 * h->n_cu ? 2 : 4;
@@ -2153,67 +2059,85 @@ static int ensure_batch(mz_handle* h, int B) {
     return 0;
 }
 
-static size_t runroll_lds(const mz_handle* h) {
-    return std::max(h->rn_lds[0], std::max(h->rn_lds[1], h->rn_lds[2]));
-}
-
 static int learner_losses(mz_handle* h, const mz_batch* b, float* grad_dev, float* losses_dev, hipStream_t st,
                           int v_act, int r_act, bool fuse_adam = false, double eta = 0.0, bool l2_done = false);
 static void adam_advance(mz_handle* h);
 
-// ResNet learner: the unroll on the network kernels, then the shared loss /
-// ∇ = 2θ kernel (the plans' outputs are already activated)
-static int rlearner_grad(mz_handle* h, const mz_batch* b, float* grad_dev, float* losses_dev, void* stream,
-                         bool fuse_adam = false, double eta = 0.0, const RpSampleParams* rq = nullptr) {
-    const int B = b->batch_size;
-    if (B < 1) return fail(h, "batch_size must be >= 1");
-    if (ensure_batch(h, B)) return -1;
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    RUnrollParams U;
+// the instance of a small-kernel family for T = {1, 2, 4}[ti] samples per workgroup (mz_small.hip)
+enum { SMK_UNROLL = 0, SMK_LEARN = 1, SMK_MULTI = 2 };
+static const void* small_kernel(const mz_handle* h, int family, int ti) {
+    static const void* const k[3][2][3] = {
+        {{(const void*)mz_unroll_small1, (const void*)mz_unroll_small2, nullptr},
+         {(const void*)mz_unroll_small1_bn, (const void*)mz_unroll_small2_bn, nullptr}},
+        {{(const void*)mz_learn_small1, (const void*)mz_learn_small2, nullptr},
+         {(const void*)mz_learn_small1_bn, (const void*)mz_learn_small2_bn, nullptr}},
+        {{(const void*)mz_learn_multi1, (const void*)mz_learn_multi2, (const void*)mz_learn_multi4},
+         {(const void*)mz_learn_multi1_bn, (const void*)mz_learn_multi2_bn, (const void*)mz_learn_multi4_bn}}};
+    return k[family][h->sm_bn ? 1 : 0][ti];
+}
+
+// ---- the ResNet learner unroll (mz_runroll_*), one step or the steps of a multi-step sub-chunk
+static size_t runroll_lds(const mz_handle* h) {
+    return std::max(h->rn_lds[0], std::max(h->rn_lds[1], h->rn_lds[2]));
+}
+// MZ_RUNROLL_FUSED=1: the one-kernel unroll (mz_runroll_kernel, one step per call only); read once, so the
+// value is fixed at the first learner call of the process
+static bool runroll_one_kernel() {
+    static const bool on = std::getenv("MZ_RUNROLL_FUSED") != nullptr;
+    return on;
+}
+// the parameters every unroll launch of the engine shares; the caller adds its batch, read-outs,
+// scratch and parameter images (and the ms_* strides of a multi-step launch)
+static void runroll_params(const mz_handle* h, int B, RUnrollParams& U) {   // (filled in place: no copy)
     std::memset(&U, 0, sizeof(U));                 // (ms = 0: one step; the fused-ADAM fields unused unless set)
     U.B = B; U.K = h->conf.num_unroll_steps; U.A = h->A; U.H = h->H;
     U.W = h->rconf.observation_shape[0]; U.P = h->plane; U.obs_feat = h->rin_feat; U.ng = h->rn_ng; U.bn_s = h->bn_s;
-    U.obs = b->observation; U.actions = b->actions;
-    if (h->ds) {                                    // representation (:347): downsampler, then the tail
-        if (ensure_dsb(h, B) || ds_launch(h, b->observation, h->d_dsb, B, st)) return -1;
-        U.obs = h->d_dsb;
-    } U.pv = h->d_pv; U.pp = h->d_pp; U.pr = h->d_pr;
-    U.hs = h->d_rhs; U.plans = h->d_rplan; U.Wimg = h->d_Wp; U.flat = h->d_flat;
-    U.plans_l = h->d_rplan_l; U.ng_l = h->rn_ng_l;
-    U.dyn_split = h->rn_dyn_split; U.ts = h->d_rts; U.otab = h->d_rtab;
-    U.stamps = nullptr;
-#ifdef MZ_STAMPS
-    if (!h->d_stamps) MZ_TRY(h, dalloc(h, &h->d_stamps, (size_t)8 * std::max(h->max_games, 128)));
-    U.stamps = h->d_stamps;
-#endif
+    U.plans = h->d_rplan; U.plans_l = h->d_rplan_l; U.ng_l = h->rn_ng_l;
+    U.dyn_split = h->rn_dyn_split; U.otab = h->d_rtab;
+}
+// Launch the unroll of U: one step (steps = 0: U.ms = 0, grid z = 1) or `steps` steps on gridDim.z.
+// prog / epoch: the fused launch's progress words and its launch counter (the one-step launch:
+// d_prog, which must exist; the multi-step launch: the steps' slice of d_ml_prog).  One step only:
+// rq (the get_batch launch, folded into the fused launch when it applies) and fuse_adam (the Σθ² /
+// ADAM slices beside the fused unroll into the second image set; *l2_fused tells the caller to swap
+// the sets).  Leaves the launched kernels' names in last_lvariant.
+static int runroll_launch(mz_handle* h, RUnrollParams& U, int steps, hipStream_t st, unsigned long long* prog,
+                          unsigned long long* epoch, const RpSampleParams* rq = nullptr, bool fuse_adam = false,
+                          double eta = 0.0, bool* l2_fused = nullptr) {
+    const int B = U.B, KH = std::max(U.K, 1);
+    const unsigned nz = steps ? steps : 1;
     void* args[] = {&U};
-    const int KH = std::max(U.K, 1);
+    U.ms = steps;
     // the B·K predictions on wide tiles (ng items) once they fill the chip
     // (B = 2048: 640 workgroups; one-item tiles there measured 2.4x slower),
     // else one-item tiles (B = 32: 160 workgroups instead of 10)
     static const bool wide_env = std::getenv("MZ_RN_PRED_WIDE") != nullptr;
-    static const bool one_kernel = std::getenv("MZ_RUNROLL_FUSED") != nullptr;
+    const bool one_kernel = !steps && runroll_one_kernel();
     const bool wide_p = wide_env || (B * KH + U.ng - 1) / U.ng >= h->n_cu;
     // one launch (mz_runroll_fused_r): the chain blocks, then the items, each
     // item waiting for its sample's chain instead of the whole launch; with
     // rq, each chain block also draws its sample (the get_batch launch folded in)
     static const bool no_fuse = std::getenv("MZ_RN_NO_FUSE") != nullptr;
     const bool fused = !one_kernel && h->rd_chain && h->rp_pred && !wide_p && !no_fuse && U.ng_l == 1 &&
-                       U.K + 1 < 64 && !h->ds && h->d_prog;
+                       U.K + 1 < 64 && !h->ds && prog;
     static const bool no_fuse_sample = std::getenv("MZ_RN_NO_FUSE_SAMPLE") != nullptr;   // A/B only
     static const bool no_fuse_adam = std::getenv("MZ_RN_NO_FUSE_ADAM") != nullptr;       // A/B only
-    bool l2_fused = false;
     if (rq && (!fused || no_fuse_sample)) {
         hipLaunchKernelGGL(mz_rp_sample, dim3((B + 3) / 4), dim3(256), 0, st, *rq);
         MZ_TRY(h, hipGetLastError());
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;          // mz_debug_enable flag 4: the unroll launches' duration
     if (h->time_unroll) {
         if (timing_events(h, &e0, &e1)) return -1;
         MZ_TRY(h, hipEventRecord(e0, st));
     }
+    if (fused || steps) {                           // (a multi-step launch carries these in every form)
+        U.rp_nv = 3 + h->rhp.depth_value;           // value head: conv, Dense, depth_value × Dense, Dense
+        U.fault = h->d_fault; U.poll_ticks = h->poll_ticks; U.dbg_skip = h->dbg_skip;
+    }
+    std::string& variant = h->last_lvariant;        // (assigned in place: no allocation per launch)
     if (one_kernel) {          // the one-kernel unroll (pred inside the chain)
-        h->last_lvariant = "mz_runroll_kernel";
+        variant = "mz_runroll_kernel";
         MZ_TRY(h, hipLaunchKernel((const void*)mz_runroll_kernel, dim3((B + U.ng - 1) / U.ng), dim3(RN_THREADS),
                                   args, runroll_lds(h), st));
     } else {                                        // chain on narrow tiles, then the B·K predictions
@@ -2226,52 +2150,81 @@ static int rlearner_grad(mz_handle* h, const mz_batch* b, float* grad_dev, float
         const bool nb1 = (U.P * U.ng_l + 15) / 16 == 1 || !nb3;
         U.rd_ep_off = (int)(h->rn_lds_l / 4);
         U.rd_trunk_nl = 1 + 2 * h->rhp.num_blocks;
-        h->last_lvariant = std::string(h->rd_chain ? (h->rd_nb == 3 ? "mz_runroll_chain_r3" : "mz_runroll_chain_r")
-                                                   : nb1 ? "mz_runroll_chain1" : "mz_runroll_chain") +
-                           (wide_p ? "+mz_runroll_pred" : h->rp_pred ? "+mz_runroll_pred_r" : nb1 ? "+mz_runroll_pred_n1"
-                                                                                       : "+mz_runroll_pred_n");
+        const unsigned nchain = (B + U.ng_l - 1) / U.ng_l, ny = U.K > 0 ? 2 : 1;
         if (fused) {
-            U.prog = h->d_prog;
-            U.prog_base = (++h->prog_epoch) * 64ull;
-            U.fault = h->d_fault; U.poll_ticks = h->poll_ticks; U.dbg_skip = h->dbg_skip;
+            U.prog = prog;
+            U.prog_base = (++*epoch) * 64ull;
             U.n_chain = B;
             U.fuse_sample = rq != nullptr && !no_fuse_sample;
             if (rq) U.rq = *rq;
             // ADAM beside the unroll: the launch reads the current image (d_Wp) and
             // writes the updated one into d_Wp2, swapped after the launch
             U.n_l2 = fuse_adam && h->d_Wp2 && !no_fuse_adam ? 96 : 0;
-            U.ad = LgAdam{1, h->d_m, h->d_v, h->bp1, h->bp2, eta, h->d_Wp2, h->d_Bp, h->d_inv_tile, nullptr,
-                          nullptr, h->d_inv_small};
-            U.flat_w = h->d_flat; U.netoff = h->d_netoff; U.part = h->d_sq;
-            l2_fused = U.n_l2 > 0;
-            h->last_lvariant = h->rd_nb == 3 ? "mz_runroll_fused_r3" : "mz_runroll_fused_r";
-            U.rp_nv = 3 + h->rhp.depth_value;       // value head: conv, Dense, depth_value × Dense, Dense
+            if (!steps) {
+                U.ad = LgAdam{1, h->d_m, h->d_v, h->bp1, h->bp2, eta, h->d_Wp2, h->d_Bp, h->d_inv_tile, nullptr,
+                              nullptr, h->d_inv_small};
+                U.flat_w = h->d_flat; U.netoff = h->d_netoff; U.part = h->d_sq;
+            }
+            if (l2_fused) *l2_fused = U.n_l2 > 0;
+            variant = h->rd_nb == 3 ? "mz_runroll_fused_r3" : "mz_runroll_fused_r";
             const int nitems = B * KH * (U.K > 0 ? 3 : 2);
             MZ_TRY(h, hipLaunchKernel(h->rd_nb == 3 ? (const void*)mz_runroll_fused_r3 : (const void*)mz_runroll_fused_r,
-                                      dim3(B + U.n_l2 + nitems), dim3(RD_THREADS), args,
+                                      dim3(nz * (B + U.n_l2 + nitems)), dim3(RD_THREADS), args,
                                       std::max(rd_chain_lds(h), rp_pred_lds(h)), st));
-        } else if (h->rd_chain)
-            MZ_TRY(h, hipLaunchKernel(h->rd_nb == 3 ? (const void*)mz_runroll_chain_r3 : (const void*)mz_runroll_chain_r,
-                                      dim3((B + U.ng_l - 1) / U.ng_l),
-                                      dim3(RD_THREADS), args, rd_chain_lds(h), st));
-        else
-            MZ_TRY(h, hipLaunchKernel(nb1 ? (const void*)mz_runroll_chain1 : (const void*)mz_runroll_chain,
-                                      dim3((B + U.ng_l - 1) / U.ng_l), dim3(RN_THREADS),
-                                      args, h->rn_lds_l, st));
-        // the B·K predictions and reward heads (wide_p above)
-        if (fused) {
-        } else if (wide_p)
-            MZ_TRY(h, hipLaunchKernel((const void*)mz_runroll_pred, dim3((B * KH + U.ng - 1) / U.ng, U.K > 0 ? 2 : 1),
-                                      dim3(RN_THREADS), args, runroll_lds(h), st));
-        else if (h->rp_pred)
-            MZ_TRY(h, hipLaunchKernel((const void*)mz_runroll_pred_r, dim3((B * KH + U.ng_l - 1) / U.ng_l,
-                                      U.K > 0 ? 2 : 1), dim3(RD_THREADS), args, rp_pred_lds(h), st));
-        else
-            MZ_TRY(h, hipLaunchKernel(nb1 ? (const void*)mz_runroll_pred_n1 : (const void*)mz_runroll_pred_n,
-                                      dim3((B * KH + U.ng_l - 1) / U.ng_l, U.K > 0 ? 2 : 1), dim3(RN_THREADS), args,
-                                      h->rn_lds_l, st));
+        } else {
+            const void* kchain;
+            if (h->rd_chain) {
+                kchain = h->rd_nb == 3 ? (const void*)mz_runroll_chain_r3 : (const void*)mz_runroll_chain_r;
+                variant = h->rd_nb == 3 ? "mz_runroll_chain_r3" : "mz_runroll_chain_r";
+            } else {
+                kchain = nb1 ? (const void*)mz_runroll_chain1 : (const void*)mz_runroll_chain;
+                variant = nb1 ? "mz_runroll_chain1" : "mz_runroll_chain";
+            }
+            MZ_TRY(h, hipLaunchKernel(kchain, dim3(nchain, 1, nz), dim3(h->rd_chain ? RD_THREADS : RN_THREADS), args,
+                                      h->rd_chain ? rd_chain_lds(h) : h->rn_lds_l, st));
+            // the B·K predictions and reward heads (wide_p above)
+            if (wide_p) {
+                variant += "+mz_runroll_pred";
+                MZ_TRY(h, hipLaunchKernel((const void*)mz_runroll_pred, dim3((B * KH + U.ng - 1) / U.ng, ny, nz),
+                                          dim3(RN_THREADS), args, runroll_lds(h), st));
+            } else if (h->rp_pred) {
+                variant += "+mz_runroll_pred_r";
+                MZ_TRY(h, hipLaunchKernel((const void*)mz_runroll_pred_r, dim3((B * KH + U.ng_l - 1) / U.ng_l, ny, nz),
+                                          dim3(RD_THREADS), args, rp_pred_lds(h), st));
+            } else {
+                variant += nb1 ? "+mz_runroll_pred_n1" : "+mz_runroll_pred_n";
+                MZ_TRY(h, hipLaunchKernel(nb1 ? (const void*)mz_runroll_pred_n1 : (const void*)mz_runroll_pred_n,
+                                          dim3((B * KH + U.ng_l - 1) / U.ng_l, ny, nz), dim3(RN_THREADS), args,
+                                          h->rn_lds_l, st));
+            }
+        }
     }
     if (e1) MZ_TRY(h, hipEventRecord(e1, st));
+    return 0;
+}
+
+// ResNet learner: the unroll on the network kernels, then the shared loss /
+// ∇ = 2θ kernel (the plans' outputs are already activated)
+static int rlearner_grad(mz_handle* h, const mz_batch* b, float* grad_dev, float* losses_dev, hipStream_t st,
+                         bool fuse_adam = false, double eta = 0.0, const RpSampleParams* rq = nullptr) {
+    const int B = b->batch_size;
+    if (B < 1) return fail(h, "batch_size must be >= 1");
+    if (ensure_batch(h, B)) return -1;
+    RUnrollParams U;
+    runroll_params(h, B, U);
+    U.obs = b->observation; U.actions = b->actions;
+    if (h->ds) {                                    // representation (:347): downsampler, then the tail
+        if (ensure_dsb(h, B) || ds_launch(h, b->observation, h->d_dsb, B, st)) return -1;
+        U.obs = h->d_dsb;
+    }
+    U.pv = h->d_pv; U.pp = h->d_pp; U.pr = h->d_pr;
+    U.hs = h->d_rhs; U.ts = h->d_rts; U.Wimg = h->d_Wp; U.flat = h->d_flat;
+#ifdef MZ_STAMPS
+    if (!h->d_stamps) MZ_TRY(h, dalloc(h, &h->d_stamps, (size_t)8 * std::max(h->max_games, 128)));
+    U.stamps = h->d_stamps;
+#endif
+    bool l2_fused = false;
+    if (runroll_launch(h, U, 0, st, h->d_prog, &h->prog_epoch, rq, fuse_adam, eta, &l2_fused)) return -1;
     if (learner_losses(h, b, grad_dev, losses_dev, st, MZ_ACT_IDENTITY, MZ_ACT_IDENTITY, fuse_adam, eta, l2_fused))
         return -1;
     if (l2_fused) {
@@ -2292,10 +2245,10 @@ int mz_learner_grad_dev(mz_handle* h, const mz_batch* b, float* grad_dev, float*
     if (!h || !b) return -2;
     if (b->batch_size < 1) return fail(h, "batch_size must be >= 1");
     if (h->learn_mode == MZ_LEARN_CORRECTED)
-        return bp_grad(h, b, grad_dev, losses_dev, stream ? (hipStream_t)stream : h->stream);
-    if (h->kind == 1) return rlearner_grad(h, b, grad_dev, losses_dev, stream);
+        return bp_grad(h, b, grad_dev, losses_dev, stream_of(h, stream));
+    if (h->kind == 1) return rlearner_grad(h, b, grad_dev, losses_dev, stream_of(h, stream));
     if (ensure_batch(h, b->batch_size)) return -1;
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     if (fc_unroll(h, b, st, nullptr)) return -1;
     return learner_losses(h, b, grad_dev, losses_dev, st, h->lay.v_act, h->lay.r_act);
 }
@@ -2313,9 +2266,8 @@ static int fc_unroll(mz_handle* h, const mz_batch* b, hipStream_t st, const RpSa
         SmallUnrollParams U;
         if (small_unroll_params(h, b, ti, rp, &U)) return -1;
         void* args[] = {&U};
-        MZ_TRY(h, hipLaunchKernel(h->sm_bn ? (ti == 0 ? (const void*)mz_unroll_small1_bn : (const void*)mz_unroll_small2_bn)
-                                           : (ti == 0 ? (const void*)mz_unroll_small1 : (const void*)mz_unroll_small2),
-                                  dim3((B + T - 1) / T), dim3(SM_THREADS), args, unroll_small_lds(h, ti), st));
+        MZ_TRY(h, hipLaunchKernel(small_kernel(h, SMK_UNROLL, ti), dim3((B + T - 1) / T), dim3(SM_THREADS), args,
+                                  unroll_small_lds(h, ti), st));
         h->last_lvariant = ti == 0 ? "mz_unroll_small1" : "mz_unroll_small2";
     } else {
         if (rp) {
@@ -3006,7 +2958,7 @@ int mz_learner_set_mode(mz_handle* h, int mode) {
 
 int mz_learner_apply_dev(mz_handle* h, const float* grad_dev, float grad_scale, double eta, void* stream) {
     if (!h) return -2;
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     const float* g = grad_dev ? grad_dev : h->d_grad;
     hipLaunchKernelGGL(mz_adam_kernel, dim3(128), dim3(MZ_THREADS), 0, st, h->d_flat, h->d_m, h->d_v, g,
                        grad_scale, h->nflat, h->bp1, h->bp2, eta, h->d_Wp, h->d_Bp, h->d_inv_tile, h->d_sm_w,
@@ -3343,7 +3295,7 @@ int mz_selfplay_move(mz_handle* h, uint32_t rng_step, uint32_t game_offset, floa
     if (!h) return -2;
     if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
     MZ_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     SpParams S = sp_params(h);
     S.step = rng_step; S.game_offset = game_offset;
     // temperature_threshold (SelfPlay.jl:344-346): per-slot temperatures
@@ -3514,7 +3466,7 @@ static int per_update(mz_handle* h, int B, hipStream_t st) {
 int mz_replay_sample(mz_handle* h, int32_t B, uint32_t step, mz_batch* batch, int32_t* index_batch, void* stream) {
     if (!h || !batch) return -2;
     MZ_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     RpSampleParams Q;
     if (rs_params(h, B, step, st, &Q, batch)) return -1;
     hipLaunchKernelGGL(mz_rp_sample, dim3((B + 3) / 4), dim3(256), 0, st, Q);
@@ -3627,10 +3579,8 @@ static int learner_sampled(mz_handle* h, int32_t B, uint32_t step, float* grad_d
         static const bool xcd = std::getenv("MZ_LEARN_XCD") != nullptr;
         L.xcd = xcd && L.nU <= h->n_cu / 8 && 8 * L.nU >= roles;
         void* args[] = {&U, &L};
-        MZ_TRY(h, hipLaunchKernel(h->sm_bn ? (ti == 0 ? (const void*)mz_learn_small1_bn : (const void*)mz_learn_small2_bn)
-                                           : (ti == 0 ? (const void*)mz_learn_small1 : (const void*)mz_learn_small2),
-                                  dim3(L.xcd ? 8 * L.nU : roles), dim3(SM_THREADS), args,
-                                  unroll_small_lds(h, ti), st));
+        MZ_TRY(h, hipLaunchKernel(small_kernel(h, SMK_LEARN, ti), dim3(L.xcd ? 8 * L.nU : roles), dim3(SM_THREADS),
+                                  args, unroll_small_lds(h, ti), st));
         if (pf) h->pf_cur = 1 - cur;
         h->last_lvariant = ti == 0 ? "mz_learn_small1" : "mz_learn_small2";
         std::swap(h->d_Wp, h->d_Wp2); std::swap(h->d_Bp, h->d_Bp2);
@@ -3650,7 +3600,7 @@ int mz_replay_update_priorities(mz_handle* h, void* stream) {
     if (!h->conf.PER) return fail(h, "PER is off in the config");
     if (h->rs_last_B <= 0) return fail(h, "no batch sampled yet");
     MZ_TRY(h, hipSetDevice(h->device));
-    return per_update(h, h->rs_last_B, stream ? (hipStream_t)stream : h->stream);
+    return per_update(h, h->rs_last_B, stream_of(h, stream));
 }
 
 int mz_replay_get_priorities(mz_handle* h, int32_t i, float* priorities, float* game_priority) {
@@ -3674,7 +3624,7 @@ int mz_replay_get_priorities(mz_handle* h, int32_t i, float* priorities, float* 
 int mz_learner_grad_sampled_dev(mz_handle* h, int32_t B, uint32_t step, float* grad_dev, float* losses_dev,
                                 void* stream) {
     if (!h) return -2;
-    return learner_sampled(h, B, step, grad_dev, losses_dev, stream ? (hipStream_t)stream : h->stream, false, 0.0);
+    return learner_sampled(h, B, step, grad_dev, losses_dev, stream_of(h, stream), false, 0.0);
 }
 
 // ---- data-parallel learner over RCCL through the C ABI
@@ -3703,7 +3653,7 @@ int mz_dp_init(mz_handle* h, int rank, int world, const uint8_t* id) {
 int mz_dp_allreduce(mz_handle* h, float* grad_dev, void* stream) {
     if (!h) return -2;
     if (!h->dp_comm) return fail(h, "mz_dp_init first");
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     float* g = grad_dev ? grad_dev : h->d_grad;
     // ncclFloat32 = 7, ncclSum = 0
     const int rc = rccl().allreduce(g, g, h->nflat, 7, 0, h->dp_comm, st);
@@ -3714,7 +3664,7 @@ int mz_dp_allreduce(mz_handle* h, float* grad_dev, void* stream) {
 int mz_learner_train_dp(mz_handle* h, int32_t B, uint32_t step, double eta, float* losses_dev, void* stream) {
     if (!h) return -2;
     if (!h->dp_comm) return fail(h, "mz_dp_init first");
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     if (learner_sampled(h, B, step, nullptr, losses_dev, st, false, 0.0)) return -1;
     if (mz_dp_allreduce(h, nullptr, st)) return -1;
     return mz_learner_apply_dev(h, nullptr, 1.0f / (float)h->dp_world, eta, st);
@@ -3722,7 +3672,7 @@ int mz_learner_train_dp(mz_handle* h, int32_t B, uint32_t step, double eta, floa
 
 int mz_learner_train_dev(mz_handle* h, int32_t B, uint32_t step, double eta, float* losses_dev, void* stream) {
     if (!h) return -2;
-    return learner_sampled(h, B, step, nullptr, losses_dev, stream ? (hipStream_t)stream : h->stream, true, eta);
+    return learner_sampled(h, B, step, nullptr, losses_dev, stream_of(h, stream), true, eta);
 }
 
 // ---- L consecutive ref_semantics learner steps (ChainParams, mz_small_params.h;
@@ -3733,16 +3683,21 @@ int mz_learner_train_dev(mz_handle* h, int32_t B, uint32_t step, double eta, flo
 // sub-chunk's chain on a second stream, ordered by events, beside the unroll
 // launch — 228.8 k vs 279.5 k steps/s at L = 64, 114.6 k vs ~170 k at L = 8:
 // the cross-stream event waits cost more than the chain they hide.)
+static bool no_multi() { return std::getenv("MZ_NO_MULTI") != nullptr; }
+static int multi_ls_env() {
+    static const int ls = std::getenv("MZ_MULTI_LS") ? std::atoi(std::getenv("MZ_MULTI_LS")) : 0;
+    return ls;
+}
 static bool multi_ok(const mz_handle* h) {
     return h->kind == 0 && h->learn_mode == MZ_LEARN_REF_SEMANTICS && !h->conf.PER && h->small_ok && h->A <= 16 &&
-           h->d_sm_w2 && !std::getenv("MZ_NO_MULTI");
+           h->d_sm_w2 && !no_multi();
 }
 // Sub-chunk length Ls and T per workgroup for L steps of B samples: one sample
 // per workgroup while the L·B workgroups fit one per CU; else two, with as
 // many steps per sub-chunk as keep one workgroup per CU (16 at B = 32)
 static int multi_plan(const mz_handle* h, int B, int L, int* Ls) {
     static const int force = std::getenv("MZ_MULTI_T") ? std::atoi(std::getenv("MZ_MULTI_T")) : 0;   // tests / A/B
-    static const int ls_env = std::getenv("MZ_MULTI_LS") ? std::atoi(std::getenv("MZ_MULTI_LS")) : 0;
+    const int ls_env = multi_ls_env();
     int ti;
     // T = 4 (round 6) when the call has the steps to fill the chip with 4 samples per workgroup
     // (twice the steps per unroll launch as T = 2 for about 1.1x a stage's cost); T = 2 when L·B
@@ -3835,8 +3790,8 @@ static int ensure_multi(mz_handle* h, int B, int L) {
 // form with the steps on gridDim.z (the fused form: step-major chain blocks, then the items;
 // RUnrollParams.ms) and one loss launch of Ls·nlb blocks
 static bool rmulti_ok(const mz_handle* h) {
-    return h->kind == 1 && h->learn_mode == MZ_LEARN_REF_SEMANTICS && !h->conf.PER && !std::getenv("MZ_NO_MULTI") &&
-           !std::getenv("MZ_RUNROLL_FUSED");
+    return h->kind == 1 && h->learn_mode == MZ_LEARN_REF_SEMANTICS && !h->conf.PER && !no_multi() &&
+           !runroll_one_kernel();
 }
 static int ensure_multi(mz_handle* h, int B, int L);
 // θ after up to two given steps, copied out by the chain launch that computes them (mz_train_run:
@@ -3887,153 +3842,132 @@ static void set_caps(ChainParams& C, const MultiCap* cap, int64_t first, int nc)
         if (cap->imaged0) *cap->imaged0 = true;
     }
 }
+// the per-step strides of the ring arrays (ensure_multi): observations, (K+1)-rows, policies
+struct MultiStrides { int B; size_t s_obs, s_k1, s_tp; };
+// q = get_batch of learner step `step` into ring slot `slot` (Q: slot 0), written in place
+static void rs_at(RpSampleParams& q, const RpSampleParams& Q, uint32_t step, int slot, const MultiStrides& S) {
+    q = Q;
+    q.step = step;
+    q.obs += slot * S.s_obs; q.actions += slot * S.s_k1; q.tv += slot * S.s_k1; q.tr += slot * S.s_k1;
+    q.tpol += slot * S.s_tp; q.gscale += (size_t)slot * S.B; q.index += (size_t)slot * 2 * S.B;
+}
+
+// The multi-step driver: chain launches of up to MZ_MULTI_MAX steps (the ADAM iterations into bank
+// half k mod 2, the steps' batches with chain_sample), each followed by its steps' sub-chunks of up to
+// Ls steps, body(c0, j0, n, ir, Qk, C): the unrolls and losses of the n steps from c0 + j0 on (ring
+// slots ir .., batches Qk, parameters at + j0 in C's banks).  Q: get_batch into ring slot 0.
+extern "C++" {                                   // (a template: not in the ABI block's linkage)
+template <class Body>
+static int multi_drive(mz_handle* h, uint32_t step0, int L, int Ls, const double* eta, float* theta_dev,
+                       hipStream_t st, const MultiCap* cap, const RpSampleParams& Q, const MultiStrides& S,
+                       bool chain_sample, Body body) {
+    const int B = S.B;
+    const size_t nw = h->packed_w_n, nb = std::max<size_t>(h->packed_b_n, 1);
+    double p1 = h->bp1, p2 = h->bp2;
+    const int Lc = std::min(L, std::max(Ls, MZ_MULTI_MAX / Ls * Ls));
+    const int R = 2 * MZ_MULTI_MAX / Lc * Lc;       // the per-step scratch ring (ensure_multi)
+    for (int k = 0, c0 = 0; c0 < L; ++k, c0 += Lc) {
+        const int nc = std::min(Lc, L - c0), half = k & 1, cr = c0 % R;
+        // 1. the ADAM chain θ_{t+c0} .. θ_{t+c0+nc} into bank half k mod 2
+        ChainParams C;
+        std::memset(&C, 0, sizeof(C));
+        C.L = nc; C.flat = h->d_flat; C.M = h->d_m; C.V = h->d_v; C.netoff = h->d_netoff;
+        C.inv_tile = h->d_inv_tile; C.inv_small = h->d_inv_small;
+        C.Wp = h->d_Wp; C.Bp = h->d_Bp; C.smw = h->d_sm_w; C.smb = h->d_sm_bias;
+        if (h->kind == 1) {                         // the MFMA image bank and the flat bank
+            C.tbank_w = h->d_tbank_w + (size_t)half * MZ_MULTI_MAX * nw;
+            C.tbank_b = h->d_tbank_b + (size_t)half * MZ_MULTI_MAX * nb;
+            C.tws = nw; C.tbs = nb;
+            C.fbank = h->d_fbank + (size_t)half * MZ_MULTI_MAX * fbank_stride(h);
+            C.fstride = fbank_stride(h);
+        } else {                                    // the small-kernel image bank
+            C.bank_w = h->d_bank_w + (size_t)half * MZ_MULTI_MAX * h->sm_w_n;
+            C.bank_b = h->d_bank_b + (size_t)half * MZ_MULTI_MAX * h->sm_b_n;
+            C.bws = h->sm_w_n; C.bbs = h->sm_b_n;
+        }
+        C.theta = theta_dev ? theta_dev + (size_t)c0 * h->nflat : nullptr;
+        C.nflat = h->nflat; C.part = h->d_ml_part + (size_t)cr * 3 * MZ_L2_BLOCKS;
+        set_caps(C, cap, (int64_t)step0 + c0, nc);
+        for (int i = 0; i < nc; ++i) {              // adam_advance's products, step by step
+            C.bp1[i] = p1; C.bp2[i] = p2; C.eta[i] = eta[c0 + i];
+            p1 = p1 * 0.9; p2 = p2 * 0.999;
+        }
+        C.B = B; rs_at(C.q, Q, step0 + (uint32_t)c0, cr, S);    // this chunk's batches: steps step0 + c0 ..
+        C.s_obs = S.s_obs; C.s_k1 = S.s_k1; C.s_tp = S.s_tp;
+        const int nsb = chain_sample ? (nc * B + MZ_THREADS / 64 - 1) / (MZ_THREADS / 64) : 0;
+        const int nht = chain_helpers(h, C);
+        if (nht < 0) return -1;
+        hipLaunchKernelGGL(mz_learn_chain, dim3(nht + 3 * MZ_L2_BLOCKS + nsb), dim3(MZ_THREADS), 0, st, C);
+        MZ_TRY(h, hipGetLastError());
+        // 2. the sub-chunks: steps step0 + c0 + j0 ..
+        for (int j0 = 0; j0 < nc; j0 += Ls) {
+            const int n = std::min(Ls, nc - j0), ir = (c0 + j0) % R;
+            RpSampleParams Qk;
+            rs_at(Qk, Q, step0 + (uint32_t)(c0 + j0), ir, S);
+            if (body(c0, j0, n, ir, Qk, C)) return -1;
+        }
+    }
+    for (int i = 0; i < L; ++i) adam_advance(h);
+    h->ml_last_B = B; h->ml_last_L = L; h->ml_last_R = R;
+    return 0;
+}
+}  // extern "C++"
+
+// ResNet nets (ref_semantics, no PER): per sub-chunk of Ls steps, the downsampler over the Ls·B
+// observations (Atari), the unroll launch(es) with the steps on gridDim.z (the fused form: step-major
+// chain blocks, then the items; RUnrollParams.ms) and one loss launch of Ls·nlb blocks (Σθ² per step
+// from the chain launch)
 static int rlearner_multi(mz_handle* h, int32_t B, uint32_t step0, int32_t L, const double* eta, float* losses_dev,
                           float* theta_dev, hipStream_t st, float* out_last, const MultiCap* cap) {
     RpSampleParams Q;
     mz_batch b;
     if (rs_params(h, B, step0, st, &Q, &b, true)) return -1;
     if (ensure_batch(h, B) || ensure_multi(h, B, L)) return -1;
-    static const int ls_env = std::getenv("MZ_MULTI_LS") ? std::atoi(std::getenv("MZ_MULTI_LS")) : 0;
+    const int ls_env = multi_ls_env();
     const int Ls = std::min(L, ls_env > 0 ? std::min(MZ_MULTI_UNROLL, ls_env) : MZ_MULTI_UNROLL);
     const int K = h->conf.num_unroll_steps, KH = std::max(K, 1), A = h->A;
     const size_t K1 = (size_t)K + 1;
-    const size_t s_obs = (size_t)B * h->obs_feat, s_k1 = (size_t)B * K1, s_tp = (size_t)B * K1 * A;
-    const size_t nw = h->packed_w_n, nb = std::max<size_t>(h->packed_b_n, 1);
+    const MultiStrides S = {B, (size_t)B * h->obs_feat, (size_t)B * K1, (size_t)B * K1 * A};
+    const size_t nw = h->packed_w_n;
     Q.obs = h->d_ml_obs; Q.actions = h->d_ml_act; Q.tv = h->d_ml_tv; Q.tr = h->d_ml_tr; Q.tpol = h->d_ml_tp;
     Q.gscale = h->d_ml_gs; Q.index = h->d_ml_index;
-    // rlearner_grad's form for one step of B samples
     RUnrollParams U;
-    std::memset(&U, 0, sizeof(U));
-    U.B = B; U.K = K; U.A = A; U.H = h->H;
-    U.W = h->rconf.observation_shape[0]; U.P = h->plane; U.obs_feat = h->rin_feat; U.ng = h->rn_ng; U.bn_s = h->bn_s;
-    U.plans = h->d_rplan; U.plans_l = h->d_rplan_l; U.ng_l = h->rn_ng_l;
-    U.dyn_split = h->rn_dyn_split; U.otab = h->d_rtab;
-    U.rd_ep_off = (int)(h->rn_lds_l / 4); U.rd_trunk_nl = 1 + 2 * h->rhp.num_blocks;
-    U.rp_nv = 3 + h->rhp.depth_value;
-    U.fault = h->d_fault; U.poll_ticks = h->poll_ticks; U.dbg_skip = h->dbg_skip;
+    runroll_params(h, B, U);
     U.ms_wimg = nw; U.ms_flat = fbank_stride(h); U.ms_obs = (size_t)B * (h->ds ? h->rin_feat : h->obs_feat);
-    U.ms_k1 = s_k1; U.ms_tp = s_tp; U.ms_hs = (size_t)B * KH * h->H;
-    static const bool wide_env = std::getenv("MZ_RN_PRED_WIDE") != nullptr;
-    static const bool no_fuse = std::getenv("MZ_RN_NO_FUSE") != nullptr;
-    static const bool nb3 = std::getenv("MZ_RN_CHAIN_NB3") != nullptr;
-    const bool wide_p = wide_env || (B * KH + U.ng - 1) / U.ng >= h->n_cu;
-    const bool fused = h->rd_chain && h->rp_pred && !wide_p && !no_fuse && U.ng_l == 1 && K + 1 < 64 && !h->ds;
-    const bool nb1 = (U.P * U.ng_l + 15) / 16 == 1 || !nb3;
+    U.ms_k1 = S.s_k1; U.ms_tp = S.s_tp; U.ms_hs = (size_t)B * KH * h->H;
     const int gw = A > 16 ? 32 : 16;
     const int nlb = (B * (int)K1 + MZ_THREADS / gw - 1) / (MZ_THREADS / gw);
-    double p1 = h->bp1, p2 = h->bp2;
-    // chain launches of up to MZ_MULTI_MAX steps (bank half k mod 2), each followed by its steps' unroll
-    // launches of up to Ls steps
-    const int Lc = std::min(L, std::max(Ls, MZ_MULTI_MAX / Ls * Ls));
-    const int R = 2 * MZ_MULTI_MAX / Lc * Lc;       // the per-step scratch ring (ensure_multi)
-    for (int k = 0, c0 = 0; c0 < L; ++k, c0 += Lc) {
-        const int nc = std::min(Lc, L - c0), half = k & 1, cr = c0 % R;
-        ChainParams C;                              // 1. ADAM chain + the nc batches
-        std::memset(&C, 0, sizeof(C));
-        C.L = nc; C.flat = h->d_flat; C.M = h->d_m; C.V = h->d_v; C.netoff = h->d_netoff;
-        C.inv_tile = h->d_inv_tile; C.inv_small = h->d_inv_small;
-        C.Wp = h->d_Wp; C.Bp = h->d_Bp; C.smw = h->d_sm_w; C.smb = h->d_sm_bias;
-        C.tbank_w = h->d_tbank_w + (size_t)half * MZ_MULTI_MAX * nw;
-        C.tbank_b = h->d_tbank_b + (size_t)half * MZ_MULTI_MAX * nb;
-        C.tws = nw; C.tbs = nb;
-        C.fbank = h->d_fbank + (size_t)half * MZ_MULTI_MAX * fbank_stride(h);
-        C.fstride = fbank_stride(h);
-        C.theta = theta_dev ? theta_dev + (size_t)c0 * h->nflat : nullptr;
-        C.nflat = h->nflat; C.part = h->d_ml_part + (size_t)cr * 3 * MZ_L2_BLOCKS;
-        set_caps(C, cap, (int64_t)step0 + c0, nc);
-        for (int i = 0; i < nc; ++i) {
-            C.bp1[i] = p1; C.bp2[i] = p2; C.eta[i] = eta[c0 + i];
-            p1 = p1 * 0.9; p2 = p2 * 0.999;
+    auto body = [&](int c0, int j0, int n, int ir, const RpSampleParams& Qk, const ChainParams& C) -> int {
+        const int i0 = c0 + j0;
+        // representation input (Atari: the downsampler with step z's parameters), the unrolls
+        U.Wimg = C.tbank_w + (size_t)j0 * nw; U.flat = C.fbank + (size_t)j0 * fbank_stride(h);
+        U.obs = Qk.obs; U.actions = Qk.actions;
+        if (h->ds) {
+            float* y = h->d_ml_dsb + (size_t)ir * B * h->rin_feat;
+            if (ds_launch(h, Qk.obs, y, n * B, st, C.fbank + (size_t)j0 * fbank_stride(h), B)) return -1;
+            U.obs = y;
         }
-        RpSampleParams Qc = Q;
-        Qc.step = step0 + (uint32_t)c0;
-        Qc.obs += cr * s_obs; Qc.actions += cr * s_k1; Qc.tv += cr * s_k1; Qc.tr += cr * s_k1;
-        Qc.tpol += cr * s_tp; Qc.gscale += (size_t)cr * B; Qc.index += (size_t)cr * 2 * B;
-        C.B = B; C.q = Qc; C.s_obs = s_obs; C.s_k1 = s_k1; C.s_tp = s_tp;
-        const int nsb = (nc * B + MZ_THREADS / 64 - 1) / (MZ_THREADS / 64);
-        const int nht = chain_helpers(h, C);
-        if (nht < 0) return -1;
-        hipLaunchKernelGGL(mz_learn_chain, dim3(nht + 3 * MZ_L2_BLOCKS + nsb), dim3(MZ_THREADS), 0, st, C);
+        U.pv = h->d_ml_pv + ir * S.s_k1; U.pp = h->d_ml_pp + ir * S.s_tp; U.pr = h->d_ml_pr + ir * S.s_k1;
+        U.hs = h->d_ml_hs + (size_t)ir * U.ms_hs; U.ts = h->d_ml_ts + (size_t)ir * U.ms_hs;
+        if (runroll_launch(h, U, n, st, h->d_ml_prog + (size_t)ir * B, &h->ml_prog_epoch)) return -1;
+        // the loss terms and per-step folds (Σθ² from the chain launch)
+        LossMultiParams M;
+        std::memset(&M, 0, sizeof(M));
+        M.B = B; M.K = K; M.A = A; M.v_act = MZ_ACT_IDENTITY; M.r_act = MZ_ACT_IDENTITY; M.nlb = nlb; M.L = n;
+        M.s_k1 = S.s_k1; M.s_tp = S.s_tp; M.pv = U.pv; M.pp = U.pp; M.pr = U.pr;
+        M.tv = Qk.tv; M.tp = Qk.tpol; M.gs = Qk.gscale;
+        M.terms = h->d_ml_terms + 2 * ir * S.s_k1; M.part = h->d_ml_part + (size_t)ir * 3 * MZ_L2_BLOCKS;
+        M.counter = h->d_ml_cnt + (size_t)ir * MZ_MULTI_CNT_STRIDE;
+        M.out = losses_dev ? losses_dev + 8 * i0 : h->d_ml_out + 8 * ir;
+        M.out_last = i0 + n == L ? out_last : nullptr;
+        hipLaunchKernelGGL(gw == 32 ? mz_learner_loss_multi32 : mz_learner_loss_multi, dim3(nlb, n), dim3(MZ_THREADS),
+                           0, st, M);
         MZ_TRY(h, hipGetLastError());
-        for (int j0 = 0; j0 < nc; j0 += Ls) {
-            const int n = std::min(Ls, nc - j0), i0 = c0 + j0, ir = i0 % R;
-            RpSampleParams Qk = Q;                  // steps step0 + i0 ..
-            Qk.step = step0 + (uint32_t)i0;
-            Qk.obs += ir * s_obs; Qk.actions += ir * s_k1; Qk.tv += ir * s_k1; Qk.tr += ir * s_k1;
-            Qk.tpol += ir * s_tp; Qk.gscale += (size_t)ir * B; Qk.index += (size_t)ir * 2 * B;
-            // 2. representation input (Atari: the downsampler with step z's parameters), the unrolls
-            U.ms = n;
-            U.Wimg = C.tbank_w + (size_t)j0 * nw; U.flat = C.fbank + (size_t)j0 * fbank_stride(h);
-            U.obs = Qk.obs; U.actions = Qk.actions;
-            if (h->ds) {
-                float* y = h->d_ml_dsb + (size_t)ir * B * h->rin_feat;
-                if (ds_launch(h, Qk.obs, y, n * B, st, C.fbank + (size_t)j0 * fbank_stride(h), B)) return -1;
-                U.obs = y;
-            }
-            U.pv = h->d_ml_pv + ir * s_k1; U.pp = h->d_ml_pp + ir * s_tp; U.pr = h->d_ml_pr + ir * s_k1;
-            U.hs = h->d_ml_hs + (size_t)ir * U.ms_hs; U.ts = h->d_ml_ts + (size_t)ir * U.ms_hs;
-            void* args[] = {&U};
-            hipEvent_t e0 = nullptr, e1 = nullptr;     // mz_debug_enable flag 4: the unroll launch's duration
-            if (h->time_unroll) {
-                if (timing_events(h, &e0, &e1)) return -1;
-                MZ_TRY(h, hipEventRecord(e0, st));
-            }
-            if (fused) {
-                U.prog = h->d_ml_prog + (size_t)ir * B;
-                U.prog_base = (++h->ml_prog_epoch) * 64ull;
-                U.n_chain = B; U.fuse_sample = 0; U.n_l2 = 0;
-                const int nitems = B * KH * (K > 0 ? 3 : 2);
-                MZ_TRY(h, hipLaunchKernel(h->rd_nb == 3 ? (const void*)mz_runroll_fused_r3 : (const void*)mz_runroll_fused_r,
-                                          dim3(n * (B + nitems)), dim3(RD_THREADS), args,
-                                          std::max(rd_chain_lds(h), rp_pred_lds(h)), st));
-            } else {
-                if (h->rd_chain)
-                    MZ_TRY(h, hipLaunchKernel(h->rd_nb == 3 ? (const void*)mz_runroll_chain_r3
-                                                            : (const void*)mz_runroll_chain_r,
-                                              dim3((B + U.ng_l - 1) / U.ng_l, 1, n), dim3(RD_THREADS), args,
-                                              rd_chain_lds(h), st));
-                else
-                    MZ_TRY(h, hipLaunchKernel(nb1 ? (const void*)mz_runroll_chain1 : (const void*)mz_runroll_chain,
-                                              dim3((B + U.ng_l - 1) / U.ng_l, 1, n), dim3(RN_THREADS), args,
-                                              h->rn_lds_l, st));
-                if (wide_p)
-                    MZ_TRY(h, hipLaunchKernel((const void*)mz_runroll_pred,
-                                              dim3((B * KH + U.ng - 1) / U.ng, K > 0 ? 2 : 1, n), dim3(RN_THREADS), args,
-                                              runroll_lds(h), st));
-                else if (h->rp_pred)
-                    MZ_TRY(h, hipLaunchKernel((const void*)mz_runroll_pred_r,
-                                              dim3((B * KH + U.ng_l - 1) / U.ng_l, K > 0 ? 2 : 1, n), dim3(RD_THREADS),
-                                              args, rp_pred_lds(h), st));
-                else
-                    MZ_TRY(h, hipLaunchKernel(nb1 ? (const void*)mz_runroll_pred_n1 : (const void*)mz_runroll_pred_n,
-                                              dim3((B * KH + U.ng_l - 1) / U.ng_l, K > 0 ? 2 : 1, n), dim3(RN_THREADS),
-                                              args, h->rn_lds_l, st));
-            }
-            if (e1) MZ_TRY(h, hipEventRecord(e1, st));
-            // 3. the loss terms and per-step folds (Σθ² from the chain launch)
-            LossMultiParams M;
-            std::memset(&M, 0, sizeof(M));
-            M.B = B; M.K = K; M.A = A; M.v_act = MZ_ACT_IDENTITY; M.r_act = MZ_ACT_IDENTITY; M.nlb = nlb; M.L = n;
-            M.s_k1 = s_k1; M.s_tp = s_tp; M.pv = U.pv; M.pp = U.pp; M.pr = U.pr;
-            M.tv = Qk.tv; M.tp = Qk.tpol; M.gs = Qk.gscale;
-            M.terms = h->d_ml_terms + 2 * ir * s_k1; M.part = h->d_ml_part + (size_t)ir * 3 * MZ_L2_BLOCKS;
-            M.counter = h->d_ml_cnt + (size_t)ir * MZ_MULTI_CNT_STRIDE;
-            M.out = losses_dev ? losses_dev + 8 * i0 : h->d_ml_out + 8 * ir;
-            M.out_last = i0 + n == L ? out_last : nullptr;
-            hipLaunchKernelGGL(gw == 32 ? mz_learner_loss_multi32 : mz_learner_loss_multi, dim3(nlb, n), dim3(MZ_THREADS),
-                               0, st, M);
-            MZ_TRY(h, hipGetLastError());
-        }
-    }
-    const std::string chain = h->rd_chain ? (h->rd_nb == 3 ? "mz_runroll_chain_r3" : "mz_runroll_chain_r")
-                                          : nb1 ? "mz_runroll_chain1" : "mz_runroll_chain";
-    const std::string pred = wide_p ? "mz_runroll_pred" : h->rp_pred ? "mz_runroll_pred_r"
-                                                        : nb1 ? "mz_runroll_pred_n1" : "mz_runroll_pred_n";
-    h->last_lvariant = std::string("mz_learn_chain+") + (h->ds ? "mz_downsample_kernel+" : "") +
-                       (fused ? (h->rd_nb == 3 ? "mz_runroll_fused_r3" : "mz_runroll_fused_r") : chain + "+" + pred) +
+        return 0;
+    };
+    if (multi_drive(h, step0, L, Ls, eta, theta_dev, st, cap, Q, S, true, body)) return -1;
+    h->last_lvariant = std::string("mz_learn_chain+") + (h->ds ? "mz_downsample_kernel+" : "") + h->last_lvariant +
                        "+mz_learner_loss_multi";
-    for (int i = 0; i < L; ++i) adam_advance(h);
-    h->ml_last_B = B; h->ml_last_L = L; h->ml_last_R = R;
     return 0;
 }
 
@@ -4061,12 +3995,14 @@ static int learner_multi(mz_handle* h, int32_t B, uint32_t step0, int32_t L, con
         h->ml_last_L = 0;                           // (no multi-step read-outs: mz_debug_unroll_step refuses)
         return 0;
     }
+    // FC nets on the small kernel: per sub-chunk, one launch of the n unrolls (with their get_batch),
+    // loss terms and per-step folds, Ls steps keeping one workgroup per CU
     RpSampleParams Q;
     mz_batch b;
     if (rs_params(h, B, step0, st, &Q, &b, true)) return -1;   // (the shard; set 0 is not touched)
     if (ensure_batch(h, B) || ensure_multi(h, B, L)) return -1;
     const size_t K1 = (size_t)h->conf.num_unroll_steps + 1, A = (size_t)h->A;
-    const size_t s_obs = (size_t)B * h->obs_feat, s_k1 = (size_t)B * K1, s_tp = (size_t)B * K1 * A;
+    const MultiStrides S = {B, (size_t)B * h->obs_feat, (size_t)B * K1, (size_t)B * K1 * A};
     Q.obs = h->d_ml_obs; Q.actions = h->d_ml_act; Q.tv = h->d_ml_tv; Q.tr = h->d_ml_tr; Q.tpol = h->d_ml_tp;
     Q.gscale = h->d_ml_gs; Q.index = h->d_ml_index;
     static const bool chain_sample = std::getenv("MZ_MULTI_CHAIN_SAMPLE") != nullptr;   // A/B
@@ -4074,82 +4010,39 @@ static int learner_multi(mz_handle* h, int32_t B, uint32_t step0, int32_t L, con
     if (small_unroll_params(h, &b, ti, nullptr, &U)) return -1;
     const int T = ti == 2 ? 4 : ti + 1, nU = (B + T - 1) / T;
     static const bool no_xcd = std::getenv("MZ_MULTI_NO_XCD") != nullptr;
-    double p1 = h->bp1, p2 = h->bp2;
-    // chain launches of up to MZ_MULTI_MAX steps (bank half k mod 2), each followed by its steps' unroll
-    // launches of Ls steps (one workgroup per CU)
-    const int Lc = std::min(L, std::max(Ls, MZ_MULTI_MAX / Ls * Ls));
-    const int R = 2 * MZ_MULTI_MAX / Lc * Lc;       // the per-step scratch ring (ensure_multi)
-    for (int k = 0, c0 = 0; c0 < L; ++k, c0 += Lc) {
-        const int nc = std::min(Lc, L - c0), half = k & 1, cr = c0 % R;
-        // 1. the ADAM chain θ_{t+c0} .. θ_{t+c0+nc} into bank half k mod 2
-        ChainParams C;
-        std::memset(&C, 0, sizeof(C));
-        C.L = nc; C.flat = h->d_flat; C.M = h->d_m; C.V = h->d_v; C.netoff = h->d_netoff;
-        C.inv_tile = h->d_inv_tile; C.inv_small = h->d_inv_small;
-        C.Wp = h->d_Wp; C.Bp = h->d_Bp; C.smw = h->d_sm_w; C.smb = h->d_sm_bias;
-        C.bank_w = h->d_bank_w + (size_t)half * MZ_MULTI_MAX * h->sm_w_n;
-        C.bank_b = h->d_bank_b + (size_t)half * MZ_MULTI_MAX * h->sm_b_n;
-        C.bws = h->sm_w_n; C.bbs = h->sm_b_n;
-        C.theta = theta_dev ? theta_dev + (size_t)c0 * h->nflat : nullptr;
-        C.nflat = h->nflat; C.part = h->d_ml_part + (size_t)cr * 3 * MZ_L2_BLOCKS;
-        set_caps(C, cap, (int64_t)step0 + c0, nc);
-        for (int i = 0; i < nc; ++i) {              // adam_advance's products, step by step
-            C.bp1[i] = p1; C.bp2[i] = p2; C.eta[i] = eta[c0 + i];
-            p1 = p1 * 0.9; p2 = p2 * 0.999;
+    auto body = [&](int c0, int j0, int n, int ir, const RpSampleParams& Qk, const ChainParams& C) -> int {
+        const int i0 = c0 + j0;
+        LearnMultiParams M;
+        std::memset(&M, 0, sizeof(M));
+        M.L = n; M.nU = nU;
+        M.xcd = !no_xcd && n > 1;
+        M.bank_w = C.bank_w + (size_t)j0 * h->sm_w_n; M.bank_b = C.bank_b + (size_t)j0 * h->sm_b_n;
+        M.bws = h->sm_w_n; M.bbs = h->sm_b_n;
+        M.s_obs = S.s_obs; M.s_k1 = S.s_k1; M.s_tp = S.s_tp;
+        M.obs = Qk.obs; M.act = Qk.actions; M.tv = Qk.tv; M.tp = Qk.tpol; M.gs = Qk.gscale;
+        M.pv = h->d_ml_pv + ir * S.s_k1; M.pp = h->d_ml_pp + ir * S.s_tp; M.pr = h->d_ml_pr + ir * S.s_k1;
+        M.terms = h->d_ml_terms + 2 * ir * S.s_k1;
+        M.part = h->d_ml_part + (size_t)ir * 3 * MZ_L2_BLOCKS;
+        M.counter = h->d_ml_cnt + (size_t)ir * MZ_MULTI_CNT_STRIDE;
+        M.out = losses_dev ? losses_dev + 8 * i0 : h->d_ml_out + 8 * ir;
+        M.out_last = i0 + n == L ? out_last : nullptr;
+        M.sample = chain_sample ? 0 : 1;
+        M.q = Qk;
+        const int grid = M.xcd ? 8 * ((n + 7) / 8) * nU : n * nU;
+        void* args[] = {&U, &M};
+        hipEvent_t e0 = nullptr, e1 = nullptr; // mz_debug_enable flag 4: the unroll launch's duration
+        if (h->time_unroll) {
+            if (timing_events(h, &e0, &e1)) return -1;
+            MZ_TRY(h, hipEventRecord(e0, st));
         }
-        RpSampleParams Qc = Q;                      // this chunk's batches: steps step0 + c0 ..
-        Qc.step = step0 + (uint32_t)c0;
-        Qc.obs += cr * s_obs; Qc.actions += cr * s_k1; Qc.tv += cr * s_k1; Qc.tr += cr * s_k1;
-        Qc.tpol += cr * s_tp; Qc.gscale += (size_t)cr * B; Qc.index += (size_t)cr * 2 * B;
-        C.B = B; C.q = Qc; C.s_obs = s_obs; C.s_k1 = s_k1; C.s_tp = s_tp;
-        const int nsb = chain_sample ? (nc * B + MZ_THREADS / 64 - 1) / (MZ_THREADS / 64) : 0;
-        const int nht = chain_helpers(h, C);
-        if (nht < 0) return -1;
-        hipLaunchKernelGGL(mz_learn_chain, dim3(nht + 3 * MZ_L2_BLOCKS + nsb), dim3(MZ_THREADS), 0, st, C);
-        MZ_TRY(h, hipGetLastError());
-        for (int j0 = 0; j0 < nc; j0 += Ls) {
-            const int n = std::min(Ls, nc - j0), i0 = c0 + j0, ir = i0 % R;
-            RpSampleParams Qk = Q;                  // steps step0 + i0 ..
-            Qk.step = step0 + (uint32_t)i0;
-            Qk.obs += ir * s_obs; Qk.actions += ir * s_k1; Qk.tv += ir * s_k1; Qk.tr += ir * s_k1;
-            Qk.tpol += ir * s_tp; Qk.gscale += (size_t)ir * B; Qk.index += (size_t)ir * 2 * B;
-            // 2. the n unrolls (with their get_batch), loss terms and per-step folds
-            LearnMultiParams M;
-            std::memset(&M, 0, sizeof(M));
-            M.L = n; M.nU = nU;
-            M.xcd = !no_xcd && n > 1;
-            M.bank_w = C.bank_w + (size_t)j0 * h->sm_w_n; M.bank_b = C.bank_b + (size_t)j0 * h->sm_b_n;
-            M.bws = h->sm_w_n; M.bbs = h->sm_b_n;
-            M.s_obs = s_obs; M.s_k1 = s_k1; M.s_tp = s_tp;
-            M.obs = Qk.obs; M.act = Qk.actions; M.tv = Qk.tv; M.tp = Qk.tpol; M.gs = Qk.gscale;
-            M.pv = h->d_ml_pv + ir * s_k1; M.pp = h->d_ml_pp + ir * s_tp; M.pr = h->d_ml_pr + ir * s_k1;
-            M.terms = h->d_ml_terms + 2 * ir * s_k1;
-            M.part = h->d_ml_part + (size_t)ir * 3 * MZ_L2_BLOCKS;
-            M.counter = h->d_ml_cnt + (size_t)ir * MZ_MULTI_CNT_STRIDE;
-            M.out = losses_dev ? losses_dev + 8 * i0 : h->d_ml_out + 8 * ir;
-            M.out_last = i0 + n == L ? out_last : nullptr;
-            M.sample = chain_sample ? 0 : 1;
-            M.q = Qk;
-            const int grid = M.xcd ? 8 * ((n + 7) / 8) * nU : n * nU;
-            void* args[] = {&U, &M};
-            hipEvent_t e0 = nullptr, e1 = nullptr; // mz_debug_enable flag 4: the unroll launch's duration
-            if (h->time_unroll) {
-                if (timing_events(h, &e0, &e1)) return -1;
-                MZ_TRY(h, hipEventRecord(e0, st));
-            }
-            const void* kbn[3] = {(const void*)mz_learn_multi1_bn, (const void*)mz_learn_multi2_bn,
-                                  (const void*)mz_learn_multi4_bn};
-            const void* kpl[3] = {(const void*)mz_learn_multi1, (const void*)mz_learn_multi2,
-                                  (const void*)mz_learn_multi4};
-            MZ_TRY(h, hipLaunchKernel(h->sm_bn ? kbn[ti] : kpl[ti],
-                                      dim3(grid), dim3(SM_THREADS), args, unroll_small_lds(h, ti), st));
-            if (e1) MZ_TRY(h, hipEventRecord(e1, st));
-        }
-    }
+        MZ_TRY(h, hipLaunchKernel(small_kernel(h, SMK_MULTI, ti), dim3(grid), dim3(SM_THREADS), args,
+                                  unroll_small_lds(h, ti), st));
+        if (e1) MZ_TRY(h, hipEventRecord(e1, st));
+        return 0;
+    };
+    if (multi_drive(h, step0, L, Ls, eta, theta_dev, st, cap, Q, S, chain_sample, body)) return -1;
     h->last_lvariant = ti == 0 ? "mz_learn_chain+mz_learn_multi1"
                      : ti == 1 ? "mz_learn_chain+mz_learn_multi2" : "mz_learn_chain+mz_learn_multi4";
-    for (int i = 0; i < L; ++i) adam_advance(h);
-    h->ml_last_B = B; h->ml_last_L = L; h->ml_last_R = R;
     return 0;
 }
 
@@ -4159,7 +4052,7 @@ int mz_learner_train_multi_dev(mz_handle* h, int32_t B, uint32_t step0, int32_t 
     if (L < 1 || L > MZ_MULTI_LMAX) return fail(h, "L must be in 1 .. 256");
     if (!eta) return fail(h, "eta: one learning rate per step");
     if (B < 1) return fail(h, "batch_size must be >= 1");
-    return learner_multi(h, B, step0, L, eta, losses_dev, theta_dev, stream ? (hipStream_t)stream : h->stream);
+    return learner_multi(h, B, step0, L, eta, losses_dev, theta_dev, stream_of(h, stream));
 }
 
 int mz_debug_unroll_step(mz_handle* h, int i, int B, float* values, float* policies, float* rewards) {
@@ -4224,7 +4117,7 @@ int mz_replay_reanalyse(mz_handle* h, int32_t first, int32_t count, void* stream
     if (first < 0) return fail(h, "reanalyse: first must be >= 0");
     if ((long long)h->sp_cap * h->sp_T > 0x7fffffffLL) return fail(h, "reanalyse: shard too large");
     MZ_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     // how many games are held is only known on the device: the grid covers the
     // selection clipped to the capacity, the kernels clip it to the held range
     const int gmax = count < 0 ? h->sp_cap - first : std::min<int>(count, h->sp_cap - first);
@@ -4292,7 +4185,7 @@ int mz_replay_clear_reanalysed(mz_handle* h, void* stream) {
     if (!h) return -2;
     if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
     MZ_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     ++h->pf_epoch;
     hipLaunchKernelGGL(mz_reanalyse_clear, dim3((h->sp_cap + 255) / 256), dim3(256), 0, st, h->sp_ring.rean, h->sp_cap);
     MZ_TRY(h, hipGetLastError());
@@ -4361,7 +4254,7 @@ int mz_replay_reanalyse_search(mz_handle* h, int32_t first, int32_t count, int e
     if (first < 0) return fail(h, "reanalyse: first must be >= 0");
     if ((long long)h->sp_cap * h->sp_T > 0x7fffffffLL) return fail(h, "reanalyse: shard too large");
     MZ_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     // as mz_replay_reanalyse: the rows cover the selection clipped to the capacity, the kernels
     // clip it to the held range
     const int gmax = count < 0 ? h->sp_cap - first : std::min<int>(count, h->sp_cap - first);
@@ -4429,7 +4322,7 @@ int mz_replay_reanalyse_next(mz_handle* h, int mode, int exploration, uint32_t r
     if (!h) return -2;
     if (rean_next_check(h, mode)) return -1;
     MZ_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     const bool search = mode == MZ_REAN_BY_SEARCH;
     const int R = search ? h->max_games : kReanChunk;
     ++h->pf_epoch;                                  // a batch drawn ahead has the old targets
@@ -4475,7 +4368,7 @@ int mz_replay_reanalyse_seek(mz_handle* h, int64_t game_number, void* stream) {
     if (!h) return -2;
     if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
     MZ_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     hipLaunchKernelGGL(mz_reanalyse_seek, dim3(1), dim3(64), 0, st, h->d_sp_counters, (long long)game_number);
     MZ_TRY(h, hipGetLastError());
     return 0;
@@ -4770,7 +4663,7 @@ int mz_train_move(mz_handle* h, uint32_t move, uint32_t game_offset, int64_t* nf
     if (!h->tr_B) return fail(h, "mz_train_init first");
     MZ_TRY(h, hipSetDevice(h->device));
     int64_t n = 0;
-    if (train_move(h, move, game_offset, &n, stream ? (hipStream_t)stream : h->stream)) return -1;
+    if (train_move(h, move, game_offset, &n, stream_of(h, stream))) return -1;
     if (nfin) *nfin = n;
     return 0;
 }
@@ -4781,7 +4674,7 @@ int mz_train_learn(mz_handle* h, int64_t steps, float* losses_dev, int64_t* stat
     if (steps < 0) return fail(h, "steps must be >= 0");
     MZ_TRY(h, hipSetDevice(h->device));
     int64_t done = 0;
-    if (train_learn(h, steps, losses_dev, stream ? (hipStream_t)stream : h->stream, &done)) return -1;
+    if (train_learn(h, steps, losses_dev, stream_of(h, stream), &done)) return -1;
     if (state_out) {
         state_out[0] = h->tr_t; state_out[1] = h->tr_games; state_out[2] = h->tr_refresh; state_out[3] = done;
     }
@@ -4794,7 +4687,7 @@ int mz_train_run(mz_handle* h, int32_t moves, uint32_t move0, uint32_t game_offs
     if (!h->tr_B) return fail(h, "mz_train_init first");
     if (moves < 0) return fail(h, "moves must be >= 0");
     MZ_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     int64_t steps = 0;
     for (int32_t mv = 0; mv < moves; ++mv) {
         int64_t nfin = 0, done = 0;

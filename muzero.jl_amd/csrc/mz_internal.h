@@ -164,3 +164,27 @@ struct LgAdam {
 };
 
 __host__ __device__ inline int mz_round16(int x) { return (x + 15) & ~15; }
+
+// ---- kernel prototypes (mz_search.hip, mz_nets.hip): the one declaration the
+// launching host files and the defining file both see
+extern "C" __global__ void mz_search_kernel_lds(SearchParams P);
+extern "C" __global__ void mz_search_kernel_hbm(SearchParams P);
+extern "C" __global__ void mz_search_kernel_lds_res(SearchParams P);
+extern "C" __global__ void mz_search_kernel_hbm_res(SearchParams P);
+extern "C" __global__ void mz_unroll_kernel(UnrollParams P);
+extern "C" __global__ void mz_forward_kernel(const int* plan, const float* Wp, const float* Bp, int total_lds,
+                                             int in_off, int in_feat, const float* x, int n, int out0_off, int o0,
+                                             float* out0, int out1_off, int o1, float* out1, int sm1, int act0,
+                                             int act1);
+extern "C" __global__ void mz_learner_grad_kernel(int B, int K, int A, int v_act, int r_act, float* pv, float* pp,
+                                                  float* pr, const float* tv, const float* tp, const float* gscale,
+                                                  float* terms, float* flat, const size_t* netoff, float* G,
+                                                  double* part, unsigned* counter, float* out, const float* wts, LgAdam ad);
+extern "C" __global__ void mz_learner_grad_kernel32(int B, int K, int A, int v_act, int r_act, float* pv, float* pp,
+                                                    float* pr, const float* tv, const float* tp, const float* gscale,
+                                                    float* terms, float* flat, const size_t* netoff, float* G,
+                                                    double* part, unsigned* counter, float* out, const float* wts, LgAdam ad);
+extern "C" __global__ void mz_adam_kernel(float* P, float* M, float* V, const float* G, float gscale, size_t n,
+                                          double bp1, double bp2, double eta, float* Wp, float* Bp,
+                                          const int* inv_tile, float* smw, float* smb, const int* inv_small);
+extern "C" __global__ void mz_repack_kernel(const float* flat, const int* src, float* packed, size_t n);

@@ -320,3 +320,28 @@ struct DsDwParams {
     float* out;                           // Flux-order data term of the gradient
     double* sq;                           // [n_job]: Σθ² of each job's parameters
 };
+
+// ---- kernel prototypes (mz_resnet.hip, mz_downsample.hip)
+extern "C" __global__ void mz_rnet_forward_kernel(RNetParams Q);
+extern "C" __global__ void mz_rsearch_root(RSearchParams P);
+extern "C" __global__ void mz_rsearch_root32(RSearchParams P);
+extern "C" __global__ void mz_rsearch_tree(RSearchParams P);
+extern "C" __global__ void mz_rsearch_tree32(RSearchParams P);
+extern "C" __global__ void mz_rsearch_tree_lds(RSearchParams P);
+extern "C" __global__ void mz_rsearch_tree_lds32(RSearchParams P);
+extern "C" __global__ void mz_rsearch_nets(RSearchParams P);
+extern "C" __global__ void mz_runroll_kernel(RUnrollParams U);
+extern "C" __global__ void mz_runroll_chain(RUnrollParams U);
+extern "C" __global__ void mz_runroll_chain1(RUnrollParams U);
+extern "C" __global__ void mz_runroll_chain_r(RUnrollParams U);
+extern "C" __global__ void mz_runroll_chain_r3(RUnrollParams U);
+extern "C" __global__ void mz_runroll_pred(RUnrollParams U);
+extern "C" __global__ void mz_runroll_pred_n(RUnrollParams U);
+extern "C" __global__ void mz_runroll_pred_n1(RUnrollParams U);
+extern "C" __global__ void mz_runroll_pred_r(RUnrollParams U);
+extern "C" __global__ void mz_runroll_fused_r(RUnrollParams U);
+extern "C" __global__ void mz_runroll_fused_r3(RUnrollParams U);
+extern "C" __global__ void mz_downsample_kernel(DsParams Q);
+extern "C" __global__ void mz_dsbp_fwd(DsBpParams Q);
+extern "C" __global__ void mz_dsbp_bwd(DsBpParams Q);
+extern "C" __global__ void mz_dsbp_dw(DsDwParams Q);

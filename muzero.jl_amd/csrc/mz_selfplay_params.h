@@ -14,6 +14,7 @@
 // finished games with the same per-game layout; game number n (1-based, the
 // Dict key of save_game) lives in ring slot (n - 1) mod cap.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 struct SpHist {                 // a set of game records: [n][T] ...
@@ -122,3 +123,26 @@ struct RpSampleParams {
     const long long* per_total; // total_samples of the held games
     float* weights;             // [B]
 };
+
+// ---- kernel prototypes (mz_selfplay.hip, mz_reanalyse.hip)
+extern "C" __global__ void mz_sp_prepare(SpParams S);
+extern "C" __global__ void mz_sp_commit(SpParams S);
+extern "C" __global__ void mz_sp_order(SpParams S);
+extern "C" __global__ void mz_sp_store(SpParams S);
+extern "C" __global__ void mz_sp_reset(SpParams S);
+extern "C" __global__ void mz_rp_sample(RpSampleParams Q);
+extern "C" __global__ void mz_rp_per_init(SpHist ring, int slot, int len, int Tmax, int td, const float* disc_pow,
+                                          int alpha);
+extern "C" __global__ void mz_rp_per_prep(SpHist ring, const long long* counters, int cap, float* cum, float* prob,
+                                          long long* total);
+extern "C" __global__ void mz_rp_per_norm(float* w, int B);
+extern "C" __global__ void mz_rp_per_update(SpHist ring, const long long* counters, int cap, int Tmax, int B, int K,
+                                            int alpha, const int32_t* index, const float* pv, const float* tv);
+extern "C" __global__ void mz_reanalyse_fc(ReanParams Q);
+extern "C" __global__ void mz_reanalyse_gather(ReanParams Q);
+extern "C" __global__ void mz_reanalyse_scatter(ReanParams Q);
+extern "C" __global__ void mz_reanalyse_clear(int32_t* rean, int cap);
+extern "C" __global__ void mz_reanalyse_sgather(ReanParams Q);
+extern "C" __global__ void mz_reanalyse_sscatter(ReanParams Q);
+extern "C" __global__ void mz_reanalyse_pack(ReanParams Q, int32_t* rows);
+extern "C" __global__ void mz_reanalyse_seek(long long* counters, long long game_number);

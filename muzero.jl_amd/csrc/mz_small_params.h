@@ -204,3 +204,28 @@ struct LossMultiParams {
 #define LEARN_L2_GROUPS 48
 #define LEARN_L2_PASSES ((3 * MZ_L2_BLOCKS + LEARN_L2_GROUPS * SM_SLOTS - 1) / (LEARN_L2_GROUPS * SM_SLOTS))
 
+// ---- kernel prototypes (mz_small.hip; mz_learner_loss_multi*: mz_nets.hip)
+extern "C" __global__ void mz_search_small1(SmallParams P);
+extern "C" __global__ void mz_search_small2(SmallParams P);
+extern "C" __global__ void mz_search_small4(SmallParams P);
+extern "C" __global__ void mz_search_small1_bn(SmallParams P);
+extern "C" __global__ void mz_search_small2_bn(SmallParams P);
+extern "C" __global__ void mz_search_small4_bn(SmallParams P);
+extern "C" __global__ void mz_unroll_small1(SmallUnrollParams P);
+extern "C" __global__ void mz_unroll_small2(SmallUnrollParams P);
+extern "C" __global__ void mz_unroll_small1_bn(SmallUnrollParams P);
+extern "C" __global__ void mz_unroll_small2_bn(SmallUnrollParams P);
+extern "C" __global__ void mz_learn_small1(SmallUnrollParams P, LearnParams L);
+extern "C" __global__ void mz_learn_small2(SmallUnrollParams P, LearnParams L);
+extern "C" __global__ void mz_learn_small1_bn(SmallUnrollParams P, LearnParams L);
+extern "C" __global__ void mz_learn_small2_bn(SmallUnrollParams P, LearnParams L);
+extern "C" __global__ void mz_learn_chain(ChainParams C);
+extern "C" __global__ void mz_learn_multi1(SmallUnrollParams P, LearnMultiParams M);
+extern "C" __global__ void mz_learn_multi2(SmallUnrollParams P, LearnMultiParams M);
+extern "C" __global__ void mz_learn_multi4(SmallUnrollParams P, LearnMultiParams M);
+extern "C" __global__ void mz_learn_multi1_bn(SmallUnrollParams P, LearnMultiParams M);
+extern "C" __global__ void mz_learn_multi2_bn(SmallUnrollParams P, LearnMultiParams M);
+extern "C" __global__ void mz_learn_multi4_bn(SmallUnrollParams P, LearnMultiParams M);
+extern "C" __global__ void mz_learner_loss_multi(LossMultiParams M);
+extern "C" __global__ void mz_learner_loss_multi32(LossMultiParams M);
+

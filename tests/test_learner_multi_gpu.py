@@ -4,8 +4,10 @@ and with PER off step s's batch is keyed by s) against the sequential learner,
 bit for bit at every step of the chunk: the six losses, the unroll read-outs
 and all three nets' θ after the step —
 * against L mz_learner_train_dev calls on an engine holding the same replay
-  shard (FC TicTacToe / Connect4, FC + BatchNorm, chunks of 1..50 steps —
-  several sub-chunks with alternating bank halves — T = 1 and T = 2 samples
+  shard (FC TicTacToe / Connect4, FC + BatchNorm, chunks of 1..70 steps —
+  several sub-chunks with alternating bank halves, at 70 steps three chain
+  launches: the 64-step scratch ring wraps and bank half 0 is reused — T = 1
+  and T = 2 samples
   per workgroup, single steps before and after the chunk; the ResNet nets of
   TicTacToe (configs[2], the fused unroll launch), Connect4 and the Atari-like
   env (downsampler, split unroll launches) with the steps on gridDim.z);
@@ -61,7 +63,7 @@ def _theta(e):
 @pytest.mark.parametrize("kind,B,L", [("ttt", 32, 8), ("ttt", 32, 16), ("ttt", 32, 1), ("ttt", 40, 5),
                                       ("c4", 24, 10), ("ttt-bn", 32, 6), ("ttt", 32, 37), ("ttt", 40, 50),
                                       ("ttt-rn", 32, 8), ("ttt-rn", 32, 21), ("ttt-rn", 7, 3), ("c4-rn", 16, 6),
-                                      ("atari", 8, 5)])
+                                      ("atari", 8, 5), ("ttt", 32, 70), ("ttt-rn", 7, 70)])
 def test_multi_matches_sequential_steps(kind, B, L):
     import torch
     from muzero_jl_amd.config import cos_schedule
