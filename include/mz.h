@@ -330,10 +330,37 @@ int mz_selfplay_move(mz_handle* h, uint32_t rng_step, uint32_t game_offset, floa
  * "human" branch); MZ_OPP_SELF: MuZero plays both sides.  Pass
  * temperature 0 to mz_selfplay_move for competitive play.  MZ_SP_TRAIN
  * (default): self_play! (:384-419).  Applies to the following moves; the
- * games in progress continue.                                              */
+ * games in progress continue.
+ * MZ_OPP_EXPERT (board envs only): on the same turns, from the same stream,
+ * the opponent is a rules search on the device, one extra launch per move
+ * and no network.  With p to move, score(s, a, d) of a legal action a is 0 /
+ * +d / -d when a ends the game in a draw / a win of p / a win of the other
+ * player (the env's own finish test and winner, Q14 included), else
+ * -V(s', d - 1); V(s, 0) = 0 and V(s, d) = max over the legal a of
+ * score(s, a, d), exhaustive to depth D = mz_expert_depth.  The expert plays
+ * the k-th (ascending) of the actions with the maximal score(s, a, D),
+ * k = mz_rng_below(draw, their count).  The reference's Config.opponent
+ * defaults to "expert" and its expert_agent() is a stub
+ * (games/AbstractGame.jl:91-93): this is the opponent that default asks for. */
 enum { MZ_SP_TRAIN = 0, MZ_SP_EVAL = 1 };
-enum { MZ_OPP_SELF = 0, MZ_OPP_RANDOM = 1 };
+enum { MZ_OPP_SELF = 0, MZ_OPP_RANDOM = 1, MZ_OPP_EXPERT = 2 };
 int mz_selfplay_mode(mz_handle* h, int mode, int opponent, int muzero_player);
+
+/* Depth D of the expert opponent, 1..9; 0 (default) = the env's default:
+ * 9 for TicTacToe (perfect play under the env's rules), 4 for Connect4
+ * (1 takes an immediate win, 2 also blocks one).  A handle setting like
+ * mz_selfplay_mode's: mz_selfplay_init and mz_snapshot_load keep it.        */
+int mz_expert_depth(mz_handle* h, int depth);
+
+/* The expert's scores of G >= 1 given positions, by the kernel evaluation
+ * play runs: boards [G][W*H*3] 0/1 bytes (planes [p1, p2, empty]), players
+ * [G] (1 or 2, the player to move), depth 1..9 -> scores [G][A]
+ * score(s, a, depth), -128 for an illegal action.  Host buffers;
+ * synchronises; needs no mz_selfplay_init.  env_kind must fit the conf as
+ * for mz_selfplay_init.  The positions are taken as not finished.  Refused:
+ * a cell set in no plane or in more than one, a player outside 1..2.        */
+int mz_expert_eval(mz_handle* h, int env_kind, int G, const uint8_t* boards, const int32_t* players, int depth,
+                   int32_t* scores);
 
 /* Evaluation tally since mz_selfplay_init: {games finished, MuZero wins,
  * opponent wins, draws}; the winner is read from the last move's reward
@@ -647,7 +674,8 @@ int mz_checkpoint_load(mz_handle* h, const char* path, int64_t* training_step);
  * Handle settings are NOT state: mz_train_set_reanalyse, mz_selfplay_mode,
  * mz_train_set_networks_path, mz_learner_set_mode and mz_debug_enable are
  * written into the metadata for information, and the loading host applies its
- * own (its mz_selfplay_mode survives the load).  At world > 1 each rank saves
+ * own (its mz_selfplay_mode and mz_expert_depth survive the load; the depth
+ * is not written to the file).  At world > 1 each rank saves
  * and loads its own file; the host orders the calls.                          */
 int mz_snapshot_save(mz_handle* h, const char* path, int64_t training_step);
 int mz_snapshot_load(mz_handle* h, const char* path, int64_t* training_step);

@@ -41,7 +41,7 @@ end
 const NET_REPR, NET_PRED, NET_DYN = Cint(0), Cint(1), Cint(2)
 const ACT_IDENTITY, ACT_RELU, ACT_TANH = Int32(0), Int32(1), Int32(2)
 const ENV_TICTACTOE, ENV_CONNECT4, ENV_ATARI = Cint(0), Cint(1), Cint(2)   # ENV_ATARI: the synthetic frame-stacked env of configs[4]
-const SP_TRAIN, SP_EVAL, OPP_SELF, OPP_RANDOM = Cint(0), Cint(1), Cint(0), Cint(1)
+const SP_TRAIN, SP_EVAL, OPP_SELF, OPP_RANDOM, OPP_EXPERT = Cint(0), Cint(1), Cint(0), Cint(1), Cint(2)
 const LEARN_REF_SEMANTICS, LEARN_CORRECTED = Cint(0), Cint(1)
 const TRAIN_LEARNER, TRAIN_ACTOR, TRAIN_QUEUED = Cint(0), Cint(1), Cint(2)
 const REAN_OFF, REAN_BY_VALUE, REAN_BY_SEARCH = Cint(0), Cint(1), Cint(2)
@@ -171,6 +171,17 @@ selfplay_move!(e::Engine, step; offset=0, temperature=1f0) =
                    e.h, step, offset, temperature, C_NULL))
 selfplay_mode!(e::Engine, mode::Cint; opponent=OPP_SELF, mzp=1) =
     check(e, ccall((:mz_selfplay_mode, libmz), Cint, (Ptr{Cvoid}, Cint, Cint, Cint), e.h, mode, opponent, mzp))
+# OPP_EXPERT (Config.opponent = "expert"): the rules search on the device; depth 1..9, 0 = the env's default
+expert_depth!(e::Engine, depth=0) =
+    check(e, ccall((:mz_expert_depth, libmz), Cint, (Ptr{Cvoid}, Cint), e.h, depth))
+"""expert_eval(e, env, boards (W*H*3, G) UInt8 planes [p1, p2, empty], players (G), depth) — the expert's
+scores (A, G), -128 for an illegal action: what would the expert play here."""
+function expert_eval(e::Engine, env::Cint, boards::Matrix{UInt8}, players::Vector{Int32}, depth::Integer, A::Integer)
+    scores = Matrix{Int32}(undef, A, size(boards, 2))
+    check(e, ccall((:mz_expert_eval, libmz), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{UInt8}, Ptr{Int32}, Cint, Ptr{Int32}),
+                   e.h, env, size(boards, 2), boards, players, depth, scores))
+    scores
+end
 function eval_results(e::Engine)               # competitive_play!: (games, MuZero wins, opponent wins, draws)
     r = zeros(Int64, 4)
     check(e, ccall((:mz_eval_results, libmz), Cint, (Ptr{Cvoid}, Ptr{Int64}), e.h, r))

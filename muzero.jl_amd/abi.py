@@ -20,7 +20,7 @@ ENV_TICTACTOE, ENV_CONNECT4, ENV_ATARI = 0, 1, 2
 SP_TRAIN, SP_EVAL = 0, 1
 TRAIN_LEARNER, TRAIN_ACTOR, TRAIN_QUEUED = 0, 1, 2
 LEARN_REF_SEMANTICS, LEARN_CORRECTED = 0, 1
-OPP_SELF, OPP_RANDOM = 0, 1
+OPP_SELF, OPP_RANDOM, OPP_EXPERT = 0, 1, 2
 REAN_OFF, REAN_BY_VALUE, REAN_BY_SEARCH = 0, 1, 2
 
 _lib = None
@@ -71,6 +71,8 @@ SIGNATURES = {
     "mz_dp_allreduce": (ctypes.c_int, [_VP, _VP, _VP]),
     "mz_learner_train_dp": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_uint32, ctypes.c_double, _VP, _VP]),
     "mz_selfplay_mode": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "mz_expert_depth": (ctypes.c_int, [_VP, ctypes.c_int]),
+    "mz_expert_eval": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP, ctypes.c_int, _VP]),
     "mz_eval_results": (ctypes.c_int, [_VP, _VP]),
     "mz_replay_counts": (ctypes.c_int, [_VP, _VP, _VP]),
     "mz_replay_save_game": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
@@ -409,6 +411,24 @@ class Engine:
     def selfplay_mode(self, mode, opponent=OPP_SELF, muzero_player=1):
         """SP_TRAIN (self_play!) or SP_EVAL (competitive_play!: games tallied, not saved)."""
         self._check(self.lib.mz_selfplay_mode(self.h, mode, opponent, muzero_player), "mz_selfplay_mode")
+
+    def expert_depth(self, depth=0):
+        """Depth of the OPP_EXPERT rules search, 1..9 (0: the env's default, TicTacToe 9, Connect4 4)."""
+        self._check(self.lib.mz_expert_depth(self.h, depth), "mz_expert_depth")
+
+    def expert_eval(self, env_kind, boards, players, depth):
+        """The expert's score(s, a, depth) of the positions boards (G, W*H*3) ([p1, p2, empty] planes)
+        with players (G,) to move: int32 (G, A), -128 for an illegal action."""
+        b = np.ascontiguousarray(boards, np.uint8)
+        b = b.reshape(1, -1) if b.ndim == 1 else b
+        p = np.ascontiguousarray(players, np.int32).reshape(-1)
+        want = {ENV_TICTACTOE: 27, ENV_CONNECT4: 126}.get(env_kind)     # any other env: the library refuses it
+        if want is not None and (b.shape[1] != want or p.size != b.shape[0]):
+            raise MzError(f"mz_expert_eval: boards must be (G, {want}) with G players")
+        out = np.zeros((b.shape[0], self.A), np.int32)
+        self._check(self.lib.mz_expert_eval(self.h, env_kind, b.shape[0], _p(b), _p(p), depth, _p(out)),
+                    "mz_expert_eval")
+        return out
 
     def eval_results(self):
         """(games finished, MuZero wins, opponent wins, draws) since selfplay_init."""

@@ -27,6 +27,7 @@ static const size_t kLdsMax = 160 * 1024;   // LDS per workgroup on gfx950
 #include "mz_resnet_params.h"
 #include "mz_backprop_params.h"
 #include "mz_selfplay_params.h"
+#include "mz_expert_rules.h"
 #include "mz_ckpt_iface.h"
 #include "mz_snap_iface.h"
 
@@ -203,6 +204,7 @@ struct mz_handle {
     bool sp_latch = false;                  // mz_selfplay_move latches temperatures per game
     std::string tr_ckpt_path;               // mz_train_set_networks_path: periodic checkpoints
     int sp_eval = 0, sp_opp = MZ_OPP_SELF, sp_mzp = 1;    // mz_selfplay_mode
+    int sp_expert_depth = 0;                              // mz_expert_depth (0: the env's default)
     long long* d_eval = nullptr;                          // [4] evaluation tally
     float* d_sp_dpow = nullptr;
     float *d_rs_obs = nullptr, *d_rs_act = nullptr, *d_rs_tv = nullptr, *d_rs_tr = nullptr, *d_rs_tp = nullptr,
@@ -3211,10 +3213,8 @@ static SpParams sp_params(mz_handle* h) {
     return S;
 }
 
-extern "C" {
-
-int mz_selfplay_init(mz_handle* h, int env_kind, int G, int replay_games) {
-    if (!h) return -2;
+// the conf must match the env (mz_selfplay_init, mz_expert_eval)
+static int sp_env_check(mz_handle* h, int env_kind) {
     const mz_config& c = h->conf;
     const int W = c.observation_shape[0], H = c.observation_shape[1], C = c.observation_shape[2];
     if (env_kind == MZ_ENV_TICTACTOE) {
@@ -3227,6 +3227,21 @@ int mz_selfplay_init(mz_handle* h, int env_kind, int G, int replay_games) {
     } else {
         return fail(h, "unknown env_kind");
     }
+    return 0;
+}
+
+// D of the expert opponent: the handle's mz_expert_depth, 0 = the env's default
+static int expert_depth_of(const mz_handle* h, int env_kind) {
+    return h->sp_expert_depth ? h->sp_expert_depth : env_kind == MZ_ENV_TICTACTOE ? 9 : 4;
+}
+
+extern "C" {
+
+int mz_selfplay_init(mz_handle* h, int env_kind, int G, int replay_games) {
+    if (!h) return -2;
+    const mz_config& c = h->conf;
+    const int W = c.observation_shape[0], H = c.observation_shape[1], C = c.observation_shape[2];
+    if (int rc = sp_env_check(h, env_kind)) return rc;
     if (G < 1 || G > h->max_games) return fail(h, "G must be in 1..max_games");
     if (replay_games < G) return fail(h, "replay_games must be >= G (one move can finish every slot)");
     if (c.max_moves < 1) return fail(h, "max_moves must be >= 1");
@@ -3317,6 +3332,10 @@ int mz_selfplay_move(mz_handle* h, uint32_t rng_step, uint32_t game_offset, floa
     int rc = search_dev(h, G, h->d_obs, h->d_legal, h->d_tp, 1, rng_step, game_offset, temperature, h->d_cv,
                         h->d_rv, h->d_act, st, S.temp_g);
     if (rc) return rc;
+    if (h->sp_eval && h->sp_opp == MZ_OPP_EXPERT) {  // the expert's turns: its move replaces the search's action
+        ExpertArgs X{expert_depth_of(h, h->sp_env), h->d_act, nullptr};
+        hipLaunchKernelGGL(mz_expert_move, waves, dim3(256), 0, st, S, X);
+    }
     hipLaunchKernelGGL(mz_sp_commit, waves, dim3(256), 0, st, S);
     hipLaunchKernelGGL(mz_sp_order, dim3(1), dim3(1024), 0, st, S);
     hipLaunchKernelGGL(mz_sp_store, dim3(G), dim3(256), 0, st, S);
@@ -3328,9 +3347,55 @@ int mz_selfplay_mode(mz_handle* h, int mode, int opponent, int muzero_player) {
     if (!h) return -2;
     if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
     if (mode != MZ_SP_TRAIN && mode != MZ_SP_EVAL) return fail(h, "mode must be MZ_SP_TRAIN or MZ_SP_EVAL");
-    if (opponent != MZ_OPP_SELF && opponent != MZ_OPP_RANDOM) return fail(h, "opponent must be MZ_OPP_SELF or MZ_OPP_RANDOM");
+    if (opponent != MZ_OPP_SELF && opponent != MZ_OPP_RANDOM && opponent != MZ_OPP_EXPERT)
+        return fail(h, "opponent must be MZ_OPP_SELF, MZ_OPP_RANDOM or MZ_OPP_EXPERT");
+    if (opponent == MZ_OPP_EXPERT && h->sp_env == MZ_ENV_ATARI) return fail(h, "expert: needs a two-player board env");
     if (muzero_player != 1 && muzero_player != 2) return fail(h, "muzero_player must be 1 or 2");
     h->sp_eval = mode == MZ_SP_EVAL; h->sp_opp = opponent; h->sp_mzp = muzero_player;
+    return 0;
+}
+
+int mz_expert_depth(mz_handle* h, int depth) {
+    if (!h) return -2;
+    if (depth < 0 || depth > MZX_MAX_DEPTH) return fail(h, "expert: depth must be in 0..9 (0 = the env's default)");
+    h->sp_expert_depth = depth;
+    return 0;
+}
+
+int mz_expert_eval(mz_handle* h, int env_kind, int G, const uint8_t* boards, const int32_t* players, int depth,
+                   int32_t* scores) {
+    if (!h || !boards || !players || !scores) return -2;
+    if (int rc = sp_env_check(h, env_kind)) return rc;
+    if (env_kind == MZ_ENV_ATARI) return fail(h, "expert: needs a two-player board env");
+    if (G < 1) return fail(h, "expert: G must be >= 1");
+    if (depth < 1 || depth > MZX_MAX_DEPTH) return fail(h, "expert: depth must be in 1..9");
+    const int A = h->A, osz = 3 * mzx_cells(env_kind);
+    for (int g = 0; g < G; ++g) {
+        ExpertPos pos;
+        if (players[g] != 1 && players[g] != 2) return fail(h, "expert: player must be 1 or 2");
+        if (!mzx_pos_from_planes(env_kind, boards + (size_t)g * osz, players[g], &pos))
+            return fail(h, "expert: every cell must be set in exactly one plane");
+    }
+    MZ_TRY(h, hipSetDevice(h->device));
+    uint8_t* d_b = nullptr; int32_t* d_p = nullptr; int32_t* d_s = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_b), (size_t)G * osz);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_p), (size_t)G * 4);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_s), (size_t)G * A * 4);
+    if (e == hipSuccess) e = hipMemcpy(d_b, boards, (size_t)G * osz, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_p, players, (size_t)G * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        SpParams S;
+        std::memset(&S, 0, sizeof(S));
+        S.G = G; S.env = env_kind; S.W = h->conf.observation_shape[0]; S.H = h->conf.observation_shape[1];
+        S.osz = osz; S.A = A; S.board = d_b; S.player = d_p;
+        ExpertArgs X{depth, nullptr, d_s};
+        hipLaunchKernelGGL(mz_expert_move, dim3((G + 3) / 4), dim3(256), 0, h->stream, S, X);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = hipMemcpy(scores, d_s, (size_t)G * A * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(d_b); (void)hipFree(d_p); (void)hipFree(d_s);
+    MZ_TRY(h, e);
     return 0;
 }
 

@@ -104,6 +104,15 @@ struct SpParams {
     float* tgame;
 };
 
+// mz_expert_move (mz_expert.hip): the rules-search expert opponent.  The rows are SpParams'
+// (G, env, A, osz, board, player; in self-play mode also muzero_player, seed, step, game_offset).
+struct ExpertArgs {
+    int depth;                  // D, 1..9
+    int32_t* act;               // self-play mode (scores == null): [G] the search's actions; the rows whose
+                                // mover is not muzero_player get the expert's
+    int32_t* scores;            // eval mode: [G][A] score(s, a, D) of every row, -128 for an illegal action
+};
+
 // get_batch + make_target (ReplayBuffer.jl:5-50, 73-107, 188-217) on the shard
 struct RpSampleParams {
     int B, K, A, osz, P, F, stacked, T, td, cap;
@@ -130,6 +139,7 @@ extern "C" __global__ void mz_sp_commit(SpParams S);
 extern "C" __global__ void mz_sp_order(SpParams S);
 extern "C" __global__ void mz_sp_store(SpParams S);
 extern "C" __global__ void mz_sp_reset(SpParams S);
+extern "C" __global__ void mz_expert_move(SpParams S, ExpertArgs X);
 extern "C" __global__ void mz_rp_sample(RpSampleParams Q);
 extern "C" __global__ void mz_rp_per_init(SpHist ring, int slot, int len, int Tmax, int td, const float* disc_pow,
                                           int alpha);

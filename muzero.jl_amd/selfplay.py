@@ -14,6 +14,7 @@ from typing import List, Optional
 import numpy as np
 
 from .config import stacked_features
+from .games.expert import DEFAULT_DEPTH, expert_pick, expert_scores
 from .rng import rng_below, rng_u32
 
 MZ_RNG_OPPONENT = 7                                               # include/mz_detmath.h
@@ -88,12 +89,16 @@ def get_stacked_observations(obs_hist, action_hist, index, num_stacked, plane):
 class BatchedSelfPlay:
     """G TicTacToe games played in lockstep on one engine (one GPU)."""
 
-    def __init__(self, engine, env_cls, G, game_offset=0, step0=0, opponent="self", muzero_player=1):
+    def __init__(self, engine, env_cls, G, game_offset=0, step0=0, opponent="self", muzero_player=1,
+                 expert_depth=None):
         """opponent "self" (self_play!, SelfPlay.jl:384-419) or "random": the
         player != muzero_player plays a uniform legal action
-        (select_opponent_action, :311-325) — competitive_play! (:421-435)."""
-        assert opponent in ("self", "random") and muzero_player in (1, 2)
+        (select_opponent_action, :311-325) — competitive_play! (:421-435);
+        "expert": that player plays the rules search of games/expert.py to
+        expert_depth plies (None: the env's default)."""
+        assert opponent in ("self", "random", "expert") and muzero_player in (1, 2)
         self.opponent = opponent
+        self.expert_depth = expert_depth
         self.muzero_player = muzero_player
         self.eng = engine
         self.conf = engine.conf
@@ -102,6 +107,7 @@ class BatchedSelfPlay:
         self.env = (env_cls(G, seed=engine.rng_seed, game_offset=game_offset) if getattr(env_cls, "KEYED", False)
                     else env_cls(G))
         self.frame_stack = getattr(env_cls, "FRAME_STACK", 0)
+        assert not (opponent == "expert" and self.frame_stack), "expert: needs a two-player board env"
         self.game_offset = game_offset
         self.step = step0
         self.plane = self.conf.observation_shape[0] * self.conf.observation_shape[1]
@@ -146,6 +152,13 @@ class BatchedSelfPlay:
                 if len(acts):
                     r = rng_u32(self.eng.rng_seed, MZ_RNG_OPPONENT, self.game_offset + int(g), self.step, 0)
                     act[g] = acts[rng_below(r, len(acts))] + 1
+        if self.opponent == "expert":                                         # the same turns, the same stream
+            name = "tictactoe" if self.env.board.shape[1] == 27 else "connect4"
+            depth = self.expert_depth or DEFAULT_DEPTH[name]
+            for g in np.flatnonzero(tp != self.muzero_player):
+                if legal[g].any():
+                    r = rng_u32(self.eng.rng_seed, MZ_RNG_OPPONENT, self.game_offset + int(g), self.step, 0)
+                    act[g] = expert_pick(expert_scores(name, self.env.board[g], int(tp[g]), depth), r)
         reward, done = self.env.step(act)                                     # :366-368
         for g, h in enumerate(self.histories):                                # :375-379
             h.child_visits.append(cv[g])
