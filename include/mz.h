@@ -341,10 +341,50 @@ int mz_selfplay_move(mz_handle* h, uint32_t rng_step, uint32_t game_offset, floa
  * the k-th (ascending) of the actions with the maximal score(s, a, D),
  * k = mz_rng_below(draw, their count).  The reference's Config.opponent
  * defaults to "expert" and its expert_agent() is a stub
- * (games/AbstractGame.jl:91-93): this is the opponent that default asks for. */
+ * (games/AbstractGame.jl:91-93): this is the opponent that default asks for.
+ * MZ_OPP_NETWORK (board envs only): net against net.  On the
+ * same turns the opponent is the same search run with the opponent's weight
+ * set (mz_opponent_*, below).  Each move searches all G slots twice, first
+ * with the engine's nets, then with the opponent's, with the same inputs,
+ * rng_step, game_offset, per-slot temperatures and exploration flag (the
+ * Philox id of slot g is game_offset + g in both), and one launch
+ * (mz_sp_pick) gives every slot whose mover is not muzero_player the
+ * opponent search's child_visits, root value and action; the history then
+ * holds the mover's own search statistics.  Nothing crosses PCIe.  With
+ * mz_debug_enable(h, 1) the dumped tree is the second (the opponent's)
+ * search's.  Refused until the opponent set is complete, and on the
+ * one-player frame-stack env.  No other mode launches or allocates anything
+ * for it.                                                                    */
 enum { MZ_SP_TRAIN = 0, MZ_SP_EVAL = 1 };
-enum { MZ_OPP_SELF = 0, MZ_OPP_RANDOM = 1, MZ_OPP_EXPERT = 2 };
+enum { MZ_OPP_SELF = 0, MZ_OPP_RANDOM = 1, MZ_OPP_EXPERT = 2, MZ_OPP_NETWORK = 3 };
 int mz_selfplay_mode(mz_handle* h, int mode, int opponent, int muzero_player);
+
+/* The opponent's weight set of MZ_OPP_NETWORK: a second set of the three
+ * nets (flat parameters and their search images), allocated by the first
+ * call that fills it.  A handle setting like mz_expert_depth:
+ * mz_selfplay_init, mz_snapshot_load and mz_weights_set leave it alone, and
+ * snapshots do not carry it.  It is complete once all three nets have been
+ * given: by three mz_opponent_weights_set, one mz_opponent_from or one
+ * mz_opponent_load.
+ *   _weights_set: host floats in mz_weights_set's layout; an n other than
+ *     mz_net_param_count is refused.  The set's search images are rebuilt
+ *     when the last missing net arrives and on every later call.
+ *     Synchronises.
+ *   _weights_get: one net of the set (refused if that net was never given).
+ *     Synchronises.
+ *   _from: a device copy, stream-ordered on `stream`, no host
+ *     synchronisation: MZ_TRAIN_LEARNER = the engine's current nets (needs
+ *     no mz_train_init), MZ_TRAIN_ACTOR / MZ_TRAIN_QUEUED = the actor-learner
+ *     loop's sets (refused before mz_train_init).
+ *   _load: the three nets' arrays, by name, from a file mz_checkpoint_save
+ *     or mz_snapshot_save wrote.  The network kind and every shape are
+ *     checked against this engine first, and a refused file leaves the set
+ *     as it was.  The learner's nets and ADAM state are not touched.
+ *     *training_step (may be NULL) = the file's.  Synchronises.              */
+int mz_opponent_weights_set(mz_handle* h, int net, const float* flat, size_t n);
+int mz_opponent_weights_get(mz_handle* h, int net, float* flat, size_t n);
+int mz_opponent_from(mz_handle* h, int which, void* stream);
+int mz_opponent_load(mz_handle* h, const char* path, int64_t* training_step);
 
 /* Depth D of the expert opponent, 1..9; 0 (default) = the env's default:
  * 9 for TicTacToe (perfect play under the env's rules), 4 for Connect4
@@ -674,8 +714,9 @@ int mz_checkpoint_load(mz_handle* h, const char* path, int64_t* training_step);
  * Handle settings are NOT state: mz_train_set_reanalyse, mz_selfplay_mode,
  * mz_train_set_networks_path, mz_learner_set_mode and mz_debug_enable are
  * written into the metadata for information, and the loading host applies its
- * own (its mz_selfplay_mode and mz_expert_depth survive the load; the depth
- * is not written to the file).  At world > 1 each rank saves
+ * own (its mz_selfplay_mode, mz_expert_depth and opponent weight set survive
+ * the load; the depth and the opponent set are not written to the file).
+ * At world > 1 each rank saves
  * and loads its own file; the host orders the calls.                          */
 int mz_snapshot_save(mz_handle* h, const char* path, int64_t training_step);
 int mz_snapshot_load(mz_handle* h, const char* path, int64_t* training_step);

@@ -42,6 +42,7 @@ const NET_REPR, NET_PRED, NET_DYN = Cint(0), Cint(1), Cint(2)
 const ACT_IDENTITY, ACT_RELU, ACT_TANH = Int32(0), Int32(1), Int32(2)
 const ENV_TICTACTOE, ENV_CONNECT4, ENV_ATARI = Cint(0), Cint(1), Cint(2)   # ENV_ATARI: the synthetic frame-stacked env of configs[4]
 const SP_TRAIN, SP_EVAL, OPP_SELF, OPP_RANDOM, OPP_EXPERT = Cint(0), Cint(1), Cint(0), Cint(1), Cint(2)
+const OPP_NETWORK = Cint(3)
 const LEARN_REF_SEMANTICS, LEARN_CORRECTED = Cint(0), Cint(1)
 const TRAIN_LEARNER, TRAIN_ACTOR, TRAIN_QUEUED = Cint(0), Cint(1), Cint(2)
 const REAN_OFF, REAN_BY_VALUE, REAN_BY_SEARCH = Cint(0), Cint(1), Cint(2)
@@ -182,7 +183,27 @@ function expert_eval(e::Engine, env::Cint, boards::Matrix{UInt8}, players::Vecto
                    e.h, env, size(boards, 2), boards, players, depth, scores))
     scores
 end
-function eval_results(e::Engine)               # competitive_play!: (games, MuZero wins, opponent wins, draws)
+# OPP_NETWORK: the opponent's weight set (a handle setting; complete after all three nets, one
+# opponent_from! or one opponent_load!), then selfplay_mode!(e, SP_EVAL; opponent=OPP_NETWORK, mzp=...)
+function opponent_set_weights!(e::Engine, net::Cint, chain)
+    flat = reduce(vcat, vec.(collect(params(chain))))
+    check(e, ccall((:mz_opponent_weights_set, libmz), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}, Csize_t),
+                   e.h, net, flat, length(flat)))
+end
+function opponent_get_weights(e::Engine, net::Cint)
+    flat = similar(get_weights(e, net))
+    check(e, ccall((:mz_opponent_weights_get, libmz), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}, Csize_t),
+                   e.h, net, flat, length(flat)))
+    flat
+end
+opponent_from!(e::Engine, which::Cint) =       # TRAIN_LEARNER | TRAIN_ACTOR | TRAIN_QUEUED, a device copy
+    check(e, ccall((:mz_opponent_from, libmz), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), e.h, which, C_NULL))
+function opponent_load!(e::Engine, path)       # a checkpoint or snapshot file's nets; the learner is not touched
+    step = Ref{Int64}(0)
+    check(e, ccall((:mz_opponent_load, libmz), Cint, (Ptr{Cvoid}, Cstring, Ref{Int64}), e.h, path, step))
+    step[]
+end
+function eval_results(e::Engine)              # competitive_play!: (games, MuZero wins, opponent wins, draws)
     r = zeros(Int64, 4)
     check(e, ccall((:mz_eval_results, libmz), Cint, (Ptr{Cvoid}, Ptr{Int64}), e.h, r))
     Tuple(r)

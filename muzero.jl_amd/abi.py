@@ -20,7 +20,7 @@ ENV_TICTACTOE, ENV_CONNECT4, ENV_ATARI = 0, 1, 2
 SP_TRAIN, SP_EVAL = 0, 1
 TRAIN_LEARNER, TRAIN_ACTOR, TRAIN_QUEUED = 0, 1, 2
 LEARN_REF_SEMANTICS, LEARN_CORRECTED = 0, 1
-OPP_SELF, OPP_RANDOM, OPP_EXPERT = 0, 1, 2
+OPP_SELF, OPP_RANDOM, OPP_EXPERT, OPP_NETWORK = 0, 1, 2, 3
 REAN_OFF, REAN_BY_VALUE, REAN_BY_SEARCH = 0, 1, 2
 
 _lib = None
@@ -73,6 +73,10 @@ SIGNATURES = {
     "mz_selfplay_mode": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "mz_expert_depth": (ctypes.c_int, [_VP, ctypes.c_int]),
     "mz_expert_eval": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP, ctypes.c_int, _VP]),
+    "mz_opponent_weights_set": (ctypes.c_int, [_VP, ctypes.c_int, _VP, ctypes.c_size_t]),
+    "mz_opponent_weights_get": (ctypes.c_int, [_VP, ctypes.c_int, _VP, ctypes.c_size_t]),
+    "mz_opponent_from": (ctypes.c_int, [_VP, ctypes.c_int, _VP]),
+    "mz_opponent_load": (ctypes.c_int, [_VP, ctypes.c_char_p, _VP]),
     "mz_eval_results": (ctypes.c_int, [_VP, _VP]),
     "mz_replay_counts": (ctypes.c_int, [_VP, _VP, _VP]),
     "mz_replay_save_game": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
@@ -429,6 +433,29 @@ class Engine:
         self._check(self.lib.mz_expert_eval(self.h, env_kind, b.shape[0], _p(b), _p(p), depth, _p(out)),
                     "mz_expert_eval")
         return out
+
+    # ---- the opponent's weight set of OPP_NETWORK: a handle setting
+    def opponent_set_weights(self, net, flat):
+        """One net of the opponent set (Flux order, as set_weights); complete after all three."""
+        flat = np.ascontiguousarray(flat, dtype=np.float32)
+        self._check(self.lib.mz_opponent_weights_set(self.h, net, _p(flat), flat.size), "mz_opponent_weights_set")
+
+    def opponent_get_weights(self, net):
+        out = np.empty(self.param_count(net), dtype=np.float32)
+        self._check(self.lib.mz_opponent_weights_get(self.h, net, _p(out), out.size), "mz_opponent_weights_get")
+        return out
+
+    def opponent_from(self, which, stream=None):
+        """The opponent set := the engine's current nets (TRAIN_LEARNER) or the actor-learner loop's
+        TRAIN_ACTOR / TRAIN_QUEUED set: a stream-ordered device copy, no host synchronisation."""
+        self._check(self.lib.mz_opponent_from(self.h, which, stream), "mz_opponent_from")
+
+    def opponent_load(self, path):
+        """The opponent set := the three nets of a checkpoint or snapshot file (the learner is not
+        touched; a refused file leaves the set as it was); returns the file's training step."""
+        step = ctypes.c_int64()
+        self._check(self.lib.mz_opponent_load(self.h, os.fsencode(path), ctypes.byref(step)), "mz_opponent_load")
+        return step.value
 
     def eval_results(self):
         """(games finished, MuZero wins, opponent wins, draws) since selfplay_init."""

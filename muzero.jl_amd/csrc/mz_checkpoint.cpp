@@ -19,6 +19,7 @@
 // __metadata__: format, network ("fc" | "resnet"), training_step, config
 // (JSON).  Loading checks every parameter's shape against this engine.
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -44,6 +45,54 @@ struct Entry {
     std::vector<int64_t> shape;   // safetensors (row-major) shape
     const void* data;
     size_t bytes;
+};
+
+// an open safetensors file: the parsed header, and reads of named tensors checked against the
+// dtype and shape the caller expects; every call returns "" or the error
+struct StFile {
+    std::unique_ptr<FILE, int (*)(FILE*)> f{nullptr, std::fclose};
+    uint64_t hl = 0;
+    long long fsize = 0;
+    mzst::JV root;
+
+    std::string open(const char* path) {
+        f.reset(std::fopen(path, "rb"));
+        if (!f) return std::string("cannot open ") + path;
+        if (std::fread(&hl, 8, 1, f.get()) != 1 || hl > (1u << 28)) return "not a safetensors file";
+        std::string hdr(hl, '\0');
+        if (std::fread(&hdr[0], 1, hl, f.get()) != hl) return "truncated header";
+        const std::string perr = mzst::parse_header(hdr.data(), hdr.size(), &root);
+        if (!perr.empty()) return perr;
+        std::fseek(f.get(), 0, SEEK_END);
+        fsize = std::ftell(f.get());
+        return "";
+    }
+    std::string read(const std::string& name, const char* dtype, size_t esz, std::vector<int64_t> shape, void* dst) {
+        long long off = 0;
+        const std::string err = mzst::entry_span(root, name, dtype, esz, shape, hl, fsize, &off);
+        if (!err.empty()) return err;
+        size_t cnt = 1;
+        for (int64_t d : shape) cnt *= (size_t)d;
+        std::fseek(f.get(), (long)off, SEEK_SET);
+        if (std::fread(dst, 1, cnt * esz, f.get()) != cnt * esz) return name + ": short read";
+        return "";
+    }
+    // the three nets' Flux.params arrays into flat (the engine's flat order), every shape checked
+    std::string read_nets(const mz_handle* h, float* flat) {
+        for (const MzParamDesc& d : mz_param_table(h)) {
+            std::vector<int64_t> shp(d.jshape.rbegin(), d.jshape.rend());
+            const std::string e = read(d.name, "F32", 4, shp, flat + d.off);
+            if (!e.empty()) return e;
+        }
+        return "";
+    }
+    std::string meta(const char* key) const {          // a __metadata__ string, "" if absent
+        auto md = root.obj.find("__metadata__");
+        if (md == root.obj.end() || md->second.t != mzst::JV::OBJ) return "";
+        auto it = md->second.obj.find(key);
+        return it != md->second.obj.end() && it->second.t == mzst::JV::STR ? it->second.str : "";
+    }
+    int64_t training_step() const { return std::strtoll(meta("training_step").c_str(), nullptr, 10); }
 };
 
 }  // namespace
@@ -94,48 +143,35 @@ int mz_checkpoint_save(mz_handle* h, const char* path, int64_t training_step) {
 int mz_checkpoint_load(mz_handle* h, const char* path, int64_t* training_step) {
     if (!h) return -2;
     if (!path) return mz_set_error(h, "null path");
-    FILE* f = std::fopen(path, "rb");
-    if (!f) return mz_set_error(h, std::string("cannot open ") + path);
-    std::unique_ptr<FILE, int (*)(FILE*)> guard(f, std::fclose);
-    uint64_t hl = 0;
-    if (std::fread(&hl, 8, 1, f) != 1 || hl > (1u << 28)) return mz_set_error(h, "not a safetensors file");
-    std::string hdr(hl, '\0');
-    if (std::fread(&hdr[0], 1, hl, f) != hl) return mz_set_error(h, "truncated header");
-    mzst::JV root;
-    const std::string perr = mzst::parse_header(hdr.data(), hdr.size(), &root);
-    if (!perr.empty()) return mz_set_error(h, perr);
-    std::fseek(f, 0, SEEK_END);
-    const long long fsize = std::ftell(f);
-    auto read = [&](const std::string& name, const char* dtype, size_t esz, std::vector<int64_t> shape,
-                    void* dst) -> int {
-        long long off = 0;
-        const std::string err = mzst::entry_span(root, name, dtype, esz, shape, hl, fsize, &off);
-        if (!err.empty()) return mz_set_error(h, err);
-        size_t cnt = 1;
-        for (int64_t d : shape) cnt *= (size_t)d;
-        std::fseek(f, (long)off, SEEK_SET);
-        if (std::fread(dst, 1, cnt * esz, f) != cnt * esz) return mz_set_error(h, name + ": short read");
-        return 0;
-    };
+    StFile sf;
+    if (const std::string e = sf.open(path); !e.empty()) return mz_set_error(h, e);
     const size_t n = mz_flat_count(h);
     std::vector<float> flat(n), m(n), v(n);
     double bp[2];
-    for (const MzParamDesc& d : mz_param_table(h)) {
-        std::vector<int64_t> shp(d.jshape.rbegin(), d.jshape.rend());
-        if (int rc = read(d.name, "F32", 4, shp, flat.data() + d.off)) return rc;
-    }
-    if (int rc = read("adam.m", "F32", 4, {(int64_t)n}, m.data())) return rc;
-    if (int rc = read("adam.v", "F32", 4, {(int64_t)n}, v.data())) return rc;
-    if (int rc = read("adam.beta_pow", "F64", 8, {2}, bp)) return rc;
-    if (training_step) {
-        *training_step = 0;
-        auto md = root.obj.find("__metadata__");
-        if (md != root.obj.end() && md->second.t == mzst::JV::OBJ) {
-            auto ts = md->second.obj.find("training_step");
-            if (ts != md->second.obj.end() && ts->second.t == mzst::JV::STR) *training_step = std::strtoll(ts->second.str.c_str(), nullptr, 10);
-        }
-    }
+    std::string e = sf.read_nets(h, flat.data());
+    if (e.empty()) e = sf.read("adam.m", "F32", 4, {(int64_t)n}, m.data());
+    if (e.empty()) e = sf.read("adam.v", "F32", 4, {(int64_t)n}, v.data());
+    if (e.empty()) e = sf.read("adam.beta_pow", "F64", 8, {2}, bp);
+    if (!e.empty()) return mz_set_error(h, e);
+    if (training_step) *training_step = sf.training_step();
     return mz_state_set(h, flat.data(), m.data(), v.data(), bp);
+}
+
+// The opponent's weight set of MZ_OPP_NETWORK from a checkpoint or a snapshot (a superset of one):
+// only the three nets' arrays are read, by name; the file is validated whole before the set changes.
+int mz_opponent_load(mz_handle* h, const char* path, int64_t* training_step) {
+    if (!h) return -2;
+    if (!path) return mz_set_error(h, "null path");
+    StFile sf;
+    if (const std::string e = sf.open(path); !e.empty()) return mz_set_error(h, e);
+    const std::string kind = sf.meta("network");
+    if (kind != mz_net_kind(h))
+        return mz_set_error(h, "opponent_load: the file's network is \"" + kind + "\", this engine's is \"" +
+                                   mz_net_kind(h) + "\"");
+    std::vector<float> flat(mz_flat_count(h));
+    if (const std::string e = sf.read_nets(h, flat.data()); !e.empty()) return mz_set_error(h, "opponent_load: " + e);
+    if (training_step) *training_step = sf.training_step();
+    return mz_opponent_put(h, flat.data());
 }
 
 }  // extern "C"

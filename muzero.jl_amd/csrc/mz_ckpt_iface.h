@@ -22,6 +22,8 @@ size_t mz_flat_count(const mz_handle* h);
 // nets back to back), ADAM moments, βp = (β1^t, β2^t) (Learning.jl:385-397)
 int mz_state_get(mz_handle* h, float* flat, float* m, float* v, double* beta_pow);
 int mz_state_set(mz_handle* h, const float* flat, const float* m, const float* v, const double* beta_pow);
+// the opponent's weight set (mz_opponent_load): the three nets, host, Flux order, back to back
+int mz_opponent_put(mz_handle* h, const float* flat);
 // "fc" | "resnet" and a JSON object describing config + hyper-parameters
 std::string mz_net_kind(const mz_handle* h);
 std::string mz_describe(const mz_handle* h);

@@ -261,6 +261,12 @@ struct mz_handle {
     struct WSet { float* flat = nullptr; float* Wp = nullptr; float* Bp = nullptr; float* smw = nullptr;
                   float* smb = nullptr; };
     WSet tr_actor;
+    // MZ_OPP_NETWORK: the opponent's weight set, a handle setting allocated by the
+    // first mz_opponent_* call that fills it; opp_have = the nets given so far (bit per net, 7 =
+    // complete); the opponent search's outputs (in sp_allocs, allocated when the mode is first used)
+    WSet opp;
+    unsigned opp_have = 0;
+    float* d_cv2 = nullptr; float* d_rv2 = nullptr; int32_t* d_act2 = nullptr;
     float* d_tr_queued = nullptr;
     int tr_B = 0;
     int64_t tr_t = 0, tr_games = 0, tr_refresh = 0;
@@ -3235,6 +3241,19 @@ static int expert_depth_of(const mz_handle* h, int env_kind) {
     return h->sp_expert_depth ? h->sp_expert_depth : env_kind == MZ_ENV_TICTACTOE ? 9 : 4;
 }
 
+static void wset_swap(mz_handle* h, mz_handle::WSet& w);
+
+// MZ_OPP_NETWORK: the opponent search's outputs, part of the self-play state (a snapshot load
+// re-creates that state and keeps the mode, so the move asks again)
+static int opp_io(mz_handle* h) {
+    if (h->d_act2) return 0;
+    const size_t G = (size_t)h->sp_G;
+    MZ_TRY(h, spalloc(h, &h->d_cv2, G * h->A, false));
+    MZ_TRY(h, spalloc(h, &h->d_rv2, G, false));
+    MZ_TRY(h, spalloc(h, &h->d_act2, G, false));
+    return 0;
+}
+
 extern "C" {
 
 int mz_selfplay_init(mz_handle* h, int env_kind, int G, int replay_games) {
@@ -3270,6 +3289,7 @@ int mz_selfplay_init(mz_handle* h, int env_kind, int G, int replay_games) {
     h->rn_cap = 0;                              // the ResNet staging buffers were in sp_allocs
     h->sp_ring.rcv = nullptr; h->d_rq_obs = nullptr;    // so were rcv and the reanalyse search's io
     h->d_rean_rows = nullptr; h->rean_rows_cap = 0;     // and the worker's row list
+    h->d_cv2 = nullptr; h->d_rv2 = nullptr; h->d_act2 = nullptr;   // and MZ_OPP_NETWORK's second outputs
     MZ_TRY(h, spalloc(h, &h->d_sp_counters, MZ_SP_COUNTERS));
     const long long cursor0 = 1;                        // the reanalyse cursor: game number 1
     MZ_TRY(h, hipMemcpy(h->d_sp_counters + MZ_REAN_CURSOR, &cursor0, sizeof(cursor0), hipMemcpyHostToDevice));
@@ -3320,6 +3340,9 @@ int mz_selfplay_move(mz_handle* h, uint32_t rng_step, uint32_t game_offset, floa
     S.tgame = h->sp_latch ? h->d_sp_tgame : nullptr;
     const int G = h->sp_G;
     const dim3 waves((G + 3) / 4);
+    // the opponent's nets play its turns (mz_selfplay_mode checked the set and the env; both stay)
+    const bool arena = h->sp_eval && h->sp_opp == MZ_OPP_NETWORK;
+    if (arena && opp_io(h)) return -1;
     if (h->sp_reset_pending) {                      // the initial Atari-like games (mz_selfplay_init)
         SpParams R = S;
         R.reset_step = 0xFFFFFFFFu;
@@ -3336,6 +3359,15 @@ int mz_selfplay_move(mz_handle* h, uint32_t rng_step, uint32_t game_offset, floa
         ExpertArgs X{expert_depth_of(h, h->sp_env), h->d_act, nullptr};
         hipLaunchKernelGGL(mz_expert_move, waves, dim3(256), 0, st, S, X);
     }
+    if (arena) {    // the same search with the opponent's nets; its turns take that search's whole result
+        wset_swap(h, h->opp);
+        rc = search_dev(h, G, h->d_obs, h->d_legal, h->d_tp, 1, rng_step, game_offset, temperature, h->d_cv2,
+                        h->d_rv2, h->d_act2, st, S.temp_g);
+        wset_swap(h, h->opp);
+        if (rc) return rc;
+        PickArgs X{h->d_cv, h->d_rv, h->d_act, h->d_cv2, h->d_rv2, h->d_act2};
+        hipLaunchKernelGGL(mz_sp_pick, waves, dim3(256), 0, st, S, X);
+    }
     hipLaunchKernelGGL(mz_sp_commit, waves, dim3(256), 0, st, S);
     hipLaunchKernelGGL(mz_sp_order, dim3(1), dim3(1024), 0, st, S);
     hipLaunchKernelGGL(mz_sp_store, dim3(G), dim3(256), 0, st, S);
@@ -3347,10 +3379,18 @@ int mz_selfplay_mode(mz_handle* h, int mode, int opponent, int muzero_player) {
     if (!h) return -2;
     if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
     if (mode != MZ_SP_TRAIN && mode != MZ_SP_EVAL) return fail(h, "mode must be MZ_SP_TRAIN or MZ_SP_EVAL");
-    if (opponent != MZ_OPP_SELF && opponent != MZ_OPP_RANDOM && opponent != MZ_OPP_EXPERT)
-        return fail(h, "opponent must be MZ_OPP_SELF, MZ_OPP_RANDOM or MZ_OPP_EXPERT");
+    if (opponent != MZ_OPP_SELF && opponent != MZ_OPP_RANDOM && opponent != MZ_OPP_EXPERT && opponent != MZ_OPP_NETWORK)
+        return fail(h, "opponent must be MZ_OPP_SELF, MZ_OPP_RANDOM, MZ_OPP_EXPERT or MZ_OPP_NETWORK");
     if (opponent == MZ_OPP_EXPERT && h->sp_env == MZ_ENV_ATARI) return fail(h, "expert: needs a two-player board env");
     if (muzero_player != 1 && muzero_player != 2) return fail(h, "muzero_player must be 1 or 2");
+    if (opponent == MZ_OPP_NETWORK) {
+        if (h->sp_env == MZ_ENV_ATARI) return fail(h, "opponent network: needs a two-player board env");
+        if (h->opp_have != 7u)
+            return fail(h, "opponent: MZ_OPP_NETWORK needs the opponent's nets (mz_opponent_weights_set / _from / "
+                           "_load first)");
+        MZ_TRY(h, hipSetDevice(h->device));
+        if (mode == MZ_SP_EVAL && opp_io(h)) return -1;
+    }
     h->sp_eval = mode == MZ_SP_EVAL; h->sp_opp = opponent; h->sp_mzp = muzero_player;
     return 0;
 }
@@ -4783,6 +4823,62 @@ int mz_train_weights_get(mz_handle* h, int which, int net, float* flat, size_t n
     return 0;
 }
 
+// ---- the opponent's weight set (MZ_OPP_NETWORK): a handle setting like
+// mz_expert_depth; mz_selfplay_init, mz_snapshot_load and mz_weights_set leave it alone
+static int opp_alloc(mz_handle* h) {
+    if (h->opp.flat) return 0;
+    mz_handle::WSet w;
+    MZ_TRY(h, dalloc(h, &w.flat, h->nflat));
+    MZ_TRY(h, dalloc(h, &w.Wp, h->packed_w_n));
+    if (h->packed_b_n) MZ_TRY(h, dalloc(h, &w.Bp, h->packed_b_n));
+    if (h->small_ok) { MZ_TRY(h, dalloc(h, &w.smw, h->sm_w_n)); MZ_TRY(h, dalloc(h, &w.smb, h->sm_b_n)); }
+    h->opp = w;
+    return 0;
+}
+
+int mz_opponent_weights_set(mz_handle* h, int net, const float* flat, size_t n) {
+    if (!h) return -2;
+    if (net < 0 || net > 2) return fail(h, "bad net id");
+    if (!flat) return fail(h, "opponent_weights_set: null weights");
+    if (n != h->nparams[net]) return fail(h, "opponent_weights_set: wrong parameter count");
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);                  // no search still reads the old set
+    if (opp_alloc(h)) return -1;
+    MZ_TRY(h, hipMemcpyAsync(h->opp.flat + h->flat_off[net], flat, n * 4, hipMemcpyHostToDevice, h->stream));
+    h->opp_have |= 1u << net;
+    if (h->opp_have == 7u && wset_repack(h, h->opp, h->stream)) return -1;   // the images need all three nets
+    MZ_SYNC(h);
+    return 0;
+}
+
+int mz_opponent_weights_get(mz_handle* h, int net, float* flat, size_t n) {
+    if (!h) return -2;
+    if (net < 0 || net > 2) return fail(h, "bad net id");
+    if (!flat) return fail(h, "opponent_weights_get: null buffer");
+    if (n != h->nparams[net]) return fail(h, "opponent_weights_get: wrong parameter count");
+    if (!(h->opp_have >> net & 1u)) return fail(h, "opponent_weights_get: this net of the set was never given");
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);                  // a stream-ordered mz_opponent_from has landed
+    MZ_TRY(h, hipMemcpy(flat, h->opp.flat + h->flat_off[net], n * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int mz_opponent_from(mz_handle* h, int which, void* stream) {
+    if (!h) return -2;
+    if (which != MZ_TRAIN_LEARNER && which != MZ_TRAIN_ACTOR && which != MZ_TRAIN_QUEUED)
+        return fail(h, "opponent_from: which must be MZ_TRAIN_LEARNER, MZ_TRAIN_ACTOR or MZ_TRAIN_QUEUED");
+    if (which != MZ_TRAIN_LEARNER && !h->tr_B) return fail(h, "opponent_from: mz_train_init first");
+    MZ_TRY(h, hipSetDevice(h->device));
+    if (opp_alloc(h)) return -1;
+    hipStream_t st = stream_of(h, stream);
+    const float* src = which == MZ_TRAIN_LEARNER ? h->d_flat
+                       : which == MZ_TRAIN_ACTOR ? h->tr_actor.flat : h->d_tr_queued;
+    MZ_TRY(h, hipMemcpyAsync(h->opp.flat, src, h->nflat * 4, hipMemcpyDeviceToDevice, st));
+    if (wset_repack(h, h->opp, st)) return -1;
+    h->opp_have = 7u;
+    return 0;
+}
+
 int mz_sync(mz_handle* h) {
     if (!h) return -2;
     MZ_TRY(h, hipSetDevice(h->device));
@@ -4793,6 +4889,18 @@ int mz_sync(mz_handle* h) {
 }
 
 }  // extern "C"
+
+// mz_opponent_load's engine side (mz_ckpt_iface.h): a validated file's three nets become the set
+int mz_opponent_put(mz_handle* h, const float* flat) {
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);
+    if (opp_alloc(h)) return -1;
+    MZ_TRY(h, hipMemcpyAsync(h->opp.flat, flat, h->nflat * 4, hipMemcpyHostToDevice, h->stream));
+    if (wset_repack(h, h->opp, h->stream)) return -1;
+    h->opp_have = 7u;
+    MZ_SYNC(h);
+    return 0;
+}
 
 // ---- snapshots (mz_snapshot.hip; mz_snap_iface.h): the engine's side
 // `train`: the weight sets of mz_train_init exist and belong to the view

@@ -4,7 +4,8 @@
 // observations, legal mask, to_play) -> the batched search -> mz_sp_commit
 // (env step, history append, finish test) -> mz_sp_order (ring slots of the
 // finished games in slot order, replay counters) -> mz_sp_store (finished
-// game -> replay ring, slot reset).  Nothing crosses PCIe.  mz_rp_sample is
+// game -> replay ring, slot reset).  Nothing crosses PCIe.  MZ_OPP_NETWORK
+// searches twice and mz_sp_pick chooses per slot before the commit.  mz_rp_sample is
 // get_batch + make_target on the ring, writing an mz_batch in HBM.
 //
 // Env rules: TicTacToe exactly as games/tictactoe/game.jl with quirk Q14 (the
@@ -136,6 +137,17 @@ extern "C" __global__ __launch_bounds__(256) void mz_sp_prepare(SpParams S) {
         if (S.temp_g)                                              // :344-346
             S.temp_g[g] = S.temp_threshold >= 0 && t >= S.temp_threshold ? 0.0f : tg;
     }
+}
+
+// MZ_OPP_NETWORK: both sides searched every slot; a slot whose
+// mover is not muzero_player takes the opponent search's whole result, so
+// mz_sp_commit records and plays the mover's own.  One wave per slot.
+extern "C" __global__ __launch_bounds__(256) void mz_sp_pick(SpParams S, PickArgs X) {
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (g >= S.G) return;
+    if (S.player[g] == S.muzero_player) return;
+    for (int a = lane; a < S.A; a += 64) X.cv[(size_t)g * S.A + a] = X.cv2[(size_t)g * S.A + a];
+    if (lane == 0) { X.act[g] = X.act2[g]; X.rv[g] = X.rv2[g]; }
 }
 
 extern "C" __global__ __launch_bounds__(256) void mz_sp_commit(SpParams S) {

@@ -113,6 +113,14 @@ struct ExpertArgs {
     int32_t* scores;            // eval mode: [G][A] score(s, a, D) of every row, -128 for an illegal action
 };
 
+// mz_sp_pick (mz_selfplay.hip): MZ_OPP_NETWORK's choice between the two searches of one move.
+// The rows are SpParams' (G, A, player, muzero_player).
+struct PickArgs {
+    float* cv; float* rv; int32_t* act;                         // [G][A], [G], [G] the engine's nets' search; the rows
+                                                                // whose mover is not muzero_player get ...
+    const float* cv2; const float* rv2; const int32_t* act2;    // ... the opponent's nets' search of the same rows
+};
+
 // get_batch + make_target (ReplayBuffer.jl:5-50, 73-107, 188-217) on the shard
 struct RpSampleParams {
     int B, K, A, osz, P, F, stacked, T, td, cap;
@@ -140,6 +148,7 @@ extern "C" __global__ void mz_sp_order(SpParams S);
 extern "C" __global__ void mz_sp_store(SpParams S);
 extern "C" __global__ void mz_sp_reset(SpParams S);
 extern "C" __global__ void mz_expert_move(SpParams S, ExpertArgs X);
+extern "C" __global__ void mz_sp_pick(SpParams S, PickArgs X);
 extern "C" __global__ void mz_rp_sample(RpSampleParams Q);
 extern "C" __global__ void mz_rp_per_init(SpHist ring, int slot, int len, int Tmax, int td, const float* disc_pow,
                                           int alpha);

@@ -90,14 +90,19 @@ class BatchedSelfPlay:
     """G TicTacToe games played in lockstep on one engine (one GPU)."""
 
     def __init__(self, engine, env_cls, G, game_offset=0, step0=0, opponent="self", muzero_player=1,
-                 expert_depth=None):
+                 expert_depth=None, opponent_engine=None):
         """opponent "self" (self_play!, SelfPlay.jl:384-419) or "random": the
         player != muzero_player plays a uniform legal action
         (select_opponent_action, :311-325) — competitive_play! (:421-435);
         "expert": that player plays the rules search of games/expert.py to
-        expert_depth plies (None: the env's default)."""
-        assert opponent in ("self", "random", "expert") and muzero_player in (1, 2)
+        expert_depth plies (None: the env's default); "network": that player's
+        moves are the same search on opponent_engine (another set of weights
+        under the same config and rng_seed), and the history holds the mover's
+        own search statistics."""
+        assert opponent in ("self", "random", "expert", "network") and muzero_player in (1, 2)
+        assert (opponent == "network") == (opponent_engine is not None), "network: needs opponent_engine (only)"
         self.opponent = opponent
+        self.opponent_engine = opponent_engine
         self.expert_depth = expert_depth
         self.muzero_player = muzero_player
         self.eng = engine
@@ -108,6 +113,7 @@ class BatchedSelfPlay:
                     else env_cls(G))
         self.frame_stack = getattr(env_cls, "FRAME_STACK", 0)
         assert not (opponent == "expert" and self.frame_stack), "expert: needs a two-player board env"
+        assert not (opponent == "network" and self.frame_stack), "opponent network: needs a two-player board env"
         self.game_offset = game_offset
         self.step = step0
         self.plane = self.conf.observation_shape[0] * self.conf.observation_shape[1]
@@ -125,6 +131,23 @@ class BatchedSelfPlay:
                                               len(h.observation_history), c.stacked_observations, self.plane)
         return out
 
+    def _search(self, eng, obs, legal, tp, temperature):
+        """The move's batched search on `eng`: (child visits, root values, actions)."""
+        c = self.conf
+        cv, rv, act = eng.mcts_search(obs, legal, tp, exploration=True, rng_step=self.step,
+                                      game_offset=self.game_offset, temperature=temperature)  # :359-360
+        if c.temperature_threshold is not None:
+            # :344-346: a game with >= temperature_threshold moves plays at temperature 0.
+            # A game's search depends only on its own inputs and Philox keys (game id,
+            # step), so the batch is searched again at 0 and those games take that action.
+            moves = np.array([len(h.action_history) for h in self.histories])
+            cold = moves >= c.temperature_threshold
+            if cold.any() and temperature != 0.0:
+                _, _, act0 = eng.mcts_search(obs, legal, tp, exploration=True, rng_step=self.step,
+                                             game_offset=self.game_offset, temperature=0.0)
+                act = np.where(cold, act0, act)
+        return cv, rv, act
+
     def play_move(self, temperature=1.0):
         """One move of every game (play_game's loop body, SelfPlay.jl:343-380)."""
         c = self.conf
@@ -134,18 +157,13 @@ class BatchedSelfPlay:
                                          self.env.board[g].astype(np.float32))   # :352
         obs = self._stacked()                                                 # :355
         legal = self.env.legal_mask()
-        cv, rv, act = self.eng.mcts_search(obs, legal, tp, exploration=True, rng_step=self.step,
-                                           game_offset=self.game_offset, temperature=temperature)  # :359-360
-        if c.temperature_threshold is not None:
-            # :344-346: a game with >= temperature_threshold moves plays at temperature 0.
-            # A game's search depends only on its own inputs and Philox keys (game id,
-            # step), so the batch is searched again at 0 and those games take that action.
-            moves = np.array([len(h.action_history) for h in self.histories])
-            cold = moves >= c.temperature_threshold
-            if cold.any() and temperature != 0.0:
-                _, _, act0 = self.eng.mcts_search(obs, legal, tp, exploration=True, rng_step=self.step,
-                                                  game_offset=self.game_offset, temperature=0.0)
-                act = np.where(cold, act0, act)
+        cv, rv, act = self._search(self.eng, obs, legal, tp, temperature)
+        if self.opponent == "network":            # the same search with the opponent's nets: its turns take
+            theirs = tp != self.muzero_player     # that search's whole result (mz_sp_pick)
+            cv2, rv2, act2 = self._search(self.opponent_engine, obs, legal, tp, temperature)
+            cv = np.where(theirs[:, None], cv2, cv)
+            rv = np.where(theirs, rv2, rv)
+            act = np.where(theirs, act2, act)
         if self.opponent == "random":                                         # :357-362, :321
             for g in np.flatnonzero(tp != self.muzero_player):
                 acts = np.flatnonzero(legal[g])
