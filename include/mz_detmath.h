@@ -9,7 +9,10 @@
  *
  * Contents
  *   - det_expf / det_tanhf / det_logf (f32 results), det_exp / det_log (f64)
- *     — accuracy ≤ 2 ulp vs libm (tested in tests/test_detmath.py);
+ *     — accuracy ≤ 2 ulp vs libm (tests/test_cpu_oracle.py,
+ *     test_det_elementary_functions_accuracy; every regime of det_tanhf and
+ *     det_expf's subnormal / zero results on the device against the oracle:
+ *     tests/test_weight_regimes_gpu.py);
  *   - Philox4x32-10 counter-based RNG and the stream layout of the engine;
  *   - the Gamma / Dirichlet sampler used by add_exploration_noise!
  *     (reference: src/SelfPlay.jl:102-109, Distributions 0.25.6 Dirichlet).

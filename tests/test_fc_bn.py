@@ -55,8 +55,8 @@ def _torch_forward(conf, hyper, net, flat, x):
             v = v @ torch.from_numpy(W.T.copy()) + torch.from_numpy(b.copy())
             if bg is not None:
                 beta, gamma = (torch.from_numpy(a.copy()) for a in bg)
-                v = F.batch_norm(v, torch.zeros(v.shape[1]), torch.ones(v.shape[1]), gamma, beta,
-                                 training=False, eps=1e-5)
+                v = F.batch_norm(v, torch.zeros(v.shape[1], dtype=v.dtype), torch.ones(v.shape[1], dtype=v.dtype),
+                                 gamma, beta, training=False, eps=1e-5)      # (v's dtype: float64 callers)
             v = torch.relu(v) if act == 1 else torch.tanh(v) if act == 2 else v
         return v
 
