@@ -202,7 +202,7 @@ int mz_debug_select_stats(mz_handle* h, int G, int32_t* fast, int32_t* walked);
 
 /* Measurement: with mz_debug_enable(h, 2) every network launch of the
  * ResNet search (mz_rsearch_nets, its dominant kernel), with flag 4 every
- * learner unroll launch (mz_runroll_kernel, mz_learn_multi*), is bracketed by HIP events on
+ * learner unroll launch (mz_runroll_*, mz_learn_multi*), is bracketed by HIP events on
  * its stream; this returns the summed duration and the launch count since
  * the previous call, and resets them.                                      */
 int mz_debug_kernel_time(mz_handle* h, double* total_ms, int* launches);

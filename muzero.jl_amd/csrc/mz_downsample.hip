@@ -2,7 +2,7 @@
 // (ResNetHP.downsample, src/Learning.jl:175-187) for BASELINE configs[4]
 // (84x84x4 observations): one workgroup per item runs every layer of the
 // DsPlan with the activations in LDS; the result (6, 6, 2C) goes to HBM,
-// where the representation's tail (mz_rsearch_root / mz_runroll_kernel /
+// where the representation's tail (mz_rsearch_root / mz_runroll_chain1 /
 // mz_rnet_forward_kernel) reads it as its input.  The 3x3 convs run one
 // thread per output position with compile-time taps (ds_conv3).
 //

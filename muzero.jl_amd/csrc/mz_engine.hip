@@ -89,10 +89,9 @@ struct mz_handle {
     std::vector<RPlan> rplan;               // [3]
     RPlan* d_rplan = nullptr;               // [3]
     int rn_ng = 0;
-    // the learner unroll's chain (mz_runroll_chain): the same nets on narrow tiles
+    // the learner unroll's chain (mz_runroll_chain1 / _chain_r): the same nets on narrow (one-sample) tiles
     std::vector<RPlan> rplan_l;
     RPlan* d_rplan_l = nullptr;
-    int rn_ng_l = 0;
     size_t rn_lds_l = 0;
     size_t rn_lds[3] = {0, 0, 0};
     float bn_s = 1.0f;
@@ -102,11 +101,10 @@ struct mz_handle {
     float* d_rhs = nullptr;                 // [bcap][K][H] learner unroll scratch (h between the nets)
     float* d_rts = nullptr;                 // [bcap][K][H] dynamics trunk outputs (the reward heads' input)
     int rn_dyn_split = 0;                   // first reward-head layer of the dynamics plan
-    bool rd_chain = false;                  // the chain runs as mz_runroll_chain_r[3] (rd_chain_ok)
-    int rd_nb = 1;                          // its column blocks (1: mz_runroll_chain_r, 3: _r3)
+    bool rd_chain = false;                  // the chain runs as mz_runroll_chain_r (rd_chain_ok)
     bool rp_pred = false;                   // one-item predictions run as mz_runroll_pred_r (rp_pred_ok)
     unsigned long long* d_prog = nullptr;   // [bcap] mz_runroll_fused_r progress words
-    float* d_rtrunk = nullptr;              // [max_games][H] dynamics trunk outputs (mz_rsearch_nets rew_split)
+    float* d_rtrunk = nullptr;              // [max_games][H] dynamics trunk outputs (mz_rsearch_nets)
     unsigned long long* d_tprog = nullptr;  // [tiles] their publish words
     unsigned long long tprog_epoch = 0;     // mz_rsearch_nets launches
     float* d_chx = nullptr;                 // [MZ_MULTI_MAX][hx_n] mz_learn_chain helpers' θ (ChainParams::hx)
@@ -940,31 +938,30 @@ static void rn_otab_fill(std::vector<int>& t, const RLayer& L, int NG, int W, in
                     }
 }
 
-// mz_runroll_chain_r[3] applies when the dynamics chain ([0, dyn_split)) is
-// RD_NL (one column block) or RD_NL3 (three column blocks) 1x1 conv layers of
-// 64 channels with BatchNorm + relu: layer 0 on the plain input with 4 < nq <=
-// 8 (nf + 1 channels: two A chunks), the others K = 64 on k-blocked inputs
+// mz_runroll_chain_r applies when the plane is one column block (the narrow
+// tiles are one sample wide) and the dynamics chain ([0, dyn_split)) is RD_NL
+// 1x1 conv layers of 64 channels with BatchNorm + relu: layer 0 on the plain
+// input with 4 < nq <= 8 (nf + 1 channels: two A chunks), the others K = 64 on
+// k-blocked inputs.  (A three-block variant for 4-block towers, 18 layers, kept
+// 304 VGPRs resident and spilled: 1.27k vs 1.53k learner steps/s on Connect4
+// ResNet-8; it was removed.)
 static size_t rd_chain_lds(const mz_handle* h) { return h->rn_lds_l + (size_t)h->rn_dyn_split * 64 * 16; }
-static int rd_chain_ok(const mz_handle* h) {          // the column blocks, or 0
+static bool rd_chain_ok(const mz_handle* h) {
     const RPlan& R = h->rplan_l[MZ_NET_DYN];
-    const int nb = (h->plane * h->rn_ng_l + 15) / 16;
-    // (three blocks / 18 layers: 304 resident VGPRs, the kernel spills — measured 1.27k vs 1.53k learner
-    // steps/s on Connect4 ResNet-8 — so only on request, MZ_RN_RD3=1)
-    static const bool rd3 = std::getenv("MZ_RN_RD3") != nullptr;
-    if (!((nb == 1 && h->rn_dyn_split == RD_NL) || (rd3 && nb == 3 && h->rn_dyn_split == RD_NL3))) return 0;
+    if ((h->plane + 15) / 16 != 1 || h->rn_dyn_split != RD_NL) return false;
     for (int i = 0; i < h->rn_dyn_split; ++i) {
         const RLayer& L = R.L[i];
-        if (L.kk != 1 || L.cout != 64 || L.n_ob != 4 || !L.spatial || !L.bn || L.act != MZ_ACT_RELU) return 0;
-        if (i == 0 ? (L.in_kb || L.nq <= 4 || L.nq > 8) : (!L.in_kb || L.K != 64 || L.nq != 4)) return 0;
+        if (L.kk != 1 || L.cout != 64 || L.n_ob != 4 || !L.spatial || !L.bn || L.act != MZ_ACT_RELU) return false;
+        if (i == 0 ? (L.in_kb || L.nq <= 4 || L.nq > 8) : (!L.in_kb || L.K != 64 || L.nq != 4)) return false;
     }
-    return rd_chain_lds(h) <= kLdsMax ? nb : 0;
+    return rd_chain_lds(h) <= kLdsMax;
 }
 // mz_runroll_pred_r applies when the prediction trunk ([0, RP_NL), the
 // first head layer next) is RP_NL such layers, all on k-blocked inputs
 static size_t rp_pred_lds(const mz_handle* h) { return h->rn_lds_l + (size_t)RP_NL * 64 * 16; }
 static bool rp_pred_ok(const mz_handle* h) {
     const RPlan& R = h->rplan_l[MZ_NET_PRED];
-    if ((h->plane * h->rn_ng_l + 15) / 16 != 1 || R.n <= RP_NL || R.L[RP_NL].cout == 64) return false;
+    if ((h->plane + 15) / 16 != 1 || R.n <= RP_NL || R.L[RP_NL].cout == 64) return false;
     if (2 * h->rhp.num_blocks + 1 != RP_NL) return false;
     for (int i = 0; i < RP_NL; ++i) {
         const RLayer& L = R.L[i];
@@ -1381,11 +1378,8 @@ int mz_engine_create_resnet(const mz_config* conf, const mz_resnet_hp* hyper, in
     h->rn_dyn_split = (int)sp[MZ_NET_DYN].size();     // the reward head: the dynamics layers of chain 2
     for (size_t i = 0; i < sp[MZ_NET_DYN].size(); ++i)
         if (sp[MZ_NET_DYN][i].chain == 2) { h->rn_dyn_split = (int)i; break; }
-    {   // learner chain tiles: MZ_RN_NG_LEARN (power of two), default 1 (tools/rn_learner_ab.sh)
-        const char* e = std::getenv("MZ_RN_NG_LEARN");
-        int ngl = e ? std::atoi(e) : 1;
-        if (ngl < 1 || ngl > h->rn_ng || (ngl & (ngl - 1))) ngl = 1;
-        h->rn_ng_l = ngl;
+    {   // learner chain tiles: one sample wide
+        const int ngl = 1;
         int wl = 0;
         h->rplan_l.resize(3);
         for (int n = 0; n < 3; ++n) {
@@ -1396,9 +1390,8 @@ int mz_engine_create_resnet(const mz_config* conf, const mz_resnet_hp* hyper, in
             CK(h->rplan_l[n].n < 0 ? fail(h, "ResNet plan: a k-blocked output buffer") : 0);
             h->rn_lds_l = std::max(h->rn_lds_l, (size_t)h->rplan_l[n].lds_floats * 4);
         }
-        h->rd_nb = rd_chain_ok(h);
-        h->rd_chain = h->rd_nb > 0 && !std::getenv("MZ_RN_NO_RD");
-        h->rp_pred = rp_pred_ok(h) && !std::getenv("MZ_RN_NO_RD");
+        h->rd_chain = rd_chain_ok(h);
+        h->rp_pred = rp_pred_ok(h);
     }
     h->inv_tile.assign(h->nflat, -1);
     for (size_t i = 0; i < sw.size(); ++i) if (sw[i] >= 0) h->inv_tile[(size_t)sw[i]] = (int)i;
@@ -1447,26 +1440,19 @@ int mz_engine_create_resnet(const mz_config* conf, const mz_resnet_hp* hyper, in
                ? 0 : fail(h, "copy"));
         CK(al(&h->d_dsout, (size_t)max_games * h->rin_feat));
     }
-    CK(hipFuncSetAttribute((const void*)mz_runroll_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                           (int)lmax) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute(runroll)"));
     CK(hipFuncSetAttribute((const void*)mz_runroll_pred, hipFuncAttributeMaxDynamicSharedMemorySize,
                            (int)lmax) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute(runroll_pred)"));
-    for (const void* k : {(const void*)mz_runroll_pred_n, (const void*)mz_runroll_pred_n1,
-                          (const void*)mz_runroll_chain1})
+    for (const void* k : {(const void*)mz_runroll_pred_n1, (const void*)mz_runroll_chain1})
         CK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->rn_lds_l) == hipSuccess
                ? 0 : fail(h, "hipFuncSetAttribute(runroll narrow)"));
-    CK(hipFuncSetAttribute((const void*)mz_runroll_chain, hipFuncAttributeMaxDynamicSharedMemorySize,
-                           (int)h->rn_lds_l) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute(runroll_chain)"));
     if (h->rd_chain)
-        CK(hipFuncSetAttribute(h->rd_nb == 3 ? (const void*)mz_runroll_chain_r3 : (const void*)mz_runroll_chain_r,
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
+        CK(hipFuncSetAttribute((const void*)mz_runroll_chain_r, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)rd_chain_lds(h)) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute(runroll_chain_r)"));
     if (h->rp_pred)
         CK(hipFuncSetAttribute((const void*)mz_runroll_pred_r, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)rp_pred_lds(h)) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute(runroll_pred_r)"));
     if (h->rd_chain && h->rp_pred)
-        CK(hipFuncSetAttribute(h->rd_nb == 3 ? (const void*)mz_runroll_fused_r3 : (const void*)mz_runroll_fused_r,
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
+        CK(hipFuncSetAttribute((const void*)mz_runroll_fused_r, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)std::max(rd_chain_lds(h), rp_pred_lds(h))) == hipSuccess
                ? 0 : fail(h, "hipFuncSetAttribute(runroll_fused_r)"));
     CK(hipFuncSetAttribute((const void*)mz_rsearch_nets, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1810,20 +1796,17 @@ static int rsearch(mz_handle* h, int G, const float* obs, const uint8_t* legal_m
     void* args[] = {&P};
     const int gw = h->A > 16 ? 32 : 16;             // lanes per game in the tree kernels
     const unsigned tiles = (unsigned)((G + P.ng - 1) / P.ng), groups = (unsigned)((G + 256 / gw - 1) / (256 / gw));
-    // the dynamics reward head on the prediction workgroup (RSearchParams.rew_split)
-    static const bool no_rsplit = std::getenv("MZ_RN_NO_RSPLIT") != nullptr;
-    if (!no_rsplit && !h->d_rtrunk) {
+    // the dynamics reward head on the prediction workgroup (mz_rsearch_nets): its trunk hand-off
+    if (!h->d_rtrunk) {
         const size_t mt = (size_t)(h->max_games + P.ng - 1) / P.ng;
         MZ_TRY(h, dalloc(h, &h->d_rtrunk, (size_t)h->max_games * h->H));
         MZ_TRY(h, dalloc(h, &h->d_tprog, mt));
         MZ_TRY(h, hipMemset(h->d_tprog, 0, mt * sizeof(unsigned long long)));
     }
-    P.rew_split = no_rsplit ? 0 : 1;
     P.trunk_nl = 1 + 2 * h->rhp.num_blocks; P.dyn_split = h->rn_dyn_split;
     P.trunk = h->d_rtrunk; P.tprog = h->d_tprog;
     P.fault = h->d_fault; P.poll_ticks = h->poll_ticks; P.dbg_skip = h->dbg_skip;
-    static const bool no_moved_skip = std::getenv("MZ_NO_MOVED_SKIP") != nullptr;   // A/B only
-    P.no_moved_skip = no_moved_skip ? 1 : 0;
+    P.no_moved_skip = 0;
     const void* kroot = gw == 32 ? (const void*)mz_rsearch_root32 : (const void*)mz_rsearch_root;
     // tree step: LDS-cached (one wave per 64/gw games) unless the tree exceeds the LDS
     const bool tl = h->rtree_lds != 0;
@@ -2088,19 +2071,13 @@ static const void* small_kernel(const mz_handle* h, int family, int ti) {
 static size_t runroll_lds(const mz_handle* h) {
     return std::max(h->rn_lds[0], std::max(h->rn_lds[1], h->rn_lds[2]));
 }
-// MZ_RUNROLL_FUSED=1: the one-kernel unroll (mz_runroll_kernel, one step per call only); read once, so the
-// value is fixed at the first learner call of the process
-static bool runroll_one_kernel() {
-    static const bool on = std::getenv("MZ_RUNROLL_FUSED") != nullptr;
-    return on;
-}
 // the parameters every unroll launch of the engine shares; the caller adds its batch, read-outs,
 // scratch and parameter images (and the ms_* strides of a multi-step launch)
 static void runroll_params(const mz_handle* h, int B, RUnrollParams& U) {   // (filled in place: no copy)
     std::memset(&U, 0, sizeof(U));                 // (ms = 0: one step; the fused-ADAM fields unused unless set)
     U.B = B; U.K = h->conf.num_unroll_steps; U.A = h->A; U.H = h->H;
     U.W = h->rconf.observation_shape[0]; U.P = h->plane; U.obs_feat = h->rin_feat; U.ng = h->rn_ng; U.bn_s = h->bn_s;
-    U.plans = h->d_rplan; U.plans_l = h->d_rplan_l; U.ng_l = h->rn_ng_l;
+    U.plans = h->d_rplan; U.plans_l = h->d_rplan_l; U.ng_l = 1;
     U.dyn_split = h->rn_dyn_split; U.otab = h->d_rtab;
 }
 // Launch the unroll of U: one step (steps = 0: U.ms = 0, grid z = 1) or `steps` steps on gridDim.z.
@@ -2119,18 +2096,12 @@ static int runroll_launch(mz_handle* h, RUnrollParams& U, int steps, hipStream_t
     // the B·K predictions on wide tiles (ng items) once they fill the chip
     // (B = 2048: 640 workgroups; one-item tiles there measured 2.4x slower),
     // else one-item tiles (B = 32: 160 workgroups instead of 10)
-    static const bool wide_env = std::getenv("MZ_RN_PRED_WIDE") != nullptr;
-    const bool one_kernel = !steps && runroll_one_kernel();
-    const bool wide_p = wide_env || (B * KH + U.ng - 1) / U.ng >= h->n_cu;
+    const bool wide_p = (B * KH + U.ng - 1) / U.ng >= h->n_cu;
     // one launch (mz_runroll_fused_r): the chain blocks, then the items, each
     // item waiting for its sample's chain instead of the whole launch; with
     // rq, each chain block also draws its sample (the get_batch launch folded in)
-    static const bool no_fuse = std::getenv("MZ_RN_NO_FUSE") != nullptr;
-    const bool fused = !one_kernel && h->rd_chain && h->rp_pred && !wide_p && !no_fuse && U.ng_l == 1 &&
-                       U.K + 1 < 64 && !h->ds && prog;
-    static const bool no_fuse_sample = std::getenv("MZ_RN_NO_FUSE_SAMPLE") != nullptr;   // A/B only
-    static const bool no_fuse_adam = std::getenv("MZ_RN_NO_FUSE_ADAM") != nullptr;       // A/B only
-    if (rq && (!fused || no_fuse_sample)) {
+    const bool fused = h->rd_chain && h->rp_pred && !wide_p && U.K + 1 < 64 && !h->ds && prog;
+    if (rq && !fused) {
         hipLaunchKernelGGL(mz_rp_sample, dim3((B + 3) / 4), dim3(256), 0, st, *rq);
         MZ_TRY(h, hipGetLastError());
     }
@@ -2144,67 +2115,51 @@ static int runroll_launch(mz_handle* h, RUnrollParams& U, int steps, hipStream_t
         U.fault = h->d_fault; U.poll_ticks = h->poll_ticks; U.dbg_skip = h->dbg_skip;
     }
     std::string& variant = h->last_lvariant;        // (assigned in place: no allocation per launch)
-    if (one_kernel) {          // the one-kernel unroll (pred inside the chain)
-        variant = "mz_runroll_kernel";
-        MZ_TRY(h, hipLaunchKernel((const void*)mz_runroll_kernel, dim3((B + U.ng - 1) / U.ng), dim3(RN_THREADS),
-                                  args, runroll_lds(h), st));
-    } else {                                        // chain on narrow tiles, then the B·K predictions
-        // units of one column block (the 1-block instances, a fifth of the code),
-        // also for wider tiles: a Connect4 1x1 conv of 4 row blocks x 3 column
-        // blocks then has 12 units for the 8 waves instead of 4 three-block ones
-        // (the same tiles, bit for bit; configs[3] learner 1.62 k -> 1.75 k
-        // steps/s, tools/gpu_r04d.sh).  MZ_RN_CHAIN_NB3=1: the three-block units
-        static const bool nb3 = std::getenv("MZ_RN_CHAIN_NB3") != nullptr;
-        const bool nb1 = (U.P * U.ng_l + 15) / 16 == 1 || !nb3;
-        U.rd_ep_off = (int)(h->rn_lds_l / 4);
-        U.rd_trunk_nl = 1 + 2 * h->rhp.num_blocks;
-        const unsigned nchain = (B + U.ng_l - 1) / U.ng_l, ny = U.K > 0 ? 2 : 1;
-        if (fused) {
-            U.prog = prog;
-            U.prog_base = (++*epoch) * 64ull;
-            U.n_chain = B;
-            U.fuse_sample = rq != nullptr && !no_fuse_sample;
-            if (rq) U.rq = *rq;
-            // ADAM beside the unroll: the launch reads the current image (d_Wp) and
-            // writes the updated one into d_Wp2, swapped after the launch
-            U.n_l2 = fuse_adam && h->d_Wp2 && !no_fuse_adam ? 96 : 0;
-            if (!steps) {
-                U.ad = LgAdam{1, h->d_m, h->d_v, h->bp1, h->bp2, eta, h->d_Wp2, h->d_Bp, h->d_inv_tile, nullptr,
-                              nullptr, h->d_inv_small};
-                U.flat_w = h->d_flat; U.netoff = h->d_netoff; U.part = h->d_sq;
-            }
-            if (l2_fused) *l2_fused = U.n_l2 > 0;
-            variant = h->rd_nb == 3 ? "mz_runroll_fused_r3" : "mz_runroll_fused_r";
-            const int nitems = B * KH * (U.K > 0 ? 3 : 2);
-            MZ_TRY(h, hipLaunchKernel(h->rd_nb == 3 ? (const void*)mz_runroll_fused_r3 : (const void*)mz_runroll_fused_r,
-                                      dim3(nz * (B + U.n_l2 + nitems)), dim3(RD_THREADS), args,
-                                      std::max(rd_chain_lds(h), rp_pred_lds(h)), st));
+    // chain on narrow (one-sample) tiles, then the B·K predictions.  The chain's units are one
+    // column block (the 1-block instances, a fifth of the code), also on planes of several
+    // blocks: a Connect4 1x1 conv of 4 row blocks x 3 column blocks then has 12 units for the
+    // 8 waves instead of 4 three-block ones (the same tiles, bit for bit; configs[3] learner
+    // 1.62 k -> 1.75 k steps/s, tools/gpu_r04d.sh)
+    U.rd_ep_off = (int)(h->rn_lds_l / 4);
+    U.rd_trunk_nl = 1 + 2 * h->rhp.num_blocks;
+    const unsigned ny = U.K > 0 ? 2 : 1;
+    if (fused) {
+        U.prog = prog;
+        U.prog_base = (++*epoch) * 64ull;
+        U.n_chain = B;
+        U.fuse_sample = rq != nullptr;
+        if (rq) U.rq = *rq;
+        // ADAM beside the unroll: the launch reads the current image (d_Wp) and
+        // writes the updated one into d_Wp2, swapped after the launch
+        U.n_l2 = fuse_adam && h->d_Wp2 ? 96 : 0;
+        if (!steps) {
+            U.ad = LgAdam{1, h->d_m, h->d_v, h->bp1, h->bp2, eta, h->d_Wp2, h->d_Bp, h->d_inv_tile, nullptr,
+                          nullptr, h->d_inv_small};
+            U.flat_w = h->d_flat; U.netoff = h->d_netoff; U.part = h->d_sq;
+        }
+        if (l2_fused) *l2_fused = U.n_l2 > 0;
+        variant = "mz_runroll_fused_r";
+        const int nitems = B * KH * (U.K > 0 ? 3 : 2);
+        MZ_TRY(h, hipLaunchKernel((const void*)mz_runroll_fused_r, dim3(nz * (B + U.n_l2 + nitems)),
+                                  dim3(RD_THREADS), args, std::max(rd_chain_lds(h), rp_pred_lds(h)), st));
+    } else {
+        variant = h->rd_chain ? "mz_runroll_chain_r" : "mz_runroll_chain1";
+        MZ_TRY(h, hipLaunchKernel(h->rd_chain ? (const void*)mz_runroll_chain_r : (const void*)mz_runroll_chain1,
+                                  dim3(B, 1, nz), dim3(h->rd_chain ? RD_THREADS : RN_THREADS), args,
+                                  h->rd_chain ? rd_chain_lds(h) : h->rn_lds_l, st));
+        // the B·K predictions and reward heads (wide_p above)
+        if (wide_p) {
+            variant += "+mz_runroll_pred";
+            MZ_TRY(h, hipLaunchKernel((const void*)mz_runroll_pred, dim3((B * KH + U.ng - 1) / U.ng, ny, nz),
+                                      dim3(RN_THREADS), args, runroll_lds(h), st));
+        } else if (h->rp_pred) {
+            variant += "+mz_runroll_pred_r";
+            MZ_TRY(h, hipLaunchKernel((const void*)mz_runroll_pred_r, dim3(B * KH, ny, nz), dim3(RD_THREADS), args,
+                                      rp_pred_lds(h), st));
         } else {
-            const void* kchain;
-            if (h->rd_chain) {
-                kchain = h->rd_nb == 3 ? (const void*)mz_runroll_chain_r3 : (const void*)mz_runroll_chain_r;
-                variant = h->rd_nb == 3 ? "mz_runroll_chain_r3" : "mz_runroll_chain_r";
-            } else {
-                kchain = nb1 ? (const void*)mz_runroll_chain1 : (const void*)mz_runroll_chain;
-                variant = nb1 ? "mz_runroll_chain1" : "mz_runroll_chain";
-            }
-            MZ_TRY(h, hipLaunchKernel(kchain, dim3(nchain, 1, nz), dim3(h->rd_chain ? RD_THREADS : RN_THREADS), args,
-                                      h->rd_chain ? rd_chain_lds(h) : h->rn_lds_l, st));
-            // the B·K predictions and reward heads (wide_p above)
-            if (wide_p) {
-                variant += "+mz_runroll_pred";
-                MZ_TRY(h, hipLaunchKernel((const void*)mz_runroll_pred, dim3((B * KH + U.ng - 1) / U.ng, ny, nz),
-                                          dim3(RN_THREADS), args, runroll_lds(h), st));
-            } else if (h->rp_pred) {
-                variant += "+mz_runroll_pred_r";
-                MZ_TRY(h, hipLaunchKernel((const void*)mz_runroll_pred_r, dim3((B * KH + U.ng_l - 1) / U.ng_l, ny, nz),
-                                          dim3(RD_THREADS), args, rp_pred_lds(h), st));
-            } else {
-                variant += nb1 ? "+mz_runroll_pred_n1" : "+mz_runroll_pred_n";
-                MZ_TRY(h, hipLaunchKernel(nb1 ? (const void*)mz_runroll_pred_n1 : (const void*)mz_runroll_pred_n,
-                                          dim3((B * KH + U.ng_l - 1) / U.ng_l, ny, nz), dim3(RN_THREADS), args,
-                                          h->rn_lds_l, st));
-            }
+            variant += "+mz_runroll_pred_n1";
+            MZ_TRY(h, hipLaunchKernel((const void*)mz_runroll_pred_n1, dim3(B * KH, ny, nz), dim3(RN_THREADS), args,
+                                      h->rn_lds_l, st));
         }
     }
     if (e1) MZ_TRY(h, hipEventRecord(e1, st));
@@ -2440,14 +2395,12 @@ static int build_bp(mz_handle* h) {
     // into the first levels (~70 units on 16 waves, serialised), ahead of the
     // dynamics chain they do not gate; ALAP spreads them along the chain.
     // Application c must precede a (a < c) when a produces c's input or adds
-    // into the same G[x] after it.  MZ_BP_ASAP=1 keeps the ASAP levels.
-    if (!std::getenv("MZ_BP_ASAP")) {
-        for (int c = 0; c < na; ++c) {
-            int l = nbl - 1;
-            for (int a = 0; a < c; ++a)
-                if (apps[c].x == apps[a].y || apps[c].x == apps[a].x) l = std::min(l, blv[a] - 1);
-            blv[c] = l;
-        }
+    // into the same G[x] after it.
+    for (int c = 0; c < na; ++c) {
+        int l = nbl - 1;
+        for (int a = 0; a < c; ++a)
+            if (apps[c].x == apps[a].y || apps[c].x == apps[a].x) l = std::min(l, blv[a] - 1);
+        blv[c] = l;
     }
     std::vector<int2> fun, bun;
     std::vector<int> flev, blev;
@@ -2924,8 +2877,7 @@ static int bp_grad(mz_handle* h, const mz_batch* b, float* grad_dev, float* loss
     Q.pv = h->d_pv; Q.pp = h->d_pp; Q.pr = h->d_pr;
     Q.n_flev = h->bp_n_flev; Q.n_blev = h->bp_n_blev; Q.n_funit = h->bp_n_funit; Q.n_bunit = h->bp_n_bunit;
     Q.fsync = h->d_bp_fsync; Q.bsync = h->d_bp_bsync; Q.cache_floats = h->bp_cache_floats; Q.obs_s = h->bp_obs_s;
-    static const bool no_warm = std::getenv("MZ_BP_NO_WARM") != nullptr;   // A/B only
-    Q.nflat = no_warm ? 0 : (int)h->nflat;
+    Q.nflat = (int)h->nflat;
     const size_t lv_lds = (size_t)Q.n_app * sizeof(BpApp) + (size_t)(Q.n_funit + Q.n_bunit) * sizeof(int2) +
                           (size_t)(2 * (Q.n_flev + Q.n_blev) + 8) * sizeof(int) + 16 + (size_t)Q.cache_floats * 4;
     Q.funits = h->d_bp_funits; Q.flev = h->d_bp_flev; Q.bunits = h->d_bp_bunits; Q.blev = h->d_bp_blev;
@@ -3627,7 +3579,7 @@ static int learner_sampled(mz_handle* h, int32_t B, uint32_t step, float* grad_d
     mz_batch b;
     const int ti = small_unroll_ti(h, B);
     const bool fused = train && ti >= 0 && !h->conf.PER && h->A <= 16 && h->d_sm_w2 && h->kind != 1 &&
-                       h->learn_mode != MZ_LEARN_CORRECTED && !std::getenv("MZ_LEARN_2LAUNCH");
+                       h->learn_mode != MZ_LEARN_CORRECTED;
     const bool pf = fused && !std::getenv("MZ_NO_BATCH_PREFETCH");
     if (rs_params(h, B, step, st, &Q, &b, pf)) return -1;
     if (ensure_batch(h, B)) return -1;
@@ -3677,15 +3629,11 @@ static int learner_sampled(mz_handle* h, int32_t B, uint32_t step, float* grad_d
         L.out = losses_dev ? losses_dev : h->d_loss;
         L.ad = LgAdam{1, h->d_m, h->d_v, h->bp1, h->bp2, eta, h->d_Wp2, h->d_Bp2, h->d_inv_tile, h->d_sm_w2,
                       h->d_sm_bias2, h->d_inv_small};
-        // MZ_LEARN_XCD=1: the unroll workgroups on one XCD (their weight image fetched into one L2):
-        // PMC 3.79 MB per launch instead of 6.41 MB, but 31.4 k instead of 33.9 k steps/s (the 8·nU
-        // grid and one L2 serving 32 workgroups; tools/ab_learn_xcd.sh, tools/pmc_learn_xcd.sh)
-        const int roles = L.nU + LEARN_L2_GROUPS + L.pf_nb;
-        static const bool xcd = std::getenv("MZ_LEARN_XCD") != nullptr;
-        L.xcd = xcd && L.nU <= h->n_cu / 8 && 8 * L.nU >= roles;
+        // (the unroll workgroups on one XCD, their weight image fetched into one L2, measured PMC
+        // 3.79 MB per launch instead of 6.41 MB, but 31.4 k instead of 33.9 k steps/s: not kept)
         void* args[] = {&U, &L};
-        MZ_TRY(h, hipLaunchKernel(small_kernel(h, SMK_LEARN, ti), dim3(L.xcd ? 8 * L.nU : roles), dim3(SM_THREADS),
-                                  args, unroll_small_lds(h, ti), st));
+        MZ_TRY(h, hipLaunchKernel(small_kernel(h, SMK_LEARN, ti), dim3(L.nU + LEARN_L2_GROUPS + L.pf_nb),
+                                  dim3(SM_THREADS), args, unroll_small_lds(h, ti), st));
         if (pf) h->pf_cur = 1 - cur;
         h->last_lvariant = ti == 0 ? "mz_learn_small1" : "mz_learn_small2";
         std::swap(h->d_Wp, h->d_Wp2); std::swap(h->d_Bp, h->d_Bp2);
@@ -3788,37 +3736,27 @@ int mz_learner_train_dev(mz_handle* h, int32_t B, uint32_t step, double eta, flo
 // sub-chunk's chain on a second stream, ordered by events, beside the unroll
 // launch — 228.8 k vs 279.5 k steps/s at L = 64, 114.6 k vs ~170 k at L = 8:
 // the cross-stream event waits cost more than the chain they hide.)
-static bool no_multi() { return std::getenv("MZ_NO_MULTI") != nullptr; }
-static int multi_ls_env() {
-    static const int ls = std::getenv("MZ_MULTI_LS") ? std::atoi(std::getenv("MZ_MULTI_LS")) : 0;
-    return ls;
-}
 static bool multi_ok(const mz_handle* h) {
     return h->kind == 0 && h->learn_mode == MZ_LEARN_REF_SEMANTICS && !h->conf.PER && h->small_ok && h->A <= 16 &&
-           h->d_sm_w2 && !no_multi();
+           h->d_sm_w2;
 }
 // Sub-chunk length Ls and T per workgroup for L steps of B samples: one sample
 // per workgroup while the L·B workgroups fit one per CU; else two, with as
 // many steps per sub-chunk as keep one workgroup per CU (16 at B = 32)
 static int multi_plan(const mz_handle* h, int B, int L, int* Ls) {
-    static const int force = std::getenv("MZ_MULTI_T") ? std::atoi(std::getenv("MZ_MULTI_T")) : 0;   // tests / A/B
-    const int ls_env = multi_ls_env();
     int ti;
     // T = 4 (round 6) when the call has the steps to fill the chip with 4 samples per workgroup
     // (twice the steps per unroll launch as T = 2 for about 1.1x a stage's cost); T = 2 when L·B
     // exceeds the CUs; T = 1 below
     const int nU4 = (B + 3) / 4;
-    if ((force == 1 || force == 2 || force == 4) && small_unroll_fits(h, force == 4 ? 2 : force - 1))
-        ti = force == 4 ? 2 : force - 1;
-    else if (!force && (size_t)L * B <= (size_t)h->n_cu && small_unroll_fits(h, 0)) ti = 0;
-    else if (!force && L >= std::min(MZ_MULTI_MAX, h->n_cu / nU4) && (size_t)L * nU4 >= (size_t)h->n_cu &&
-             small_unroll_fits(h, 2) && !std::getenv("MZ_MULTI_NO_T4")) ti = 2;
+    if ((size_t)L * B <= (size_t)h->n_cu && small_unroll_fits(h, 0)) ti = 0;
+    else if (L >= std::min(MZ_MULTI_MAX, h->n_cu / nU4) && (size_t)L * nU4 >= (size_t)h->n_cu &&
+             small_unroll_fits(h, 2)) ti = 2;
     else if (small_unroll_fits(h, 1)) ti = 1;
     else if (small_unroll_fits(h, 0)) ti = 0;
     else return -1;
     const int T = ti == 2 ? 4 : ti + 1, nU = (B + T - 1) / T;
-    int ls = std::max(1, std::min(ti == 2 ? MZ_MULTI_MAX : MZ_MULTI_UNROLL, h->n_cu / nU));
-    if (ls_env > 0) ls = std::min(MZ_MULTI_MAX, ls_env);          // (A/B: more than one workgroup per CU)
+    const int ls = std::max(1, std::min(ti == 2 ? MZ_MULTI_MAX : MZ_MULTI_UNROLL, h->n_cu / nU));
     *Ls = std::min(ls, L);
     return ti;
 }
@@ -3895,8 +3833,7 @@ static int ensure_multi(mz_handle* h, int B, int L) {
 // form with the steps on gridDim.z (the fused form: step-major chain blocks, then the items;
 // RUnrollParams.ms) and one loss launch of Ls·nlb blocks
 static bool rmulti_ok(const mz_handle* h) {
-    return h->kind == 1 && h->learn_mode == MZ_LEARN_REF_SEMANTICS && !h->conf.PER && !no_multi() &&
-           !runroll_one_kernel();
+    return h->kind == 1 && h->learn_mode == MZ_LEARN_REF_SEMANTICS && !h->conf.PER;
 }
 static int ensure_multi(mz_handle* h, int B, int L);
 // θ after up to two given steps, copied out by the chain launch that computes them (mz_train_run:
@@ -3908,10 +3845,9 @@ struct MultiCap {
     bool* imaged0;                                  // set when a chain launch wrote them
 };
 // mz_learn_chain's helper workgroups (ChainParams::nh) for the nets with more parameters than one pass
-// of the slices (MZ_CHAIN_HELP=0: off, A/B).  Measured (tools/gpu_r06t.sh): FC 32.1 -> 24.8 us per
+// of the slices.  Measured against none (tools/gpu_r06t.sh): FC 32.1 -> 24.8 us per
 // 32-step chain, ResNet configs[2] 63.3 -> 44.2 us.  Returns the helper count.
 static int chain_helpers(mz_handle* h, ChainParams& C) {
-    static const char* env = std::getenv("MZ_CHAIN_HELP");
     const size_t stride = (size_t)MZ_L2_BLOCKS * MZ_THREADS;
     int nht = 0;
     size_t hx_n = 0;
@@ -3922,11 +3858,7 @@ static int chain_helpers(mz_handle* h, ChainParams& C) {
         hx_n += c > stride ? c : 0;
         nht += C.nh[n];
     }
-    const bool on = nht > 0 && (!env || std::atoi(env) != 0);
-    if (!on) {
-        C.nh[0] = C.nh[1] = C.nh[2] = 0;
-        return 0;
-    }
+    if (!nht) return 0;
     if (!h->d_chcnt) {
         MZ_TRY(h, dalloc(h, &h->d_chx, (size_t)MZ_MULTI_MAX * hx_n));
         MZ_TRY(h, dalloc(h, &h->d_chcnt, (size_t)3 * MZ_L2_BLOCKS));
@@ -4028,8 +3960,7 @@ static int rlearner_multi(mz_handle* h, int32_t B, uint32_t step0, int32_t L, co
     mz_batch b;
     if (rs_params(h, B, step0, st, &Q, &b, true)) return -1;
     if (ensure_batch(h, B) || ensure_multi(h, B, L)) return -1;
-    const int ls_env = multi_ls_env();
-    const int Ls = std::min(L, ls_env > 0 ? std::min(MZ_MULTI_UNROLL, ls_env) : MZ_MULTI_UNROLL);
+    const int Ls = std::min(L, MZ_MULTI_UNROLL);
     const int K = h->conf.num_unroll_steps, KH = std::max(K, 1), A = h->A;
     const size_t K1 = (size_t)K + 1;
     const MultiStrides S = {B, (size_t)B * h->obs_feat, (size_t)B * K1, (size_t)B * K1 * A};
@@ -4110,17 +4041,15 @@ static int learner_multi(mz_handle* h, int32_t B, uint32_t step0, int32_t L, con
     const MultiStrides S = {B, (size_t)B * h->obs_feat, (size_t)B * K1, (size_t)B * K1 * A};
     Q.obs = h->d_ml_obs; Q.actions = h->d_ml_act; Q.tv = h->d_ml_tv; Q.tr = h->d_ml_tr; Q.tpol = h->d_ml_tp;
     Q.gscale = h->d_ml_gs; Q.index = h->d_ml_index;
-    static const bool chain_sample = std::getenv("MZ_MULTI_CHAIN_SAMPLE") != nullptr;   // A/B
     SmallUnrollParams U;
     if (small_unroll_params(h, &b, ti, nullptr, &U)) return -1;
     const int T = ti == 2 ? 4 : ti + 1, nU = (B + T - 1) / T;
-    static const bool no_xcd = std::getenv("MZ_MULTI_NO_XCD") != nullptr;
     auto body = [&](int c0, int j0, int n, int ir, const RpSampleParams& Qk, const ChainParams& C) -> int {
         const int i0 = c0 + j0;
         LearnMultiParams M;
         std::memset(&M, 0, sizeof(M));
         M.L = n; M.nU = nU;
-        M.xcd = !no_xcd && n > 1;
+        M.xcd = n > 1;
         M.bank_w = C.bank_w + (size_t)j0 * h->sm_w_n; M.bank_b = C.bank_b + (size_t)j0 * h->sm_b_n;
         M.bws = h->sm_w_n; M.bbs = h->sm_b_n;
         M.s_obs = S.s_obs; M.s_k1 = S.s_k1; M.s_tp = S.s_tp;
@@ -4131,7 +4060,7 @@ static int learner_multi(mz_handle* h, int32_t B, uint32_t step0, int32_t L, con
         M.counter = h->d_ml_cnt + (size_t)ir * MZ_MULTI_CNT_STRIDE;
         M.out = losses_dev ? losses_dev + 8 * i0 : h->d_ml_out + 8 * ir;
         M.out_last = i0 + n == L ? out_last : nullptr;
-        M.sample = chain_sample ? 0 : 1;
+        M.sample = 1;                               // (each step's get_batch in its unroll workgroups)
         M.q = Qk;
         const int grid = M.xcd ? 8 * ((n + 7) / 8) * nU : n * nU;
         void* args[] = {&U, &M};
@@ -4145,7 +4074,7 @@ static int learner_multi(mz_handle* h, int32_t B, uint32_t step0, int32_t L, con
         if (e1) MZ_TRY(h, hipEventRecord(e1, st));
         return 0;
     };
-    if (multi_drive(h, step0, L, Ls, eta, theta_dev, st, cap, Q, S, chain_sample, body)) return -1;
+    if (multi_drive(h, step0, L, Ls, eta, theta_dev, st, cap, Q, S, false, body)) return -1;
     h->last_lvariant = ti == 0 ? "mz_learn_chain+mz_learn_multi1"
                      : ti == 1 ? "mz_learn_chain+mz_learn_multi2" : "mz_learn_chain+mz_learn_multi4";
     return 0;
@@ -4639,23 +4568,14 @@ static int train_move(mz_handle* h, uint32_t move, uint32_t game_offset, int64_t
     h->sp_latch = false;
     wset_swap(h, h->tr_actor);
     if (rc) return rc;
-    static const bool copy_sync = std::getenv("MZ_TRAIN_SYNC") != nullptr;   // A/B: round 6's copies + sync
-    if (copy_sync) {
-        if (rean && train_rean_rounds(h, move, game_offset, st)) return -1;
-        MZ_TRY(h, hipMemcpyAsync(h->h_tr_cnt, h->d_sp_counters, sizeof(long long), hipMemcpyDeviceToHost, st));
-        h->h_tr_cnt[1] = 0;
-        if (h->d_fault) MZ_TRY(h, hipMemcpyAsync(h->h_tr_cnt + 1, h->d_fault, 4, hipMemcpyDeviceToHost, st));
-        MZ_TRY(h, hipStreamSynchronize(st));
-    } else {
-        const long long seq = ++h->tr_pub_seq;
-        hipLaunchKernelGGL(mz_tr_publish, dim3(1), dim3(64), 0, st, (const long long*)h->d_sp_counters,
-                           (const unsigned*)h->d_fault, h->h_tr_pub, seq);
-        MZ_TRY(h, hipGetLastError());
-        if (rean && train_rean_rounds(h, move, game_offset, st)) return -1;
-        if (tr_wait_publish(h, seq, st)) return -1;
-        h->h_tr_cnt[0] = h->h_tr_pub[0];
-        h->h_tr_cnt[1] = h->h_tr_pub[1];
-    }
+    const long long seq = ++h->tr_pub_seq;
+    hipLaunchKernelGGL(mz_tr_publish, dim3(1), dim3(64), 0, st, (const long long*)h->d_sp_counters,
+                       (const unsigned*)h->d_fault, h->h_tr_pub, seq);
+    MZ_TRY(h, hipGetLastError());
+    if (rean && train_rean_rounds(h, move, game_offset, st)) return -1;
+    if (tr_wait_publish(h, seq, st)) return -1;
+    h->h_tr_cnt[0] = h->h_tr_pub[0];
+    h->h_tr_cnt[1] = h->h_tr_pub[1];
     if (h->h_tr_cnt[1] && check_fault(h)) return -1;
     *nfin = h->h_tr_cnt[0] - h->tr_games;
     h->tr_games = h->h_tr_cnt[0];
@@ -4681,18 +4601,15 @@ static int train_refresh(mz_handle* h, int64_t t, hipStream_t st) {
 // 2. `nreq` learner steps while t <= training_steps (Learning.jl:327), get_batch keyed by
 //    the step number, eta = Cos(step); every checkpoint_interval steps (t % ci == 0, t > 1)
 //    an actor refresh.  Round 6: the steps of one call run as ONE mz_learner_train_multi_dev
-//    chunk across the refresh points (up to 256 steps per call; MZ_TRAIN_L caps it): nothing
+//    chunk across the refresh points (up to 256 steps per call): nothing
 //    reads the actors' or the queued nets between two learner steps of one move, so only
 //    the sets after the last refresh matter — θ of the last refresh step is queued, θ of the
 //    one before it (or, with one refresh, the previously queued nets) goes to the actors, and
 //    the chain launch that computes those θ copies them out (MultiCap).  With periodic
-//    checkpoint files (networks_path) or MZ_TRAIN_PER_REFRESH=1 the chunks end at every
+//    checkpoint files (networks_path) the chunks end at every
 //    refresh step as in round 5 (the checkpoint writes the learner's nets of that step).
 static int train_learn(mz_handle* h, int64_t nreq, float* losses_dev, hipStream_t st, int64_t* done) {
-    static const int chunk_env = std::getenv("MZ_TRAIN_L") ? std::atoi(std::getenv("MZ_TRAIN_L")) : 0;
-    static const bool per_refresh_env = std::getenv("MZ_TRAIN_PER_REFRESH") != nullptr;
-    const int chunk_max = std::max(1, std::min(MZ_MULTI_LMAX, chunk_env > 0 ? chunk_env : MZ_MULTI_LMAX));
-    const bool per_refresh = per_refresh_env || !h->tr_ckpt_path.empty();
+    const bool per_refresh = !h->tr_ckpt_path.empty();
     const int64_t ci = h->conf.checkpoint_interval;
     auto is_refresh = [&](int64_t t) { return t % ci == 0 && t > 1; };
     const int64_t n_all = std::max<int64_t>(0, std::min<int64_t>(nreq, (int64_t)h->conf.training_steps + 1 - h->tr_t));
@@ -4701,8 +4618,7 @@ static int train_learn(mz_handle* h, int64_t nreq, float* losses_dev, hipStream_
     // the actors' set: θ of the next-to-last refresh step, its search images written by the chain launch
     // that computes it (else repacked after the call)
     bool imaged = false;
-    static const bool no_cap_img = std::getenv("MZ_TRAIN_REPACK") != nullptr;   // A/B
-    MultiCap cap{{-1, -1}, {h->tr_actor.flat, h->d_tr_queued}, no_cap_img ? nullptr : &h->tr_actor, &imaged};
+    MultiCap cap{{-1, -1}, {h->tr_actor.flat, h->d_tr_queued}, &h->tr_actor, &imaged};
     int64_t nref = 0;
     if (!per_refresh) {
         // the refresh steps in (t, t + n]: the last two
@@ -4720,7 +4636,7 @@ static int train_learn(mz_handle* h, int64_t nreq, float* losses_dev, hipStream_
     double eta[MZ_MULTI_LMAX];
     for (int64_t k = 0; k < n_all;) {
         const int64_t t0 = h->tr_t + 1;
-        int64_t n = std::min<int64_t>(n_all - k, chunk_max);
+        int64_t n = std::min<int64_t>(n_all - k, MZ_MULTI_LMAX);
         if (per_refresh) {                                 // the chunk ends at the next refresh step
             int64_t tb = (t0 + ci - 1) / ci * ci;
             if (tb <= 1) tb += ci;

@@ -1260,18 +1260,14 @@ extern "C" __global__ __launch_bounds__(64 * RT_WAVES) void mz_rsearch_tree_lds3
     rsearch_tree_lds_body<32>(P);
 }
 
-// Networks of simulation s: blockIdx.y = 0 prediction(parent h), 1 dynamics
-// (2h ⊕ a/|A|, Q1) writing h' into hidden slot s+1.  With P.rew_split the
-// dynamics is y = 0 (the producer, dispatched first: no consumer can occupy
-// the CU its producer needs) and the prediction workgroup of the tile runs the
-// dynamics reward head after its own heads, on the published trunk output.
+// Networks of simulation s: blockIdx.y = 0 dynamics (2h ⊕ a/|A|, Q1) writing
+// h' into hidden slot s+1 (the producer, dispatched first: no consumer can
+// occupy the CU its producer needs), 1 prediction(parent h); the prediction
+// workgroup of the tile runs the dynamics reward head after its own heads, on
+// the published trunk output.
 extern "C" __global__ __launch_bounds__(RN_THREADS_NETS) void mz_rsearch_nets(RSearchParams P) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const bool split = P.rew_split != 0;
-    const int net = (blockIdx.y == 0) != split ? MZ_NET_PRED : MZ_NET_DYN;
-#ifdef RN_DIAG_ONLY          // diagnostic builds (wrong results): time one net alone
-    if ((int)blockIdx.y != RN_DIAG_ONLY) return;
-#endif
+    const int net = blockIdx.y == 0 ? MZ_NET_DYN : MZ_NET_PRED;
     const RPlan& R = P.plans[net];
     const int NG = P.ng, t0 = blockIdx.x * NG, H = P.H, S = P.S;
     unsigned long long* st = nullptr;
@@ -1322,81 +1318,63 @@ extern "C" __global__ __launch_bounds__(RN_THREADS_NETS) void mz_rsearch_nets(RS
     // the k-table path is left out of this kernel (registers: the 12-wave cap)
     // (the PF prefetch set does not fit the 12-wave register budget: 200 spilled VGPRs, and an A-only
     // prefetch into the layer's own registers measured 76 vs 70 µs)
-    if (split) {
-        if (net == MZ_NET_DYN) {
-            rn_run<false, false, 3, false, true, true>(R, P.Wimg, P.flat, lds, NG, P.W, P.P, P.bn_s, st, 0, P.trunk_nl);
-            const RLayer Ls = rn_layer_at(R, P.dyn_split);             // the reward head's input: the trunk output
-            if ((H & 3) == 0) {                                         // 16-byte sc1 pieces (rn_st_sc1)
-                const auto rs = __builtin_amdgcn_make_buffer_rsrc(P.trunk, (short)0, P.G * H * 4, 0x00020000);
-                rn_unstage_rows(lds + Ls.in_off, Ls.in_kb, NG, P.P, H, t0, P.G, [&](int g, int q, float4 v) {
-                    rn_st_sc1(rs, ((t0 + g) * H + 4 * q) * 4, v);
-                });
-            } else if (ok) {
-                rn_unstage_l(lds + Ls.in_off, Ls.in_kb, NG, P.P, H, t, [&](int f, float v) {
-                    __hip_atomic_store(P.trunk + (size_t)gg * H + f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                });
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // every wave's stores performed
-            __syncthreads();
-            if (threadIdx.x == 0 && (int)blockIdx.x != P.dbg_skip)
-                __hip_atomic_store(P.tprog + blockIdx.x, P.tepoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            rn_run<false, false, 3, false, true, true>(R, P.Wimg, P.flat, lds, NG, P.W, P.P, P.bn_s, nullptr, P.trunk_nl,
-                                                 P.dyn_split);                        // the state head
-            if ((H & 3) == 0) {
-                rn_unstage_rows(lds + R.out0_off, R.out0_kb, NG, P.P, H, t0, P.G, [&](int g, int q, float4 v) {
-                    reinterpret_cast<float4*>(P.hid + ((size_t)(t0 + g) * (S + 1) + P.s + 1) * H)[q] = v;
-                });
-            } else if (ok) {
-                float* o = P.hid + ((size_t)gg * (S + 1) + P.s + 1) * H;
-                rn_unstage_l(lds + R.out0_off, R.out0_kb, NG, P.P, H, t, [&](int f, float v) { o[f] = v; });
-            }
-            if ((int)threadIdx.x < NG && t0 + (int)threadIdx.x < P.G)     // the new node's h' not used yet
-                P.hk[(size_t)(t0 + threadIdx.x) * (S + 1) + P.s + 1] = 0;
-            return;
-        }
-        rn_run<false, false, 3, false, true, true>(R, P.Wimg, P.flat, lds, NG, P.W, P.P, P.bn_s, st);
-        if (ok) {
-            if (t.f0 == 0) P.o_v[gg] = rn_act(R.out0_act, lds[R.out0_off + t.g]);   // (RAWTANH)
-            float* o = P.o_logit + (size_t)gg * P.A;
-            rn_unstage(lds + R.out1_off, NG, P.A, t, [&](int f, float v) { o[f] = v; });
-        }
-        __syncthreads();                                              // the outputs read before the LDS is reused
-        if (threadIdx.x == 0)                   // bounded: a publish that never comes is reported (P.fault)
-            mz_poll_ge(P.tprog + blockIdx.x, P.tepoch, P.fault, MZ_FAULT_RS_TRUNK, P.poll_ticks);
-        __syncthreads();
-        const RPlan& Rd = P.plans[MZ_NET_DYN];
-        const RLayer Ls = rn_layer_at(Rd, P.dyn_split);
-        if ((H & 3) == 0) {                                           // 16-byte sc1 pieces (rn_ld_sc1)
+    if (net == MZ_NET_DYN) {
+        rn_run<false, false, 3, false, true, true>(R, P.Wimg, P.flat, lds, NG, P.W, P.P, P.bn_s, st, 0, P.trunk_nl);
+        const RLayer Ls = rn_layer_at(R, P.dyn_split);             // the reward head's input: the trunk output
+        if ((H & 3) == 0) {                                         // 16-byte sc1 pieces (rn_st_sc1)
             const auto rs = __builtin_amdgcn_make_buffer_rsrc(P.trunk, (short)0, P.G * H * 4, 0x00020000);
-            rn_stage_rows_ld(lds + Ls.in_off, Ls.in_kb, NG, P.P, H, t0, P.G, [&](int g, int q) {
-                return rn_ld_sc1(rs, ((t0 + g) * H + 4 * q) * 4);
+            rn_unstage_rows(lds + Ls.in_off, Ls.in_kb, NG, P.P, H, t0, P.G, [&](int g, int q, float4 v) {
+                rn_st_sc1(rs, ((t0 + g) * H + 4 * q) * 4, v);
             });
-        } else {
-            rn_stage_l(lds + Ls.in_off, Ls.in_kb, NG, P.P, H, t, [&](int f) {
-                return ok ? __hip_atomic_load(P.trunk + (size_t)gg * H + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                          : 0.0f;
+        } else if (ok) {
+            rn_unstage_l(lds + Ls.in_off, Ls.in_kb, NG, P.P, H, t, [&](int f, float v) {
+                __hip_atomic_store(P.trunk + (size_t)gg * H + f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             });
         }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // every wave's stores performed
         __syncthreads();
-        rn_run<false, false, 3, false, true, true>(Rd, P.Wimg, P.flat, lds, NG, P.W, P.P, P.bn_s, nullptr, P.dyn_split);
-        if (ok && t.f0 == 0) P.o_r[gg] = rn_act(Rd.out1_act, lds[Rd.out1_off + t.g]);
+        if (threadIdx.x == 0 && (int)blockIdx.x != P.dbg_skip)
+            __hip_atomic_store(P.tprog + blockIdx.x, P.tepoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        rn_run<false, false, 3, false, true, true>(R, P.Wimg, P.flat, lds, NG, P.W, P.P, P.bn_s, nullptr, P.trunk_nl,
+                                                   P.dyn_split);                  // the state head
+        if ((H & 3) == 0) {
+            rn_unstage_rows(lds + R.out0_off, R.out0_kb, NG, P.P, H, t0, P.G, [&](int g, int q, float4 v) {
+                reinterpret_cast<float4*>(P.hid + ((size_t)(t0 + g) * (S + 1) + P.s + 1) * H)[q] = v;
+            });
+        } else if (ok) {
+            float* o = P.hid + ((size_t)gg * (S + 1) + P.s + 1) * H;
+            rn_unstage_l(lds + R.out0_off, R.out0_kb, NG, P.P, H, t, [&](int f, float v) { o[f] = v; });
+        }
+        if ((int)threadIdx.x < NG && t0 + (int)threadIdx.x < P.G)     // the new node's h' not used yet
+            P.hk[(size_t)(t0 + threadIdx.x) * (S + 1) + P.s + 1] = 0;
         return;
     }
     rn_run<false, false, 3, false, true, true>(R, P.Wimg, P.flat, lds, NG, P.W, P.P, P.bn_s, st);
-#ifdef MZ_STAMPS
-    if (st && (threadIdx.x & 63) == 0) st[(threadIdx.x >> 6) * 64 + 61] = __builtin_amdgcn_s_memtime();
-#endif
-    if (!ok) return;
-    if (net == MZ_NET_PRED) {
-        if (t.f0 == 0) P.o_v[gg] = rn_act(R.out0_act, lds[R.out0_off + t.g]);
+    if (ok) {
+        if (t.f0 == 0) P.o_v[gg] = rn_act(R.out0_act, lds[R.out0_off + t.g]);   // (RAWTANH)
         float* o = P.o_logit + (size_t)gg * P.A;
         rn_unstage(lds + R.out1_off, NG, P.A, t, [&](int f, float v) { o[f] = v; });
-    } else {
-        float* o = P.hid + ((size_t)gg * (S + 1) + P.s + 1) * H;
-        rn_unstage_l(lds + R.out0_off, R.out0_kb, NG, P.P, H, t, [&](int f, float v) { o[f] = v; });
-        if (t.f0 == 0) P.o_r[gg] = rn_act(R.out1_act, lds[R.out1_off + t.g]);
-        if (t.f0 == 0) P.hk[(size_t)gg * (S + 1) + P.s + 1] = 0;   // the new node's h' not used yet
     }
+    __syncthreads();                                              // the outputs read before the LDS is reused
+    if (threadIdx.x == 0)                   // bounded: a publish that never comes is reported (P.fault)
+        mz_poll_ge(P.tprog + blockIdx.x, P.tepoch, P.fault, MZ_FAULT_RS_TRUNK, P.poll_ticks);
+    __syncthreads();
+    const RPlan& Rd = P.plans[MZ_NET_DYN];
+    const RLayer Ls = rn_layer_at(Rd, P.dyn_split);
+    if ((H & 3) == 0) {                                           // 16-byte sc1 pieces (rn_ld_sc1)
+        const auto rs = __builtin_amdgcn_make_buffer_rsrc(P.trunk, (short)0, P.G * H * 4, 0x00020000);
+        rn_stage_rows_ld(lds + Ls.in_off, Ls.in_kb, NG, P.P, H, t0, P.G, [&](int g, int q) {
+            return rn_ld_sc1(rs, ((t0 + g) * H + 4 * q) * 4);
+        });
+    } else {
+        rn_stage_l(lds + Ls.in_off, Ls.in_kb, NG, P.P, H, t, [&](int f) {
+            return ok ? __hip_atomic_load(P.trunk + (size_t)gg * H + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                      : 0.0f;
+        });
+    }
+    __syncthreads();
+    rn_run<false, false, 3, false, true, true>(Rd, P.Wimg, P.flat, lds, NG, P.W, P.P, P.bn_s, nullptr, P.dyn_split);
+    if (ok && t.f0 == 0) P.o_r[gg] = rn_act(Rd.out1_act, lds[Rd.out1_off + t.g]);
 }
 
 // ================================================================ learner
@@ -1420,71 +1398,20 @@ __device__ __forceinline__ RUnrollParams rn_step(const RUnrollParams& U, int zs 
     return V;
 }
 
-extern "C" __global__ __launch_bounds__(RN_THREADS) void mz_runroll_kernel(RUnrollParams U) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const RPlan& Rr = U.plans[MZ_NET_REPR];
-    const RPlan& Rp = U.plans[MZ_NET_PRED];
-    const RPlan& Rd = U.plans[MZ_NET_DYN];
-    const int NG = U.ng, t0 = blockIdx.x * NG, H = U.H, A = U.A, K1 = U.K + 1;
-    const RnLane t = rn_lane(NG);
-    const int b = t0 + t.g;
-    const bool ok = b < U.B;
-    const size_t bs = (size_t)(ok ? b : 0);
-    float* hs = U.hs + bs * H;
-    rn_fill_ktabs(Rr, lds, NG, U.W, U.P);
-    {
-        const float* x = U.obs + bs * U.obs_feat;
-        rn_stage_l(lds + Rr.in_off, Rr.in_kb, NG, U.P, Rr.in_feat, t, [&](int f) { return ok ? x[f] : 0.0f; });
-    }
-    __syncthreads();
-    rn_run(Rr, U.Wimg, U.flat, lds, NG, U.W, U.P, U.bn_s);                     // :347
-    if (ok) rn_unstage_l(lds + Rr.out0_off, Rr.out0_kb, NG, U.P, H, t, [&](int f, float v) { hs[f] = v; });
-    if (ok && t.f0 == 0) U.pr[bs * K1] = 0.0f;
-    const int ns = U.K > 0 ? U.K : 1;              // K = 0: the prediction of h0 alone
-    for (int s = 1; s <= ns; ++s) {
-        __syncthreads();
-        rn_fill_ktabs(Rp, lds, NG, U.W, U.P);
-        rn_stage_l(lds + Rp.in_off, Rp.in_kb, NG, U.P, H, t, [&](int f) { return ok ? hs[f] : 0.0f; });
-        __syncthreads();
-        rn_run(Rp, U.Wimg, U.flat, lds, NG, U.W, U.P, U.bn_s);                 // :351 / :356
-        if (ok) {
-            // step s (and step 0 from the same prediction of h0, Q10)
-            for (int j = s == 1 ? 0 : s; j <= (s <= U.K ? s : 0); ++j) {
-                if (t.f0 == 0) U.pv[bs * K1 + j] = lds[Rp.out0_off + t.g];
-                float* o = U.pp + (bs * K1 + j) * A;
-                rn_unstage(lds + Rp.out1_off, NG, A, t, [&](int f, float v) { o[f] = v; });
-            }
-        }
-        if (s > U.K) break;
-        __syncthreads();
-        rn_fill_ktabs(Rd, lds, NG, U.W, U.P);
-        {                                                                      // make_dynamics_input (:293-304)
-            const float av = ok ? U.actions[bs * K1 + (s - 1)] / (float)A : 0.0f;
-            rn_stage_l(lds + Rd.in_off, Rd.in_kb, NG, U.P, Rd.in_feat, t, [&](int f) { return !ok ? 0.0f : f < H ? hs[f] * 2.0f : av; });
-        }
-        __syncthreads();
-        rn_run(Rd, U.Wimg, U.flat, lds, NG, U.W, U.P, U.bn_s);                 // :362
-        if (ok) {
-            rn_unstage_l(lds + Rd.out0_off, Rd.out0_kb, NG, U.P, H, t, [&](int f, float v) { hs[f] = v; });
-            if (t.f0 == 0) U.pr[bs * K1 + s] = lds[Rd.out1_off + t.g];
-        }
-    }
-}
-
-// Learner unroll, split form (the same read-outs as mz_runroll_kernel, bit for
-// bit: every tile column is an independent fma chain, so the tile width does
-// not change a result).  The unroll's only sequential part is representation
+// Learner unroll, split form (the same read-outs as one workgroup running the
+// whole unroll of its tile, bit for bit: every tile column is an independent
+// fma chain, so the tile width does not change a result; that one-kernel form
+// was removed).  The unroll's only sequential part is representation
 // (:347) then the K dynamics steps' state path (:355-362: the trunk and the
 // state head, h_{s-1} -> h_s); the K predictions (:351, :356) only read h_0 ..
 // h_{K-1} and the K reward heads only the dynamics trunk outputs.
-// mz_runroll_chain runs that path on narrow tiles of ng_l samples — B / ng_l
+// mz_runroll_chain1 runs that path on narrow tiles of ng_l samples — B / ng_l
 // workgroups instead of B / 16, a narrower MFMA column range per layer, so a
 // short per-layer critical path, with each layer's plan entry and first
 // operands loaded under the previous one — and stores h_s to hs[b][s] and the
 // trunk output of step s to ts[b][s-1]; mz_runroll_pred then runs the B·K
 // predictions (blockIdx.y = 0) and the B·K reward heads (y = 1) as one wide
 // launch on tiles of ng items.
-template <int NBWMAX>
 __device__ __forceinline__ void runroll_chain_body(const RUnrollParams& U) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const RPlan& Rr = U.plans_l[MZ_NET_REPR];
@@ -1516,7 +1443,7 @@ __device__ __forceinline__ void runroll_chain_body(const RUnrollParams& U) {
         rn_stage_l(lds + Rr.in_off, Rr.in_kb, NG, U.P, Rr.in_feat, t, [&](int f) { return ok ? x[f] : 0.0f; });
     }
     __syncthreads();
-    rn_run<true, true, NBWMAX>(Rr, U.Wimg, U.flat, lds, NG, U.W, U.P, U.bn_s, st_r);         // :347
+    rn_run<true, true, 1>(Rr, U.Wimg, U.flat, lds, NG, U.W, U.P, U.bn_s, st_r);         // :347
     if (ok) rn_unstage_l(lds + Rr.out0_off, Rr.out0_kb, NG, U.P, H, t, [&](int f, float v) { hs[f] = v; });
     if (ok && t.f0 == 0) U.pr[bs * K1] = 0.0f;                                 // :352 zeros
     for (int s = 1; s <= K; ++s) {
@@ -1528,7 +1455,7 @@ __device__ __forceinline__ void runroll_chain_body(const RUnrollParams& U) {
             rn_stage_l(lds + Rd.in_off, Rd.in_kb, NG, U.P, Rd.in_feat, t, [&](int f) { return !ok ? 0.0f : f < H ? hp[f] * 2.0f : av; });
         }
         __syncthreads();
-        rn_run<true, true, NBWMAX>(Rd, U.Wimg, U.flat, lds, NG, U.W, U.P, U.bn_s, s == 1 ? st_d : nullptr, 0, split);  // :362
+        rn_run<true, true, 1>(Rd, U.Wimg, U.flat, lds, NG, U.W, U.P, U.bn_s, s == 1 ? st_d : nullptr, 0, split);  // :362
         if (ok) {
             if (s < K) rn_unstage_l(lds + Rd.out0_off, Rd.out0_kb, NG, U.P, H, t,
                                     [&](int f, float v) { hs[(size_t)s * H + f] = v; });
@@ -1537,11 +1464,9 @@ __device__ __forceinline__ void runroll_chain_body(const RUnrollParams& U) {
     }
 }
 
-extern "C" __global__ __launch_bounds__(RN_THREADS) void mz_runroll_chain(RUnrollParams U) {
-    runroll_chain_body<3>(rn_step(U));
-}
+// (units of one column block, on planes of several blocks too: NBWMAX = 1)
 extern "C" __global__ __launch_bounds__(RN_THREADS) void mz_runroll_chain1(RUnrollParams U) {
-    runroll_chain_body<1>(rn_step(U));
+    runroll_chain_body(rn_step(U));
 }
 
 // ---- the chain with a register-resident dynamics path (mz_runroll_chain_r)
@@ -1594,7 +1519,9 @@ __device__ __forceinline__ void rd_epilogue(const RLayer& L, const mz_f32x4 (&ac
 }
 
 // layer I of the resident chain (wave ob < 4); a[] = this layer's chunks;
-// NB column blocks of 16, one after the other (reads, 16 MFMAs, epilogue)
+// NB column blocks of 16, one after the other (reads, 16 MFMAs, epilogue).
+// (Every caller has NB = 1; the parameter and its one-trip loop stay because the
+// compiler schedules the kernels differently without them.)
 template <int NCH, int NB = 1>
 __device__ __forceinline__ void rd_layer(const RLayer& L, const float (&a)[NCH][4][4], const float4* ep_lds,
                                          float* lds, int ncols, float bn_s, float bn_r) {
@@ -1658,7 +1585,7 @@ __device__ __forceinline__ void rd_layer(const RLayer& L, const float (&a)[NCH][
     }
 }
 
-template <int I, int NL, int NB>
+template <int I, int NL>
 __device__ __forceinline__ void rd_run(const RPlan& Rd, const float (&a0)[2][4][4], const float (&ar)[NL][4][4],
                                        const float4* ep_lds, float* lds, int ncols, float bn_s, float bn_r,
                                        unsigned long long* st, int nrun = NL) {
@@ -1669,10 +1596,10 @@ __device__ __forceinline__ void rd_run(const RPlan& Rd, const float (&a0)[2][4][
 #ifdef MZ_STAMPS
             if (st && (threadIdx.x & 63) == 0) st[(threadIdx.x >> 6) * 64 + 63] = __builtin_amdgcn_s_memtime();
 #endif
-            rd_layer<2, NB>(L, a0, ep_lds, lds, ncols, bn_s, bn_r);
+            rd_layer<2>(L, a0, ep_lds, lds, ncols, bn_s, bn_r);
         } else {
             const float (&a1)[1][4][4] = *reinterpret_cast<const float (*)[1][4][4]>(&ar[I]);
-            rd_layer<1, NB>(L, a1, ep_lds + I * 64, lds, ncols, bn_s, bn_r);
+            rd_layer<1>(L, a1, ep_lds + I * 64, lds, ncols, bn_s, bn_r);
         }
 #ifdef MZ_STAMPS
         if (st && (threadIdx.x & 63) == 0 && I < 31) st[(threadIdx.x >> 6) * 64 + 2 * I] = __builtin_amdgcn_s_memtime();
@@ -1681,7 +1608,7 @@ __device__ __forceinline__ void rd_run(const RPlan& Rd, const float (&a0)[2][4][
 #ifdef MZ_STAMPS
         if (st && (threadIdx.x & 63) == 0 && I < 31) st[(threadIdx.x >> 6) * 64 + 2 * I + 1] = __builtin_amdgcn_s_memtime();
 #endif
-        rd_run<I + 1, NL, NB>(Rd, a0, ar, ep_lds, lds, ncols, bn_s, bn_r, st, nrun);
+        rd_run<I + 1, NL>(Rd, a0, ar, ep_lds, lds, ncols, bn_s, bn_r, st, nrun);
     }
     (void)st;
 }
@@ -1720,10 +1647,10 @@ __device__ __forceinline__ void rd_wait(const RUnrollParams& U, int b, int p) {
     __syncthreads();
 }
 
-// NL: the dynamics chain's layers ([0, dyn_split)); NB: column blocks of the tile;
+// NL: the dynamics chain's layers ([0, dyn_split)); the tile is one column block;
 // FUSE: mz_runroll_fused_r's chain blocks (ng_l = 1: tile = sample), which
 // draw their sample first when U.fuse_sample and publish their progress
-template <int NL, int NB, bool FUSE = false>
+template <int NL, bool FUSE = false>
 __device__ __forceinline__ void runroll_chain_r_body(const RUnrollParams& U, int tile) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const RPlan& Rr = U.plans_l[MZ_NET_REPR];
@@ -1768,7 +1695,7 @@ __device__ __forceinline__ void runroll_chain_r_body(const RUnrollParams& U, int
         rn_stage_l(lds + Rr.in_off, Rr.in_kb, NG, U.P, Rr.in_feat, t, [&](int f) { return ok ? x[f] : 0.0f; });
     }
     __syncthreads();
-    rn_run<true, true, NB == 1 ? 1 : 3, true>(Rr, U.Wimg, U.flat, lds, NG, U.W, U.P, U.bn_s, st_r);   // :347
+    rn_run<true, true, 1, true>(Rr, U.Wimg, U.flat, lds, NG, U.W, U.P, U.bn_s, st_r);   // :347
     // resident A fragments of the dynamics chain (wave w = row block w), issued
     // after the representation (live across it, they cost its code registers)
     const int lane = threadIdx.x & 63, ob = threadIdx.x >> 6;
@@ -1796,8 +1723,8 @@ __device__ __forceinline__ void runroll_chain_r_body(const RUnrollParams& U, int
         __syncthreads();
         // :362, [0, split); the last step's state head is skipped: h_K is never read
         // (predictions take h_0..h_{K-1}, the reward heads the trunk outputs)
-        rd_run<0, NL, NB>(Rd, a0, ar, ep_lds, lds, ncols, U.bn_s, bn_r, s == 1 ? st_d : nullptr,
-                          s < K ? NL : U.rd_trunk_nl);
+        rd_run<0, NL>(Rd, a0, ar, ep_lds, lds, ncols, U.bn_s, bn_r, s == 1 ? st_d : nullptr,
+                      s < K ? NL : U.rd_trunk_nl);
         if (ok) {
             if (s < K) rn_unstage_l(lds + Rd.out0_off, Rd.out0_kb, NG, U.P, H, t, [&](int f, float v) {
                 if constexpr (FUSE) rd_st(hs + (size_t)s * H + f, v); else hs[(size_t)s * H + f] = v;
@@ -1809,13 +1736,9 @@ __device__ __forceinline__ void runroll_chain_r_body(const RUnrollParams& U, int
         if constexpr (FUSE) rd_publish(U, t0, s + 1);                         // h_s (s < K), trunk of step s
     }
 }
-// TicTacToe resnet_hyper (2 blocks: 10 chain layers, 3x3 board: one column
-// block) and Connect4 ResNet-8 (4 blocks: 18 layers, 6x7 board: three)
+// TicTacToe resnet_hyper (2 blocks: 10 chain layers, 3x3 board: one column block)
 extern "C" __global__ __launch_bounds__(RD_THREADS) void mz_runroll_chain_r(RUnrollParams U) {
-    runroll_chain_r_body<RD_NL, 1>(rn_step(U), blockIdx.x);
-}
-extern "C" __global__ __launch_bounds__(RD_THREADS) void mz_runroll_chain_r3(RUnrollParams U) {
-    runroll_chain_r_body<RD_NL3, 3>(rn_step(U), blockIdx.x);
+    runroll_chain_r_body<RD_NL>(rn_step(U), blockIdx.x);
 }
 
 // blockIdx.y = 0: prediction(h_s) for items i = b·KH + s (KH = max(K, 1)):
@@ -1960,7 +1883,7 @@ __device__ __forceinline__ void runroll_l2_block(const RUnrollParams& U, int j) 
     }
 }
 
-template <int NL, int NB>
+template <int NL>
 __device__ __forceinline__ void runroll_fused_r_body(const RUnrollParams& U, int bi) {
 #ifdef MZ_STAMPS   // diagnostic build: per block {start, input published / chain's last publish, end} (s_memrealtime)
     unsigned long long* fs = U.stamps ? U.stamps + 2048 + 4 * bi : nullptr;
@@ -1969,7 +1892,7 @@ __device__ __forceinline__ void runroll_fused_r_body(const RUnrollParams& U, int
 #else
 #define RD_FS_END() do {} while (0)
 #endif
-    if (bi < U.n_chain) { runroll_chain_r_body<NL, NB, true>(U, bi); RD_FS_END(); return; }
+    if (bi < U.n_chain) { runroll_chain_r_body<NL, true>(U, bi); RD_FS_END(); return; }
     if (bi < U.n_chain + U.n_l2) { runroll_l2_block(U, bi - U.n_chain); RD_FS_END(); return; }
     // per step: B value-head items, B policy-head items, B reward heads (K > 0)
     const int ny = U.K > 0 ? 3 : 2, KH = U.K > 0 ? U.K : 1;
@@ -1983,33 +1906,27 @@ __device__ __forceinline__ void runroll_fused_r_body(const RUnrollParams& U, int
 // A multi-step launch (U.ms steps, one-dimensional grid): the chain blocks of
 // every step first (step-major), so each step's chains are dispatched before
 // any item of any step waits on them, then the items step by step
-template <int NL, int NB>
+template <int NL>
 __device__ __forceinline__ void runroll_fused_r_entry(const RUnrollParams& U) {
     const int bi = blockIdx.x;
-    if (!U.ms) { runroll_fused_r_body<NL, NB>(U, bi); return; }
+    if (!U.ms) { runroll_fused_r_body<NL>(U, bi); return; }
     const int nc = U.n_chain, per = (U.K > 0 ? 3 : 2) * U.B * (U.K > 0 ? U.K : 1);
     if (bi < U.ms * nc) {
         const int z = bi / nc;
-        runroll_fused_r_body<NL, NB>(rn_step(U, z), bi - z * nc);
+        runroll_fused_r_body<NL>(rn_step(U, z), bi - z * nc);
     } else {
         const int j = bi - U.ms * nc, z = j / per;
-        runroll_fused_r_body<NL, NB>(rn_step(U, z), nc + U.n_l2 + (j - z * per));
+        runroll_fused_r_body<NL>(rn_step(U, z), nc + U.n_l2 + (j - z * per));
     }
 }
 extern "C" __global__ __launch_bounds__(RD_THREADS) void mz_runroll_fused_r(RUnrollParams U) {
-    runroll_fused_r_entry<RD_NL, 1>(U);
-}
-extern "C" __global__ __launch_bounds__(RD_THREADS) void mz_runroll_fused_r3(RUnrollParams U) {
-    runroll_fused_r_entry<RD_NL3, 3>(U);
+    runroll_fused_r_entry<RD_NL>(U);
 }
 
 // wide tiles of ng items (plans), or one item per workgroup on the narrow
 // (chain) plans — B·K workgroups, a short per-layer critical path
 extern "C" __global__ __launch_bounds__(RN_THREADS) void mz_runroll_pred(RUnrollParams U) {
     runroll_pred_body<false>(rn_step(U));
-}
-extern "C" __global__ __launch_bounds__(RN_THREADS) void mz_runroll_pred_n(RUnrollParams U) {
-    runroll_pred_body<true>(rn_step(U));
 }
 extern "C" __global__ __launch_bounds__(RN_THREADS) void mz_runroll_pred_n1(RUnrollParams U) {
     runroll_pred_body<true, 1>(rn_step(U));

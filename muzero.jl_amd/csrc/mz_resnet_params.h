@@ -151,17 +151,19 @@ struct RSearchParams {
     const RPlan* plans;    // repr, pred, dyn
     unsigned long long* stamps;   // -DMZ_STAMPS builds: per-layer ticks of nets blocks (0,0), (0,1)
     const float* Wimg; const float* flat;
-    // rew_split (mz_rsearch_nets): y = 0 runs the dynamics trunk, publishes its
+    // mz_rsearch_nets: y = 0 runs the dynamics trunk, publishes its
     // output (trunk[G][H], agent-scope stores, then tprog[tile] = tepoch) and runs
     // the state head; y = 1 runs the prediction, then the dynamics reward head
     // ([dyn_split, n)) on the published trunk output — the two workgroups of a
     // tile carry about equal work instead of 101 k / 142 k ticks
-    int rew_split, trunk_nl, dyn_split;
+    int trunk_nl, dyn_split;
     float* trunk; unsigned long long* tprog; unsigned long long tepoch;
     unsigned* fault;                   // MZ_FAULT_RS_TRUNK on a publish that never came (mz_poll_ge)
     unsigned long long poll_ticks;     // the poll's bound (MZ_POLL_TICKS)
     int dbg_skip;                      // debug: the tile whose trunk publish is skipped (-1 = none)
-    int no_moved_skip;                 // A/B only (MZ_NO_MOVED_SKIP): after a min / max move the walk starts at the root
+    int no_moved_skip;                 // always 0 (rsearch): its test stays in mz_rsearch_tree_lds* because the
+                                       // kernels without it measured a slower configs[2] search
+                                       // (profiles/ab_switches_removed.txt)
 };
 
 // LDS layout of the LDS-cached tree step (mz_rsearch_tree_lds*): one wave per
@@ -199,11 +201,11 @@ struct RUnrollParams {
     float bn_s;
     const float* obs; const float* actions;
     float* pv; float* pp; float* pr;   // (K+1, B), (A, K+1, B), (K+1, B)
-    float* hs;                         // [B][H] scratch (mz_runroll_kernel); [B][K][H] h_0..h_{K-1} (split form)
+    float* hs;                         // [B][K][H] h_0..h_{K-1}: the chain's states, the predictions' input
     const RPlan* plans;
     const float* Wimg; const float* flat;
-    // split form: mz_runroll_chain (representation + the K dynamics steps, the
-    // sequential part) on tiles of ng_l samples with plans_l, then
+    // split form: mz_runroll_chain1 (representation + the K dynamics steps, the
+    // sequential part) on tiles of ng_l samples (the host writes 1) with plans_l, then
     // mz_runroll_pred (the K predictions, independent) on tiles of ng items
     const RPlan* plans_l; int ng_l;
     const int* otab;                   // the narrow plans' offset tables (RPlan.tab_src)
@@ -243,7 +245,6 @@ struct RUnrollParams {
 // mz_runroll_chain_r: the dynamics chain's layers ([0, dyn_split) = RD_NL:
 // trunk + state head of 2-block towers) with register-resident A fragments
 #define RD_NL 10
-#define RD_NL3 18        // mz_runroll_chain_r3: 4-block towers on three column blocks (Connect4 ResNet-8)
 #define RD_THREADS 256
 // mz_runroll_pred_r: the prediction trunk's RP_NL layers (1 + 2 blocks) the same way
 #define RP_NL 5
@@ -330,17 +331,12 @@ extern "C" __global__ void mz_rsearch_tree32(RSearchParams P);
 extern "C" __global__ void mz_rsearch_tree_lds(RSearchParams P);
 extern "C" __global__ void mz_rsearch_tree_lds32(RSearchParams P);
 extern "C" __global__ void mz_rsearch_nets(RSearchParams P);
-extern "C" __global__ void mz_runroll_kernel(RUnrollParams U);
-extern "C" __global__ void mz_runroll_chain(RUnrollParams U);
 extern "C" __global__ void mz_runroll_chain1(RUnrollParams U);
 extern "C" __global__ void mz_runroll_chain_r(RUnrollParams U);
-extern "C" __global__ void mz_runroll_chain_r3(RUnrollParams U);
 extern "C" __global__ void mz_runroll_pred(RUnrollParams U);
-extern "C" __global__ void mz_runroll_pred_n(RUnrollParams U);
 extern "C" __global__ void mz_runroll_pred_n1(RUnrollParams U);
 extern "C" __global__ void mz_runroll_pred_r(RUnrollParams U);
 extern "C" __global__ void mz_runroll_fused_r(RUnrollParams U);
-extern "C" __global__ void mz_runroll_fused_r3(RUnrollParams U);
 extern "C" __global__ void mz_downsample_kernel(DsParams Q);
 extern "C" __global__ void mz_dsbp_fwd(DsBpParams Q);
 extern "C" __global__ void mz_dsbp_bwd(DsBpParams Q);

@@ -228,11 +228,7 @@ __device__ __forceinline__ void sm_load(int k0, int k1, const float* W, float (&
             for (int i = 0; i < 4; ++i) {
                 // a skipped chunk reads the shared zero line (branch-free; one
                 // cache line for every skipping lane)
-#ifdef MZ_NO_WLOAD   // diagnostic only (wrong results): the setup without the weight stream
-                const float4 v = make_float4((float)(m >> i & 1u), 0.0f, 0.0f, 0.0f);
-#else
                 const float4 v = *((m >> i) & 1u ? src + i * 256 : zero16);
-#endif
                 wr[k + DST][4 * i] = v.x; wr[k + DST][4 * i + 1] = v.y; wr[k + DST][4 * i + 2] = v.z;
                 wr[k + DST][4 * i + 3] = v.w;
             }
@@ -391,28 +387,6 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
     // selects for game w, behind the recompute's barrier (the last simulation's
     // backup and entries are visible) and in front of the one before stage 0.
     for (int s = 0; s < S; ++s) {
-#ifdef MZ_SELECT_WALK   // A/B: the serial walk on wave 0 for all T games
-        if (tid < 64) {
-            // ---- select (:256-268)
-            if (active) {
-                // the start level and its node / incoming edge from the last path
-#ifdef MZ_NO_SKIP   // A/B: every walk from the root
-                const int D = 0;
-#else
-                const int D = c_skip[g];
-#endif
-                const int e0 = D > 0 ? path[2 * D + 1] : 0;
-                const uint32_t npc0 = D > 0 ? tree.nc(path[2 * D]) : 0u;
-                const SelectOut so = select_path_cached(tree, c_cache + g * NN, (uint32_t)ver, path, sg_rootN[g],
-                                                        sg_root_tp[g], legal, sg_mmin[g], sg_mmax[g], a, lane, A,
-                                                        P.players, l_pbterm, P.seed, gid, P.rng_step, s, nullptr,
-                                                        nullptr, D, e0, npc0);
-                if (a == 0) { sg_leaf_e[g] = so.leaf_e; sg_leaf_a[g] = so.leaf_a; sg_vtp[g] = so.vtp; sg_depth[g] = so.depth; }
-            }
-            __builtin_amdgcn_wave_barrier();
-            SM_STAMP(1);
-        }
-#else
         if (tid < 64 * T) {
             // ---- select (:256-268): wave w selects for game w.  The ballot pass
             // reads the path off the cache in constant depth; when it stops at a
@@ -432,11 +406,7 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
                     found = select_path_ballot(tw, cw, c_stat + w * NNS, verw, pw, s + 1, s + 1, rtp, lane, A,
                                                P.players, so, D, e0, npc0);
                 } else {                       // the tree outgrows one wave: the walk, from the skip-ahead level
-#ifdef MZ_NO_SKIP
-                    D = 0;
-#else
                     D = c_skip[w];
-#endif
                     e0 = D > 0 ? pw[2 * D + 1] : 0;
                     npc0 = D > 0 ? tw.nc(pw[2 * D]) : 0u;
                 }
@@ -457,7 +427,6 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
             __builtin_amdgcn_wave_barrier();
             SM_STAMP(1);
         }
-#endif
         __syncthreads();
 #ifdef MZ_STAMPS
         if (threadIdx.x == 0) {                 // slot 7: select levels walked (max over the T games)
@@ -486,14 +455,7 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
                 // f64 tanh chains run at once), then each quad's lanes 0 / 1 to all
                 // four by DPP quad_perm [0,0,0,0] / [1,1,1,1]
                 const bool odd = (a & 1) != 0;
-#ifdef MZ_DIAG_TANH_TWICE     // diagnostic (same results): the read-out activations twice
-                float rin = act[(odd ? P.r_out : P.v_out) + g];
-                const float ro0 = mz_post_act(odd ? P.r_act : P.v_act, rin);
-                asm volatile("" : "+v"(rin) : "v"(ro0));
-                const float ro = mz_post_act(odd ? P.r_act : P.v_act, rin);
-#else
                 const float ro = mz_post_act(odd ? P.r_act : P.v_act, act[(odd ? P.r_out : P.v_out) + g]);
-#endif
                 const float val = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
                     0, __builtin_bit_cast(int, ro), 0x00, 0xF, 0xF, false));
                 const float rew = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
@@ -536,15 +498,8 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
             const int g2 = (tid - 128) >> 4;
             const bool active2 = tile0 + g2 < P.G;
             TreeView tree2 = tree_view(lds_tree + (size_t)g2 * P.tree_game_bytes, E, NN);
-#ifdef MZ_DIAG_EXPAND_TWICE   // diagnostic (same results): the double softmax twice — is expand on the critical path?
-            float lgt = act[P.p_out + a * T + g2];
-            const float prior0 = double_softmax_prior(a < A ? lgt : 0.0f, a, A, sg_legal[g2], sg_stage + 16 * g2);
-            asm volatile("" : "+v"(lgt) : "v"(prior0));
-            const float prior = double_softmax_prior(a < A ? lgt : 0.0f, a, A, sg_legal[g2], sg_stage + 16 * g2);
-#else
             const float prior = double_softmax_prior(a < A ? act[P.p_out + a * T + g2] : 0.0f, a, A, sg_legal[g2],
                                                      sg_stage + 16 * g2);
-#endif
             if (active2) init_edges(tree2, e_new, a, A, prior);
             W_STAMP(1);
         } else if (tid >= 192) {
@@ -576,11 +531,6 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
                               "+v"(l0.y), "+v"(n0));   // all issued together, one wait
             const bool full = hd.x != 0;
             const int n = full ? s + 2 : hd.y + 1;
-#ifdef MZ_NO_SKIP_MIN   // A/B: no skip-ahead bound while the ballot select runs (it does not read c_skip)
-            const bool skip_min = !sel_ballot;
-#else
-            const bool skip_min = true;
-#endif
             const bool lgl = a < A && (((uint32_t)hd.w >> a) & 1u);
             const TreeView tq = tree_view(lds_tree + (size_t)gq * P.tree_game_bytes, E, NN);
             uint2* cq = c_cache + gq * NN;
@@ -591,14 +541,14 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
             if (j0 < n) {
                 const int ch = cache_row(tq, cq, (uint32_t)hd.z, full ? j0 : (int)l0.x, full ? n0 : (int)l0.y, lgl,
                                          a, A, mm.x, mm.y, l_pbterm, lane);
-                if (skip_min && !full && a == 0 && (j0 >= hd.y || ch != pe0 - (int)l0.x * A)) atomicMin(c_skip + gq, j0);
+                if (!full && a == 0 && (j0 >= hd.y || ch != pe0 - (int)l0.x * A)) atomicMin(c_skip + gq, j0);
             }
             for (int j = j0 + SM_THREADS / 16 / T; j < n; j += SM_THREADS / 16 / T) {   // deep paths, large trees
                 int slot, Np;
                 if (full) { slot = j; Np = c_nN[gq * NN + j]; }
                 else { const uint2 l = c_lvl[gq * (S + 2) + j]; slot = (int)l.x; Np = (int)l.y; }
                 const int ch = cache_row(tq, cq, (uint32_t)hd.z, slot, Np, lgl, a, A, mm.x, mm.y, l_pbterm, lane);
-                if (skip_min && !full && a == 0 && (j >= hd.y || ch != pq[2 * (j + 1)] - slot * A)) atomicMin(c_skip + gq, j);
+                if (!full && a == 0 && (j >= hd.y || ch != pq[2 * (j + 1)] - slot * A)) atomicMin(c_skip + gq, j);
             }
             __syncthreads();
             SM_STAMP(6);                           // stamp build: slot 6 = the cache recompute (+ finish)
@@ -817,11 +767,7 @@ __device__ __forceinline__ void learn_body(const SmallUnrollParams& P, const Lea
 #ifdef MZ_STAMPS
     const unsigned long long t_start = __builtin_amdgcn_s_memtime();
 #endif
-    // logical block: with L.xcd the unroll workgroups are the physical blocks
-    // 0, 8, 16, .. (one XCD under round-robin dispatch: their weight image is
-    // fetched into one L2), the other roles take the remaining blocks in order
-    const int pb = (int)blockIdx.x;
-    const int lb = L.xcd ? ((pb & 7) == 0 ? pb >> 3 : L.nU + pb - (pb >> 3) - 1) : pb;
+    const int lb = (int)blockIdx.x;
     if (lb < L.nU) {
         unroll_body<T, BNM>(P, lb, sm_io(P));
 #ifdef MZ_STAMPS
@@ -900,16 +846,10 @@ __device__ __forceinline__ void chain_param(const ChainParams& C, size_t p, doub
     for (int i = 0; i < L; ++i) {
         if constexpr (HELP) __hip_atomic_store(hx + (size_t)i * C.hx_n, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else rd[i * MZ_THREADS] += (double)x * (double)x;           // step t+i's Σθ² reads θ_{t+i}
-#ifndef MZ_DBG_NO_BANK   // diagnostic only (wrong results): the chain without the bank scatter
         if (sbank) mz_scatter(x, is, C.bank_w + i * C.bws, C.bank_b + i * C.bbs);
-#endif
         if (tbank) mz_scatter(x, it, C.tbank_w + i * C.tws, C.tbank_b + i * C.tbs);
         if (C.fbank) C.fbank[i * C.fstride + p] = x;
-#ifdef MZ_DBG_CHEAP_ADAM   // diagnostic only (wrong results): the chain without ADAM's f64 arithmetic
-        x = x * 0.999f + (float)sbp[2][i];
-#else
         x = adam_2theta(x, m, v, sbp[0][i], sbp[1][i], sbp[2][i]);   // Learning.jl:395-397
-#endif
         if (C.theta) C.theta[i * C.nflat + p] = x;
         if constexpr (CAP) {
             if (i == C.cap_i[0]) {
@@ -934,12 +874,8 @@ __device__ __forceinline__ void chain_slice(const ChainParams& C, int net, int s
     const int tid = threadIdx.x;
     const size_t off = C.netoff[net], cnt = C.netoff[3 + net];
     const size_t stride = (size_t)MZ_L2_BLOCKS * MZ_THREADS;
-    for (size_t e = (size_t)sb * MZ_THREADS + tid; e < cnt; e += stride) {
+    for (size_t e = (size_t)sb * MZ_THREADS + tid; e < cnt; e += stride)
         chain_param<CAP, false>(C, off + e, &red[0][tid], nullptr, sbp);
-#ifdef MZ_DBG_ONE_ELEM   // diagnostic only (wrong results): each thread's first parameter alone
-        break;
-#endif
-    }
 }
 
 // lg_tree256 per step: level o adds red[i][j + o] into red[i][j] for j < o, every step i; the o·L adds of

@@ -115,7 +115,6 @@ struct SmallUnrollParams {
 // race them; the last block folds the losses.
 struct LearnParams {
     int nU;
-    int xcd;              // the unroll workgroups on physical blocks 0, 8, .. (grid 8·nU; learn_body)
     const float* tv; const float* tp; const float* gscale;
     float* terms; float* flat; const size_t* netoff; double* part; unsigned* counter; float* out;
     LgAdam ad;
@@ -139,8 +138,9 @@ struct LearnParams {
 //    its step's bank image: waves 0..T-1 first draw the workgroup's samples of
 //    step t+i (get_batch keyed by the step, one wave per sample), then the
 //    unroll and the loss terms; the last workgroup of step i folds step i's
-//    losses with the chain launch's Σθ² partials.  (MZ_MULTI_CHAIN_SAMPLE=1:
-//    the chain launch draws the L batches in blocks after its slices instead.)
+//    losses with the chain launch's Σθ² partials.  (For the ResNet multi-step
+//    learner the chain launch draws the L batches in blocks after its slices
+//    instead; the FC host always sets LearnMultiParams.sample.)
 #define MZ_MULTI_MAX 32           // steps per chain launch (a bank half holds their images)
 #define MZ_MULTI_UNROLL 16        // steps per unroll launch (FC: one workgroup per CU at B = 32, T = 2)
 #define MZ_MULTI_LMAX 256         // steps per mz_learner_train_multi_dev call

@@ -90,6 +90,12 @@ def test_multi_matches_sequential_steps(kind, B, L):
         assert ("multi" in e2.learner_variant()) == (rn or e1.learner_variant().startswith("mz_learn_small")), \
             (e1.learner_variant(), e2.learner_variant())
         multi = "multi" in e2.learner_variant()
+        # the three FC multi-step kernels, each reached by the plan's own choice of T at 256 CUs
+        # (MZ_MULTI_MAX = 32): L·B <= 256 -> T = 1; L >= 32 and L·⌈B/4⌉ >= 256 -> T = 4; else T = 2
+        plan = {("ttt", 32, 8): "mz_learn_multi1", ("ttt", 32, 16): "mz_learn_multi2",
+                ("ttt", 32, 37): "mz_learn_multi4"}.get((kind, B, L))
+        if plan and torch.cuda.get_device_properties(0).multi_processor_count == 256:
+            assert e2.learner_variant().endswith(plan), e2.learner_variant()
         got_l, got_t = lm.cpu().numpy(), th.cpu().numpy()
         for i, (wl, wt, wu) in enumerate(want):
             assert np.array_equal(got_l[i, :6], wl), (rnd, i, got_l[i, :6], wl)

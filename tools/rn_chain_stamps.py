@@ -1,5 +1,5 @@
 """Diagnostic: per-layer ticks (s_memtime) of the ResNet learner chain kernel
-(mz_runroll_chain), from a separate -DMZ_STAMPS build (libmz_stamps.so): for
+(mz_runroll_chain1 / mz_runroll_chain_r), from a separate -DMZ_STAMPS build (libmz_stamps.so): for
 chain workgroup 0, per wave, the compute span of each layer of the
 representation and of the first dynamics step, and the wait at its barrier.
 usage: python tools/rn_chain_stamps.py [--no-build] [--game atari]"""
