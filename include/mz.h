@@ -408,6 +408,73 @@ int mz_expert_eval(mz_handle* h, int env_kind, int G, const uint8_t* boards, con
  * mover).  Synchronises.                                                    */
 int mz_eval_results(mz_handle* h, int64_t* out4);
 
+/* ---- The test worker (the reference's muzero.jl:29-31 leaves it
+ * as "Launch the test worker to get performance metrics") -------------------
+ * Evaluation games on a second, independent set of E game slots of the
+ * handle, so a training job can be measured while it runs: the self-play
+ * slots, their histories, the shard, its counters and PER state, the batch
+ * drawn ahead, the train loop's weight sets and mz_eval_results are not
+ * touched.  What an evaluation uses is what every search on the stream uses:
+ * the engine's tree buffers and search io.  Nothing crosses PCIe.
+ *   mz_test_config: a handle setting like mz_expert_depth (mz_selfplay_init
+ *     and mz_snapshot_load keep it): E = games test slots (1..max_games; 0 =
+ *     off, which frees nothing until the next mz_selfplay_init), the opponent
+ *     MZ_OPP_* and muzero_player 1|2.  Refused as mz_selfplay_mode refuses:
+ *     before mz_selfplay_init, an unknown opponent, muzero_player outside
+ *     1..2, EXPERT / NETWORK on the frame-stack env, NETWORK before the
+ *     opponent set is complete.
+ *   mz_test_play: one evaluation, stream-ordered, no host synchronisation.
+ *     Every test slot g starts a new game as mz_selfplay_init plus the first
+ *     mz_selfplay_move would start slot g (boards: empty, player 1; the
+ *     Atari-like env: mz_sp_reset's draw keyed by game_offset + g), then
+ *     T = max_moves + 1 moves are enqueued.  Move m is what
+ *     mz_selfplay_move(rng_step0 + m, game_offset, temperature) does in
+ *     MZ_SP_EVAL mode with the configured opponent and muzero_player, with the
+ *     weights mz_net_forward would use at this point of the stream
+ *     (temperature_threshold applies as there).  A slot whose game has ended
+ *     (done, or more than max_moves moves) is frozen for the rest of the
+ *     evaluation: neither restarted nor stored, nothing more of it recorded;
+ *     its search row is the dummy row of the Reanalyse rounds (zero
+ *     observation, every action legal, to_play 1).  The host never learns when
+ *     every slot is done: it always enqueues T moves, each followed by one
+ *     launch of mz_test_tally in place of mz_sp_order / mz_sp_store.  So slot
+ *     g's game is, bit for bit, the first game slot g plays after
+ *     mz_selfplay_init(env, E, E) + mz_selfplay_mode(MZ_SP_EVAL, opponent,
+ *     muzero_player) + those moves, and what the host mirror's
+ *     BatchedSelfPlay(...).play_games() returns.  With mz_debug_enable(h, 1)
+ *     the dumped tree is the evaluation's last search's.  The test slots are
+ *     allocated by the first call after each mz_selfplay_init /
+ *     mz_snapshot_load.  Refused before mz_selfplay_init and with games == 0;
+ *     mz_test_config's refusals are checked again.
+ *     Each evaluation appends one record, kept in slot e % MZ_TEST_RECORDS of
+ *     a device ring that lives with the handle (mz_selfplay_init keeps it):
+ *       counts[8] = {training_step, games finished, MuZero wins, opponent
+ *                    wins, draws, moves, value_moves, rng_step0}
+ *       sums[3]   = {reward_muzero, reward_opponent, value_sum}
+ *     Winner and draw as mz_eval_results reads them; moves = the sum of the
+ *     game lengths.  MuZero's moves of a game are its records with to_play ==
+ *     muzero_player, and every record when the opponent is MZ_OPP_SELF or
+ *     players == 1: reward_muzero sums their rewards, value_sum their stored
+ *     root values (value_moves counts them), reward_opponent the other
+ *     records' rewards.  The numerics are part of the contract: each game's
+ *     three sums are f64, start at +0 and add (double)x in record order, and
+ *     the record adds the finished games' sums in (move, ascending slot)
+ *     order; selfplay.evaluation_record is the exact host mirror.
+ *   mz_test_results: the latest min(max_records, held) records, oldest first
+ *     (held = min(total, MZ_TEST_RECORDS)); *total = evaluations since create
+ *     / mz_test_clear; counts [n][8], sums [n][3]; any pointer may be NULL.
+ *     Synchronises.  mz_test_clear: total back to 0.
+ *   mz_test_get_game (parity): test slot `slot`'s game of the last evaluation,
+ *     layouts of mz_replay_get_game; synchronises.                            */
+enum { MZ_TEST_RECORDS = 1024 };
+int mz_test_config(mz_handle* h, int32_t games, int opponent, int muzero_player);
+int mz_test_play(mz_handle* h, int64_t training_step, uint32_t rng_step0, uint32_t game_offset,
+                 float temperature, void* stream);
+int mz_test_results(mz_handle* h, int64_t* total, int64_t* counts, double* sums, int32_t max_records);
+int mz_test_clear(mz_handle* h);
+int mz_test_get_game(mz_handle* h, int32_t slot, int32_t* T, uint8_t* obs, int32_t* actions, float* rewards,
+                     int32_t* to_play, float* child_visits, float* root_values);
+
 /* The shard's counters {num_played_games, num_played_steps, total_samples}
  * (ReplayBuffer.jl:133-161) and the games it holds; synchronises.          */
 int mz_replay_counts(mz_handle* h, int64_t* counts, int32_t* games_in_buffer);
@@ -659,6 +726,21 @@ int mz_replay_reanalyse_seek(mz_handle* h, int64_t game_number, void* stream);
  *     (the default): no round, every launch as without the call.  Refused:
  *     rounds_per_move < 0, an unknown mode, and what mz_replay_reanalyse_next
  *     refuses.  The setting stays with the handle.
+ *   mz_train_set_test: the test worker inside mz_train_run.  With interval > 0,
+ *     after a move's learner steps took the learner from step t0 to t1 with
+ *     t1 / interval > t0 / interval, the loop runs one evaluation:
+ *     mz_test_play(h, t1, (uint32_t)t1 * (uint32_t)(max_moves + 1),
+ *     game_offset, temperature, stream).  The move's learner steps run as one
+ *     chunk and the chunk is not cut: the evaluation sees the nets after the
+ *     move's last step (the latest-weights behaviour of an asynchronous test
+ *     worker), at the point of the stream where the next move's Reanalyse
+ *     rounds search with them too.  mz_train_move / mz_train_learn never
+ *     evaluate; the split-loop host calls mz_test_play itself.  At world > 1
+ *     every rank evaluates its own games: the condition is rank-invariant and
+ *     nothing is exchanged.  interval 0 (the default): no evaluation, every
+ *     launch as without the call.  Refused: a negative interval, and an
+ *     interval > 0 with no test slots configured (mz_test_config; checked
+ *     again by the evaluation).  The setting stays with the handle.
  *   mz_train_set_networks_path: conf.networks_path (Constructors.jl:47) for
  *     the periodic checkpoints; NULL or "" (the default) writes none.
  *   mz_train_weights_get: the learner's, actors' or queued nets (Flux order).
@@ -668,6 +750,7 @@ int mz_train_init(mz_handle* h, int32_t batch_size);
 int mz_train_init_at(mz_handle* h, int32_t batch_size, int64_t t0);
 int mz_train_set_networks_path(mz_handle* h, const char* networks_path);
 int mz_train_set_reanalyse(mz_handle* h, int mode, int rounds_per_move, int exploration);
+int mz_train_set_test(mz_handle* h, int64_t interval, uint32_t game_offset, float temperature);
 int mz_train_run(mz_handle* h, int32_t moves, uint32_t move0, uint32_t game_offset, int64_t* state_out,
                  float* losses_dev, void* stream);
 int mz_train_move(mz_handle* h, uint32_t move, uint32_t game_offset, int64_t* nfin, void* stream);
@@ -716,6 +799,9 @@ int mz_checkpoint_load(mz_handle* h, const char* path, int64_t* training_step);
  * written into the metadata for information, and the loading host applies its
  * own (its mz_selfplay_mode, mz_expert_depth and opponent weight set survive
  * the load; the depth and the opponent set are not written to the file).
+ * The test worker's settings (mz_test_config, mz_train_set_test) and its
+ * record ring are handle settings too: not written, and they survive the load;
+ * the test slots are re-created by the next mz_test_play.
  * At world > 1 each rank saves
  * and loads its own file; the host orders the calls.                          */
 int mz_snapshot_save(mz_handle* h, const char* path, int64_t training_step);

@@ -275,6 +275,38 @@ train_set_reanalyse!(e::Engine, mode::Cint; rounds_per_move=1, exploration=false
     check(e, ccall((:mz_train_set_reanalyse, libmz), Cint, (Ptr{Cvoid}, Cint, Cint, Cint),
                    e.h, mode, rounds_per_move, exploration ? 1 : 0))
 
+# ---- the test worker (muzero.jl:29-31's TODO; DESIGN §20): evaluation games on their own slots while a job trains
+test_config!(e::Engine, games; opponent::Cint=OPP_SELF, muzero_player=1) =
+    check(e, ccall((:mz_test_config, libmz), Cint, (Ptr{Cvoid}, Int32, Cint, Cint), e.h, games, opponent, muzero_player))
+# one evaluation with the current nets: every test slot plays one game, one record is appended (stream-ordered)
+test_play!(e::Engine, training_step, rng_step0; game_offset=0, temperature=0f0) =
+    check(e, ccall((:mz_test_play, libmz), Cint, (Ptr{Cvoid}, Int64, UInt32, UInt32, Float32, Ptr{Cvoid}),
+                   e.h, training_step, rng_step0, game_offset, temperature, C_NULL))
+# (evaluations so far, counts (8, n): training_step, games, MuZero wins, opponent wins, draws, moves, value_moves,
+#  rng_step0; sums (3, n): reward_muzero, reward_opponent, value_sum), the latest n records, oldest first
+function test_results(e::Engine; max_records=1024)
+    total = Ref{Int64}(0); counts = zeros(Int64, 8, max_records); sums = zeros(Float64, 3, max_records)
+    check(e, ccall((:mz_test_results, libmz), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Float64}, Int32),
+                   e.h, total, counts, sums, max_records))
+    n = min(max_records, total[], 1024)
+    total[], counts[:, 1:n], sums[:, 1:n]
+end
+test_clear!(e::Engine) = check(e, ccall((:mz_test_clear, libmz), Cint, (Ptr{Cvoid},), e.h))
+function test_get_game(e::Engine, slot, osz, A, max_moves)   # test slot `slot`'s game of the last evaluation
+    T = Ref{Int32}(0); M = max_moves + 1
+    obs = zeros(UInt8, osz, M); act = zeros(Int32, M); rew = zeros(Float32, M); tp = zeros(Int32, M)
+    cv = zeros(Float32, A, M); rv = zeros(Float32, M)
+    check(e, ccall((:mz_test_get_game, libmz), Cint,
+                   (Ptr{Cvoid}, Int32, Ref{Int32}, Ptr{UInt8}, Ptr{Int32}, Ptr{Float32}, Ptr{Int32}, Ptr{Float32},
+                    Ptr{Float32}), e.h, slot, T, obs, act, rew, tp, cv, rv))
+    n = T[]
+    (obs[:, 1:n], act[1:n], rew[1:n], tp[1:n], cv[:, 1:n], rv[1:n])
+end
+# train_run! then evaluates after every move whose learner steps crossed a multiple of `interval` (0, the default: never)
+train_set_test!(e::Engine, interval; game_offset=0, temperature=0f0) =
+    check(e, ccall((:mz_train_set_test, libmz), Cint, (Ptr{Cvoid}, Int64, UInt32, Float32),
+                   e.h, interval, game_offset, temperature))
+
 """The actor–learner loop of self_play! ‖ learning! (src/SelfPlay.jl:384-419,
 src/Learning.jl:306-438; quirk Q16) on one GPU: `moves` self-play moves with the
 actors' nets, one learner step per finished game, the actors one checkpoint behind.

@@ -22,6 +22,11 @@ TRAIN_LEARNER, TRAIN_ACTOR, TRAIN_QUEUED = 0, 1, 2
 LEARN_REF_SEMANTICS, LEARN_CORRECTED = 0, 1
 OPP_SELF, OPP_RANDOM, OPP_EXPERT, OPP_NETWORK = 0, 1, 2, 3
 REAN_OFF, REAN_BY_VALUE, REAN_BY_SEARCH = 0, 1, 2
+TEST_RECORDS = 1024                              # MZ_TEST_RECORDS: the test worker's record ring
+# one record of the test worker (mz_test_results): counts[8] then sums[3]
+TEST_COUNT_FIELDS = ("training_step", "games", "muzero_wins", "opponent_wins", "draws", "moves", "value_moves",
+                     "rng_step0")
+TEST_SUM_FIELDS = ("reward_muzero", "reward_opponent", "value_sum")
 
 _lib = None
 
@@ -78,6 +83,12 @@ SIGNATURES = {
     "mz_opponent_from": (ctypes.c_int, [_VP, ctypes.c_int, _VP]),
     "mz_opponent_load": (ctypes.c_int, [_VP, ctypes.c_char_p, _VP]),
     "mz_eval_results": (ctypes.c_int, [_VP, _VP]),
+    "mz_test_config": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int, ctypes.c_int]),
+    "mz_test_play": (ctypes.c_int, [_VP, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, _VP]),
+    "mz_test_results": (ctypes.c_int, [_VP, _VP, _VP, _VP, ctypes.c_int32]),
+    "mz_test_clear": (ctypes.c_int, [_VP]),
+    "mz_test_get_game": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mz_train_set_test": (ctypes.c_int, [_VP, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float]),
     "mz_replay_counts": (ctypes.c_int, [_VP, _VP, _VP]),
     "mz_replay_save_game": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mz_replay_sample": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(MzBatch), _VP, _VP]),
@@ -462,6 +473,61 @@ class Engine:
         out = np.zeros(4, np.int64)
         self._check(self.lib.mz_eval_results(self.h, _p(out)), "mz_eval_results")
         return tuple(int(x) for x in out)
+
+    # ---- the test worker: evaluation games on their own slots
+    def test_config(self, games, opponent=OPP_SELF, muzero_player=1):
+        """E = games test slots (0 = off), the opponent and MuZero's side: a handle setting."""
+        self._check(self.lib.mz_test_config(self.h, games, opponent, muzero_player), "mz_test_config")
+
+    def test_play(self, training_step, rng_step0, game_offset=0, temperature=0.0, stream=None):
+        """One evaluation: every test slot plays one game with the current nets (moves keyed rng_step0 + m,
+        game_offset); appends one record.  Stream-ordered, no host synchronisation."""
+        self._check(self.lib.mz_test_play(self.h, int(training_step), rng_step0 & 0xffffffff,
+                                          game_offset & 0xffffffff, temperature, stream), "mz_test_play")
+
+    def test_results(self, max_records=TEST_RECORDS):
+        """(evaluations since create / test_clear, the latest records oldest first): each record a dict of
+        TEST_COUNT_FIELDS (int) and TEST_SUM_FIELDS (np.float64).  Synchronises."""
+        total = ctypes.c_int64()
+        counts = np.zeros((max(max_records, 1), 8), np.int64)
+        sums = np.zeros((max(max_records, 1), 3), np.float64)
+        self._check(self.lib.mz_test_results(self.h, ctypes.byref(total), _p(counts), _p(sums), max_records),
+                    "mz_test_results")
+        n = min(max_records, total.value, TEST_RECORDS)
+        recs = []
+        for c, s in zip(counts[:n], sums[:n]):
+            r = {k: int(v) for k, v in zip(TEST_COUNT_FIELDS, c)}
+            r.update({k: np.float64(v) for k, v in zip(TEST_SUM_FIELDS, s)})
+            recs.append(r)
+        return int(total.value), recs
+
+    def test_clear(self):
+        self._check(self.lib.mz_test_clear(self.h), "mz_test_clear")
+
+    def test_get_game(self, slot):
+        """Test slot `slot`'s game of the last evaluation as a selfplay.GameHistory."""
+        from .selfplay import GameHistory
+        Tm = self.conf.max_moves + 1
+        T = ctypes.c_int32()
+        obs = np.zeros((Tm, self.osz), np.uint8)
+        act = np.zeros(Tm, np.int32)
+        rew = np.zeros(Tm, np.float32)
+        tp = np.zeros(Tm, np.int32)
+        cv = np.zeros((Tm, self.A), np.float32)
+        rv = np.zeros(Tm, np.float32)
+        self._check(self.lib.mz_test_get_game(self.h, slot, ctypes.byref(T), _p(obs), _p(act), _p(rew), _p(tp),
+                                              _p(cv), _p(rv)), "mz_test_get_game")
+        n = T.value
+        return GameHistory(observation_history=[o.astype(np.float32) for o in obs[:n]],
+                           action_history=[int(x) for x in act[:n]], reward_history=[float(x) for x in rew[:n]],
+                           to_play_history=[int(x) for x in tp[:n]], child_visits=[c for c in cv[:n]],
+                           root_values=[float(x) for x in rv[:n]])
+
+    def train_set_test(self, interval, game_offset=0, temperature=0.0):
+        """The test worker inside train_run: one evaluation after every move whose learner steps crossed a
+        multiple of `interval` (test_play(t1, t1 * (max_moves + 1), game_offset, temperature)); 0 = off."""
+        self._check(self.lib.mz_train_set_test(self.h, int(interval), game_offset & 0xffffffff, temperature),
+                    "mz_train_set_test")
 
     def replay_counts(self):
         """({num_played_games, num_played_steps, total_samples}, games held)."""

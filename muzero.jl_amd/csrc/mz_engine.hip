@@ -204,6 +204,22 @@ struct mz_handle {
     int sp_eval = 0, sp_opp = MZ_OPP_SELF, sp_mzp = 1;    // mz_selfplay_mode
     int sp_expert_depth = 0;                              // mz_expert_depth (0: the env's default)
     long long* d_eval = nullptr;                          // [4] evaluation tally
+    // the test worker (mz_test_*).  Handle settings: mz_test_config, mz_train_set_test.
+    // The record ring stays with the handle (allocated by the first mz_test_play); the test slots
+    // are self-play state (in sp_allocs, allocated by the first mz_test_play after a re-init).
+    int test_E = 0, test_opp = MZ_OPP_SELF, test_mzp = 1;
+    int64_t test_interval = 0; uint32_t test_goff = 0; float test_temp = 0.0f;
+    long long* d_test_counts = nullptr;                   // [MZ_TEST_RECORDS][8]
+    double* d_test_sums = nullptr;                        // [MZ_TEST_RECORDS][3]
+    int64_t test_total = 0;                               // evaluations since create / mz_test_clear
+    struct TestSlots {
+        int E = 0;                                        // 0: not allocated
+        bool played = false;                              // an evaluation's games are in `hist`
+        uint8_t* board = nullptr; int32_t* player = nullptr; uint8_t* over = nullptr; uint32_t* ekey = nullptr;
+        SpHist hist{};
+        int32_t* done = nullptr; int32_t* frozen = nullptr; float* temp = nullptr;
+        float* cv2 = nullptr; float* rv2 = nullptr; int32_t* act2 = nullptr;   // MZ_OPP_NETWORK's second outputs
+    } ts;
     float* d_sp_dpow = nullptr;
     float *d_rs_obs = nullptr, *d_rs_act = nullptr, *d_rs_tv = nullptr, *d_rs_tr = nullptr, *d_rs_tp = nullptr,
           *d_rs_gs = nullptr;
@@ -3153,7 +3169,9 @@ static int sp_alloc_hist(mz_handle* h, SpHist& r, size_t n) {
     return 0;
 }
 
-static SpParams sp_params(mz_handle* h) {
+// `test`: the rows are the test worker's slots (h->ts) in evaluation mode with mz_test_config's
+// opponent; the shard, the counters and the tally are not theirs (null: no launch of theirs reads them)
+static SpParams sp_params(mz_handle* h, bool test = false) {
     SpParams S;
     std::memset(&S, 0, sizeof(S));
     const mz_config& c = h->conf;
@@ -3168,6 +3186,14 @@ static SpParams sp_params(mz_handle* h) {
     S.eval = h->sp_eval; S.opponent = h->sp_opp; S.muzero_player = h->sp_mzp;
     S.seed = h->seed; S.eval_counts = h->d_eval;
     S.per = c.PER != 0; S.per_alpha = c.PER_alpha; S.td = c.td_steps; S.disc_pow = h->d_sp_dpow;
+    if (test) {
+        const mz_handle::TestSlots& t = h->ts;
+        S.G = t.E;
+        S.board = t.board; S.player = t.player; S.over = t.over; S.ekey = t.ekey;
+        S.hist = t.hist; S.done = t.done; S.frozen = t.frozen;
+        S.ring = SpHist{}; S.cap = 0; S.counters = nullptr; S.ring_pos = nullptr; S.eval_counts = nullptr;
+        S.eval = 1; S.opponent = h->test_opp; S.muzero_player = h->test_mzp;
+    }
     return S;
 }
 
@@ -3203,6 +3229,35 @@ static int opp_io(mz_handle* h) {
     MZ_TRY(h, spalloc(h, &h->d_cv2, G * h->A, false));
     MZ_TRY(h, spalloc(h, &h->d_rv2, G, false));
     MZ_TRY(h, spalloc(h, &h->d_act2, G, false));
+    return 0;
+}
+
+// One move of S's rows up to the commit, shared by mz_selfplay_move (the self-play slots) and
+// mz_test_play (the test slots): mz_sp_prepare -> the search on the engine's io with the handle's
+// current nets -> mz_expert_move, or the opponent's search (outputs cv2 / rv2 / act2) and mz_sp_pick
+// -> mz_sp_commit.  The keys, the temperature and the mode are S's.
+static int sp_move_body(mz_handle* h, const SpParams& S, float* cv2, float* rv2, int32_t* act2, hipStream_t st) {
+    const int G = S.G;
+    const dim3 waves((G + 3) / 4);
+    hipLaunchKernelGGL(mz_sp_prepare, waves, dim3(256), 0, st, S);
+    MZ_TRY(h, hipGetLastError());
+    int rc = search_dev(h, G, h->d_obs, h->d_legal, h->d_tp, 1, S.step, S.game_offset, S.temperature, h->d_cv,
+                        h->d_rv, h->d_act, st, S.temp_g);
+    if (rc) return rc;
+    if (S.eval && S.opponent == MZ_OPP_EXPERT) {     // the expert's turns: its move replaces the search's action
+        ExpertArgs X{expert_depth_of(h, h->sp_env), h->d_act, nullptr};
+        hipLaunchKernelGGL(mz_expert_move, waves, dim3(256), 0, st, S, X);
+    }
+    if (S.eval && S.opponent == MZ_OPP_NETWORK) {    // the same search with the opponent's nets; its turns take
+        wset_swap(h, h->opp);                        // that search's whole result
+        rc = search_dev(h, G, h->d_obs, h->d_legal, h->d_tp, 1, S.step, S.game_offset, S.temperature, cv2, rv2, act2,
+                        st, S.temp_g);
+        wset_swap(h, h->opp);
+        if (rc) return rc;
+        PickArgs X{h->d_cv, h->d_rv, h->d_act, cv2, rv2, act2};
+        hipLaunchKernelGGL(mz_sp_pick, waves, dim3(256), 0, st, S, X);
+    }
+    hipLaunchKernelGGL(mz_sp_commit, waves, dim3(256), 0, st, S);
     return 0;
 }
 
@@ -3242,6 +3297,7 @@ int mz_selfplay_init(mz_handle* h, int env_kind, int G, int replay_games) {
     h->sp_ring.rcv = nullptr; h->d_rq_obs = nullptr;    // so were rcv and the reanalyse search's io
     h->d_rean_rows = nullptr; h->rean_rows_cap = 0;     // and the worker's row list
     h->d_cv2 = nullptr; h->d_rv2 = nullptr; h->d_act2 = nullptr;   // and MZ_OPP_NETWORK's second outputs
+    h->ts = mz_handle::TestSlots{};                     // and the test worker's slots (its settings and records stay)
     MZ_TRY(h, spalloc(h, &h->d_sp_counters, MZ_SP_COUNTERS));
     const long long cursor0 = 1;                        // the reanalyse cursor: game number 1
     MZ_TRY(h, hipMemcpy(h->d_sp_counters + MZ_REAN_CURSOR, &cursor0, sizeof(cursor0), hipMemcpyHostToDevice));
@@ -3302,25 +3358,7 @@ int mz_selfplay_move(mz_handle* h, uint32_t rng_step, uint32_t game_offset, floa
         MZ_TRY(h, hipGetLastError());
         h->sp_reset_pending = false;
     }
-    hipLaunchKernelGGL(mz_sp_prepare, waves, dim3(256), 0, st, S);
-    MZ_TRY(h, hipGetLastError());
-    int rc = search_dev(h, G, h->d_obs, h->d_legal, h->d_tp, 1, rng_step, game_offset, temperature, h->d_cv,
-                        h->d_rv, h->d_act, st, S.temp_g);
-    if (rc) return rc;
-    if (h->sp_eval && h->sp_opp == MZ_OPP_EXPERT) {  // the expert's turns: its move replaces the search's action
-        ExpertArgs X{expert_depth_of(h, h->sp_env), h->d_act, nullptr};
-        hipLaunchKernelGGL(mz_expert_move, waves, dim3(256), 0, st, S, X);
-    }
-    if (arena) {    // the same search with the opponent's nets; its turns take that search's whole result
-        wset_swap(h, h->opp);
-        rc = search_dev(h, G, h->d_obs, h->d_legal, h->d_tp, 1, rng_step, game_offset, temperature, h->d_cv2,
-                        h->d_rv2, h->d_act2, st, S.temp_g);
-        wset_swap(h, h->opp);
-        if (rc) return rc;
-        PickArgs X{h->d_cv, h->d_rv, h->d_act, h->d_cv2, h->d_rv2, h->d_act2};
-        hipLaunchKernelGGL(mz_sp_pick, waves, dim3(256), 0, st, S, X);
-    }
-    hipLaunchKernelGGL(mz_sp_commit, waves, dim3(256), 0, st, S);
+    if (int rc = sp_move_body(h, S, h->d_cv2, h->d_rv2, h->d_act2, st)) return rc;
     hipLaunchKernelGGL(mz_sp_order, dim3(1), dim3(1024), 0, st, S);
     hipLaunchKernelGGL(mz_sp_store, dim3(G), dim3(256), 0, st, S);
     MZ_TRY(h, hipGetLastError());
@@ -3399,6 +3437,144 @@ int mz_eval_results(mz_handle* h, int64_t* out4) {
     long long c[4];
     MZ_TRY(h, hipMemcpy(c, h->d_eval, sizeof(c), hipMemcpyDeviceToHost));
     for (int i = 0; i < 4; ++i) out4[i] = c[i];
+    return 0;
+}
+
+// ---- the test worker: evaluation games on their own slots
+// mz_selfplay_mode's refusals, for mz_test_config's setting (checked again by every mz_test_play:
+// the env and the opponent set may have changed since)
+static int test_check(mz_handle* h, int games, int opponent, int muzero_player) {
+    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
+    if (games < 0 || games > h->max_games) return fail(h, "mz_test_config: games must be in 0..max_games");
+    if (opponent != MZ_OPP_SELF && opponent != MZ_OPP_RANDOM && opponent != MZ_OPP_EXPERT && opponent != MZ_OPP_NETWORK)
+        return fail(h, "opponent must be MZ_OPP_SELF, MZ_OPP_RANDOM, MZ_OPP_EXPERT or MZ_OPP_NETWORK");
+    if (opponent == MZ_OPP_EXPERT && h->sp_env == MZ_ENV_ATARI) return fail(h, "expert: needs a two-player board env");
+    if (muzero_player != 1 && muzero_player != 2) return fail(h, "muzero_player must be 1 or 2");
+    if (opponent == MZ_OPP_NETWORK) {
+        if (h->sp_env == MZ_ENV_ATARI) return fail(h, "opponent network: needs a two-player board env");
+        if (h->opp_have != 7u)
+            return fail(h, "opponent: MZ_OPP_NETWORK needs the opponent's nets (mz_opponent_weights_set / _from / "
+                           "_load first)");
+    }
+    return 0;
+}
+
+// the test slots: self-play state (sp_allocs).  Nothing is zeroed: mz_test_begin starts every slot,
+// and every other word is written before it is read.
+static int test_alloc(mz_handle* h) {
+    mz_handle::TestSlots& t = h->ts;
+    const size_t E = (size_t)h->test_E, T = (size_t)h->sp_T, A = (size_t)h->A;
+    if (t.E != h->test_E) {                  // the first evaluation after a re-init, or another E since
+        t = mz_handle::TestSlots{};
+        MZ_TRY(h, spalloc(h, &t.board, E * h->sp_osz, false));
+        MZ_TRY(h, spalloc(h, &t.player, E, false));
+        MZ_TRY(h, spalloc(h, &t.over, E, false));
+        MZ_TRY(h, spalloc(h, &t.ekey, E, false));
+        MZ_TRY(h, spalloc(h, &t.hist.obs, E * T * h->sp_osz, false));
+        MZ_TRY(h, spalloc(h, &t.hist.act, E * T, false));
+        MZ_TRY(h, spalloc(h, &t.hist.rew, E * T, false));
+        MZ_TRY(h, spalloc(h, &t.hist.tp, E * T, false));
+        MZ_TRY(h, spalloc(h, &t.hist.cv, E * T * A, false));
+        MZ_TRY(h, spalloc(h, &t.hist.rv, E * T, false));
+        MZ_TRY(h, spalloc(h, &t.hist.len, E, false));
+        MZ_TRY(h, spalloc(h, &t.done, E, false));
+        MZ_TRY(h, spalloc(h, &t.frozen, E, false));
+        MZ_TRY(h, spalloc(h, &t.temp, E, false));
+        t.E = h->test_E;
+    }
+    if (h->test_opp == MZ_OPP_NETWORK && !t.act2) {
+        MZ_TRY(h, spalloc(h, &t.cv2, E * A, false));
+        MZ_TRY(h, spalloc(h, &t.rv2, E, false));
+        MZ_TRY(h, spalloc(h, &t.act2, E, false));
+    }
+    if (!h->d_test_counts) {                 // the record ring: the handle's
+        MZ_TRY(h, dalloc(h, &h->d_test_counts, (size_t)MZ_TEST_RECORDS * 8));
+        MZ_TRY(h, dalloc(h, &h->d_test_sums, (size_t)MZ_TEST_RECORDS * 3));
+    }
+    return 0;
+}
+
+int mz_test_config(mz_handle* h, int32_t games, int opponent, int muzero_player) {
+    if (!h) return -2;
+    if (int rc = test_check(h, games, opponent, muzero_player)) return rc;
+    h->test_E = games; h->test_opp = opponent; h->test_mzp = muzero_player;
+    return 0;
+}
+
+int mz_test_play(mz_handle* h, int64_t training_step, uint32_t rng_step0, uint32_t game_offset, float temperature,
+                 void* stream) {
+    if (!h) return -2;
+    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
+    if (h->test_E < 1) return fail(h, "mz_test_play: no test slots (mz_test_config with games >= 1 first)");
+    if (int rc = test_check(h, h->test_E, h->test_opp, h->test_mzp)) return rc;
+    MZ_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream_of(h, stream);
+    if (test_alloc(h)) return -1;
+    const mz_handle::TestSlots& t = h->ts;
+    SpParams S = sp_params(h, true);
+    S.game_offset = game_offset; S.reset_step = 0xFFFFFFFFu;
+    S.temperature = temperature; S.temp_threshold = h->conf.temperature_threshold;
+    S.temp_g = h->conf.temperature_threshold >= 0 ? t.temp : nullptr;
+    const size_t slot = (size_t)(h->test_total % MZ_TEST_RECORDS);
+    TestRec R{h->d_test_counts + slot * 8, h->d_test_sums + slot * 3, (long long)training_step, rng_step0, t.frozen,
+              h->conf.players};
+    hipLaunchKernelGGL(mz_test_begin, dim3((t.E + 3) / 4), dim3(256), 0, st, S, R);
+    MZ_TRY(h, hipGetLastError());
+    // the host never learns when every slot is done: always T moves, the frozen slots as dummy rows
+    for (int m = 0; m < h->sp_T; ++m) {
+        S.step = rng_step0 + (uint32_t)m;
+        if (int rc = sp_move_body(h, S, t.cv2, t.rv2, t.act2, st)) return rc;
+        hipLaunchKernelGGL(mz_test_tally, dim3(1), dim3(1024), 0, st, S, R);
+        MZ_TRY(h, hipGetLastError());
+    }
+    h->ts.played = true;
+    ++h->test_total;
+    return 0;
+}
+
+int mz_test_results(mz_handle* h, int64_t* total, int64_t* counts, double* sums, int32_t max_records) {
+    if (!h) return -2;
+    if (max_records < 0) return fail(h, "mz_test_results: max_records must be >= 0");
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);
+    if (total) *total = h->test_total;
+    const int64_t held = std::min<int64_t>(h->test_total, MZ_TEST_RECORDS);
+    const int64_t n = std::min<int64_t>(max_records, held);
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t slot = (size_t)((h->test_total - n + i) % MZ_TEST_RECORDS);
+        long long c[8];
+        MZ_TRY(h, hipMemcpy(c, h->d_test_counts + slot * 8, sizeof(c), hipMemcpyDeviceToHost));
+        if (counts) for (int k = 0; k < 8; ++k) counts[i * 8 + k] = c[k];
+        if (sums) MZ_TRY(h, hipMemcpy(sums + i * 3, h->d_test_sums + slot * 3, 3 * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+int mz_test_clear(mz_handle* h) {
+    if (!h) return -2;
+    h->test_total = 0;
+    return 0;
+}
+
+int mz_test_get_game(mz_handle* h, int32_t slot, int32_t* T, uint8_t* obs, int32_t* actions, float* rewards,
+                     int32_t* to_play, float* child_visits, float* root_values) {
+    if (!h) return -2;
+    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
+    if (!h->ts.played) return fail(h, "mz_test_get_game: no evaluation since mz_selfplay_init (mz_test_play first)");
+    if (slot < 0 || slot >= h->ts.E) return fail(h, "mz_test_get_game: slot out of range");
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);
+    const size_t base = (size_t)slot * h->sp_T, A = (size_t)h->A;
+    const SpHist& r = h->ts.hist;
+    int32_t len = 0;
+    MZ_TRY(h, hipMemcpy(&len, r.len + slot, 4, hipMemcpyDeviceToHost));
+    if (T) *T = len;
+    if (obs) MZ_TRY(h, hipMemcpy(obs, r.obs + base * h->sp_osz, (size_t)len * h->sp_osz, hipMemcpyDeviceToHost));
+    if (actions) MZ_TRY(h, hipMemcpy(actions, r.act + base, (size_t)len * 4, hipMemcpyDeviceToHost));
+    if (rewards) MZ_TRY(h, hipMemcpy(rewards, r.rew + base, (size_t)len * 4, hipMemcpyDeviceToHost));
+    if (to_play) MZ_TRY(h, hipMemcpy(to_play, r.tp + base, (size_t)len * 4, hipMemcpyDeviceToHost));
+    if (child_visits) MZ_TRY(h, hipMemcpy(child_visits, r.cv + base * A, (size_t)len * A * 4, hipMemcpyDeviceToHost));
+    if (root_values) MZ_TRY(h, hipMemcpy(root_values, r.rv + base, (size_t)len * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -4418,6 +4594,15 @@ int mz_train_set_reanalyse(mz_handle* h, int mode, int rounds_per_move, int expl
     return 0;
 }
 
+int mz_train_set_test(mz_handle* h, int64_t interval, uint32_t game_offset, float temperature) {
+    if (!h) return -2;
+    if (interval < 0) return fail(h, "mz_train_set_test: interval must be >= 0");
+    if (interval > 0 && h->test_E < 1)
+        return fail(h, "mz_train_set_test: no test slots (mz_test_config with games >= 1 first)");
+    h->test_interval = interval; h->test_goff = game_offset; h->test_temp = temperature;
+    return 0;
+}
+
 int mz_selfplay_slots(mz_handle* h, int32_t* history_len, uint8_t* board, int32_t* player) {
     if (!h) return -2;
     if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
@@ -4716,8 +4901,16 @@ int mz_train_run(mz_handle* h, int32_t moves, uint32_t move0, uint32_t game_offs
         // data parallel (mz_dp_init): every rank takes the learner steps of the games all
         // ranks finished, so the replicas stay identical
         if (h->dp_comm && h->dp_world > 1 && dp_sum_count(h, &nfin, st)) return -1;
+        const int64_t t0 = h->tr_t;
         if (train_learn(h, nfin, losses_dev, st, &done)) return -1;
         steps += done;
+        // the test worker (mz_train_set_test): the move's learner steps crossed a multiple of the
+        // interval -> one evaluation with the learner's nets after the move's last step (the chunk is
+        // not cut), where the next move's Reanalyse rounds search with them too
+        const int64_t iv = h->test_interval, t1 = h->tr_t;
+        if (iv > 0 && t1 / iv > t0 / iv &&
+            mz_test_play(h, t1, (uint32_t)t1 * (uint32_t)h->sp_T, h->test_goff, h->test_temp, st))
+            return -1;
     }
     if (state_out) {
         state_out[0] = h->tr_t; state_out[1] = h->tr_games; state_out[2] = h->tr_refresh; state_out[3] = steps;

@@ -31,6 +31,7 @@ __device__ int expert_prefix(const ExpertPos& root, uint32_t legal1, int A, int 
 extern "C" __global__ __launch_bounds__(256) void mz_expert_move(SpParams S, ExpertArgs X) {
     const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (g >= S.G) return;
+    if (S.frozen && S.frozen[g]) return;                           // test worker: the slot's game is over
     const int player = S.player[g];
     if (!X.scores && player == S.muzero_player) return;           // MuZero's own turn: the search's action stands
     const int A = S.A, cells = S.osz / 3;

@@ -6,7 +6,10 @@
 // finished games in slot order, replay counters) -> mz_sp_store (finished
 // game -> replay ring, slot reset).  Nothing crosses PCIe.  MZ_OPP_NETWORK
 // searches twice and mz_sp_pick chooses per slot before the commit.  mz_rp_sample is
-// get_batch + make_target on the ring, writing an mz_batch in HBM.
+// get_batch + make_target on the ring, writing an mz_batch in HBM.  The test
+// worker plays its own slots with the same prepare / pick / commit
+// in their one-game mode (S.frozen), between mz_test_begin and, per move,
+// mz_test_tally in place of mz_sp_order / mz_sp_store.
 //
 // Env rules: TicTacToe exactly as games/tictactoe/game.jl with quirk Q14 (the
 // win test looks at the plane of the player TO MOVE; reward ±1 by the mover's
@@ -116,6 +119,15 @@ __device__ void env_reset(const SpParams& S, int g, int lane) {
 extern "C" __global__ __launch_bounds__(256) void mz_sp_prepare(SpParams S) {
     const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (g >= S.G) return;
+    if (S.frozen && S.frozen[g]) {                                 // test worker: the game is over, the dummy row
+        for (int k = lane; k < S.F; k += 64) S.obs[(size_t)g * S.F + k] = 0.0f;
+        for (int a = lane; a < S.A; a += 64) S.legal[(size_t)g * S.A + a] = 1;
+        if (lane == 0) {
+            S.tp[g] = 1;
+            if (S.temp_g) S.temp_g[g] = 0.0f;
+        }
+        return;
+    }
     const int t = S.hist.len[g];                                   // moves so far
     uint8_t* ho = S.hist.obs + ((size_t)g * S.T + t) * S.osz;     // observation_history append (:352)
     const uint8_t* b = S.board + (size_t)g * S.osz;
@@ -145,6 +157,7 @@ extern "C" __global__ __launch_bounds__(256) void mz_sp_prepare(SpParams S) {
 extern "C" __global__ __launch_bounds__(256) void mz_sp_pick(SpParams S, PickArgs X) {
     const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (g >= S.G) return;
+    if (S.frozen && S.frozen[g]) return;
     if (S.player[g] == S.muzero_player) return;
     for (int a = lane; a < S.A; a += 64) X.cv[(size_t)g * S.A + a] = X.cv2[(size_t)g * S.A + a];
     if (lane == 0) { X.act[g] = X.act2[g]; X.rv[g] = X.rv2[g]; }
@@ -153,6 +166,7 @@ extern "C" __global__ __launch_bounds__(256) void mz_sp_pick(SpParams S, PickArg
 extern "C" __global__ __launch_bounds__(256) void mz_sp_commit(SpParams S) {
     const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (g >= S.G) return;
+    if (S.frozen && S.frozen[g]) return;                           // test worker: nothing of a finished game is recorded
     const int t = S.hist.len[g];
     const size_t r = (size_t)g * S.T + t;
     for (int a = lane; a < S.A; a += 64) S.hist.cv[r * S.A + a] = S.cv[(size_t)g * S.A + a];   // :375-379
@@ -202,6 +216,89 @@ extern "C" __global__ __launch_bounds__(256) void mz_sp_commit(SpParams S) {
 extern "C" __global__ __launch_bounds__(256) void mz_sp_reset(SpParams S) {
     const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (g < S.G) atari_reset(S, g, S.reset_step, lane);
+}
+
+// ------------------------------------------------------------ test worker
+// (mz_test_play): E test slots play one evaluation game each with
+// the kernels above in their one-game mode (S.frozen).  mz_test_begin starts
+// every slot's game as mz_selfplay_init plus the first move would (boards:
+// empty, player 1; the Atari-like env: mz_sp_reset's draw) and opens the
+// evaluation's record; one wave per slot.
+extern "C" __global__ __launch_bounds__(256) void mz_test_begin(SpParams S, TestRec R) {
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (blockIdx.x == 0 && threadIdx.x < 8)
+        R.counts[threadIdx.x] = threadIdx.x == 0 ? R.training_step : threadIdx.x == 7 ? (long long)R.rng_step0 : 0ll;
+    if (blockIdx.x == 0 && threadIdx.x < 3) R.sums[threadIdx.x] = 0.0;
+    if (g >= S.G) return;
+    if (S.env == MZ_ENV_ATARI) atari_reset(S, g, S.reset_step, lane);
+    else env_reset(S, g, lane);
+    if (lane == 0) { S.hist.len[g] = 0; S.done[g] = 0; R.frozen[g] = 0; }
+}
+
+// Behind mz_sp_commit, in place of mz_sp_order / mz_sp_store: the games that
+// ended on this move go into the record and their slots freeze.  One
+// workgroup, 1024 slots per pass.  Every lane sums its own game's records
+// serially in f64 (+0, then + (double)x in record order); wave 0 then adds the
+// finished games to the record in ascending slot order — a ballot per 64 slots
+// finds them, every lane reads the same LDS entry, so each lane's chain of adds
+// is the serial one and lane 0 stores it.  No float atomics: the host mirror
+// (selfplay.evaluation_record) is exact.
+extern "C" __global__ __launch_bounds__(1024) void mz_test_tally(SpParams S, TestRec R) {
+    __shared__ double gs[3][1024];
+    __shared__ int gi[3][1024];                    // 0 not finished | 1 MuZero won | 2 the opponent | 3 draw; length; MuZero's moves
+    const int tid = threadIdx.x, lane = tid & 63;
+    const bool every = S.opponent == MZ_OPP_SELF || R.players == 1;   // every record is MuZero's
+    long long games = 0, won = 0, lost = 0, draws = 0, moves = 0, vmoves = 0;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    if (tid < 64) {
+        games = R.counts[1]; won = R.counts[2]; lost = R.counts[3]; draws = R.counts[4];
+        moves = R.counts[5]; vmoves = R.counts[6];
+        s0 = R.sums[0]; s1 = R.sums[1]; s2 = R.sums[2];
+    }
+    for (int base = 0; base < S.G; base += 1024) {
+        const int g = base + tid;
+        int cls = 0, len = 0, vm = 0;
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+        if (g < S.G && !R.frozen[g] && S.done[g]) {
+            len = S.hist.len[g];                   // 1..T (mz_sp_commit)
+            const size_t r0 = (size_t)g * S.T;
+            for (int k = 0; k < len; ++k) {
+                const float rew = S.hist.rew[r0 + k];
+                if (every || S.hist.tp[r0 + k] == S.muzero_player) {
+                    a0 = a0 + (double)rew;
+                    a2 = a2 + (double)S.hist.rv[r0 + k];
+                    ++vm;
+                } else {
+                    a1 = a1 + (double)rew;
+                }
+            }
+            const int w = game_winner(S, S.hist.rew[r0 + len - 1], S.hist.tp[r0 + len - 1]);
+            cls = w == 0 ? 3 : w == S.muzero_player ? 1 : 2;
+            R.frozen[g] = 1;
+        }
+        gs[0][tid] = a0; gs[1][tid] = a1; gs[2][tid] = a2;
+        gi[0][tid] = cls; gi[1][tid] = len; gi[2][tid] = vm;
+        __syncthreads();
+        if (tid < 64) {
+            for (int ch = 0; ch < 1024 && base + ch < S.G; ch += 64) {
+                uint64_t m = __ballot(gi[0][ch + lane] != 0);
+                while (m) {
+                    const int k = ch + __builtin_ctzll(m);
+                    m &= m - 1;
+                    const int c = gi[0][k];
+                    games += 1; won += c == 1; lost += c == 2; draws += c == 3;
+                    moves += gi[1][k]; vmoves += gi[2][k];
+                    s0 = s0 + gs[0][k]; s1 = s1 + gs[1][k]; s2 = s2 + gs[2][k];
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        R.counts[1] = games; R.counts[2] = won; R.counts[3] = lost; R.counts[4] = draws;
+        R.counts[5] = moves; R.counts[6] = vmoves;
+        R.sums[0] = s0; R.sums[1] = s1; R.sums[2] = s2;
+    }
 }
 
 // Ring slots of this move's finished games in slot order (the host driver

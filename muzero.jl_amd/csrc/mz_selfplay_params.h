@@ -102,6 +102,22 @@ struct SpParams {
     // as play_game(env, temperature, ...) takes it once per game (SelfPlay.jl:396-407);
     // tgame [G] holds it (nullptr: every move uses `temperature`)
     float* tgame;
+    // the test worker's one-game mode (mz_test_play): frozen[g] != 0 marks a slot whose
+    // game of this evaluation has ended.  Its search row is the dummy row of mz_reanalyse_sgather
+    // (zero observation, every action legal, to_play 1) and mz_sp_commit / mz_expert_move / mz_sp_pick
+    // leave it alone.  nullptr (every other launch): no slot is frozen.
+    const int32_t* frozen;
+};
+
+// mz_test_begin / mz_test_tally (mz_selfplay.hip): the evaluation's record in the handle's ring
+struct TestRec {
+    long long* counts;          // [8] training_step, games, muzero wins, opponent wins, draws, moves, value_moves,
+                                //     rng_step0
+    double* sums;               // [3] reward_muzero, reward_opponent, value_sum
+    long long training_step;    // mz_test_begin stamps these two
+    uint32_t rng_step0;
+    int32_t* frozen;            // [G] the slots' flags (SpParams::frozen, writable)
+    int players;                // conf.players: with 1 every record is MuZero's
 };
 
 // mz_expert_move (mz_expert.hip): the rules-search expert opponent.  The rows are SpParams'
@@ -149,6 +165,8 @@ extern "C" __global__ void mz_sp_store(SpParams S);
 extern "C" __global__ void mz_sp_reset(SpParams S);
 extern "C" __global__ void mz_expert_move(SpParams S, ExpertArgs X);
 extern "C" __global__ void mz_sp_pick(SpParams S, PickArgs X);
+extern "C" __global__ void mz_test_begin(SpParams S, TestRec R);
+extern "C" __global__ void mz_test_tally(SpParams S, TestRec R);
 extern "C" __global__ void mz_rp_sample(RpSampleParams Q);
 extern "C" __global__ void mz_rp_per_init(SpHist ring, int slot, int len, int Tmax, int td, const float* disc_pow,
                                           int alpha);

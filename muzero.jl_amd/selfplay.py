@@ -212,6 +212,57 @@ class BatchedSelfPlay:
         return results
 
 
+def evaluation_record(histories, env_name, opponent, muzero_player, players, training_step=0, rng_step0=0):
+    """The test worker's record of one evaluation (mz_test_play) from its games, one finished
+    GameHistory per slot in slot order: the exact mirror of mz_test_tally, integers and float64 bits.
+    Each game's three sums are float64, start at +0 and add float64(x) in record order; the record adds
+    the games' sums in (move on which the game ended, ascending slot) order.  MuZero's moves are the
+    records with to_play == muzero_player, every record when the opponent is "self" or players == 1."""
+    every = opponent == "self" or players == 1
+    rec = dict(training_step=int(training_step), games=0, muzero_wins=0, opponent_wins=0, draws=0, moves=0,
+               value_moves=0, rng_step0=int(rng_step0) & 0xffffffff, reward_muzero=np.float64(0.0),
+               reward_opponent=np.float64(0.0), value_sum=np.float64(0.0))
+    for g in sorted(range(len(histories)), key=lambda g: (len(histories[g].action_history), g)):
+        h = histories[g]
+        mine, theirs, values, vm = np.float64(0.0), np.float64(0.0), np.float64(0.0), 0
+        for rew, tp, rv in zip(h.reward_history, h.to_play_history, h.root_values):
+            if every or tp == muzero_player:
+                mine = mine + np.float64(np.float32(rew))
+                values = values + np.float64(np.float32(rv))
+                vm += 1
+            else:
+                theirs = theirs + np.float64(np.float32(rew))
+        w = game_winner(env_name, h.reward_history[-1], h.to_play_history[-1])
+        rec["games"] += 1
+        rec["draws" if w == 0 else "muzero_wins" if w == muzero_player else "opponent_wins"] += 1
+        rec["moves"] += len(h.action_history)
+        rec["value_moves"] += vm
+        rec["reward_muzero"] = rec["reward_muzero"] + mine
+        rec["reward_opponent"] = rec["reward_opponent"] + theirs
+        rec["value_sum"] = rec["value_sum"] + values
+    return rec
+
+
+def env_name_of(env_cls):
+    """game_winner's name of a batched env class: "tictactoe", "connect4" or "atari"."""
+    if getattr(env_cls, "FRAME_STACK", 0):
+        return "atari"
+    return "tictactoe" if env_cls(1).board.shape[1] == 27 else "connect4"
+
+
+def evaluate(engine, env_cls, E, opponent="self", muzero_player=1, rng_step0=0, game_offset=0, temperature=0.0,
+             training_step=0, expert_depth=None, opponent_engine=None):
+    """One evaluation of the test worker on the host: E slots play one game each (move m keyed
+    rng_step0 + m, game_offset); returns (the histories in slot order, their evaluation_record)."""
+    sp = BatchedSelfPlay(engine, env_cls, E, game_offset=game_offset, step0=rng_step0, opponent=opponent,
+                         muzero_player=muzero_player, expert_depth=expert_depth, opponent_engine=opponent_engine)
+    histories = sp.play_games(temperature)
+    players = engine.conf.players                      # Config.players lists the player ids
+    return histories, evaluation_record(histories, env_name_of(env_cls), opponent, muzero_player,
+                                        players if isinstance(players, int) else len(players), training_step,
+                                        rng_step0)
+
+
 def random_positions(env_cls, G, seed=0, max_plies=6):
     """Real positions for benchmarking (any env with [p1, p2, empty] board
     planes, stacked_observations = 1): random legal play from the initial
