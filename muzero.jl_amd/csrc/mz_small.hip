@@ -37,10 +37,21 @@
 // written to the second half of the stamps array (blocks gridDim.x + b)
 #define W_STAMP0() unsigned long long w_t0_ = __builtin_amdgcn_s_memtime()
 #define W_STAMP(k) do { w_acc[k] += __builtin_amdgcn_s_memtime() - w_t0_; } while (0)
+// the search prologue's marks, ticks since the kernel's first instruction, on thread 0 and on the
+// first thread of slot 1 (wave 4): 0 image issued, 1 tables in LDS, 2 noise done, 3 representation
+// done, 4 reload issued, 5 root prediction done, 6 root expand done.  Packed 21 bits each, three
+// to a slot, into slots 3..7 of the per-wave rows: thread 0's seven in slots 3..5, thread 256's
+// marks 0..5 in slots 6..7 (its mark 6 follows a workgroup barrier: thread 0's)
+#define P_MARK(i)                                                                \
+    do {                                                                         \
+        if ((threadIdx.x & 255) == 0)                                            \
+            p_mark[i] = (__builtin_amdgcn_s_memtime() - p_t0) & 0x1fffffull;     \
+    } while (0)
 #else
 #define SM_STAMP(i) do {} while (0)
 #define W_STAMP0() do {} while (0)
 #define W_STAMP(k) do {} while (0)
+#define P_MARK(i) do {} while (0)
 #endif
 
 // Thread -> (slot, slot row, quarter): see the header comment.
@@ -236,12 +247,57 @@ __device__ __forceinline__ void sm_load(int k0, int k1, const float* W, float (&
     }
 }
 
+// One register set from image stage `stage` of W, chunks by `mask` (the wave's nonzero-chunk
+// mask of that stage; a clear chunk reads the zero line, as sm_load).  No run-time range test:
+// the search prologue selects the source, never whether a load is issued.
+__device__ __forceinline__ void sm_load_set(float (&w)[16], const float* W, int stage, uint32_t mask,
+                                            const float4* zero16) {
+    const int tid = threadIdx.x, sl = tid >> 8, t = tid & 255, q = (tid >> 4) & 3;
+    const float4* src = reinterpret_cast<const float4*>(W + (((size_t)stage * SM_SLOTS + sl) * 4) * 1024) + t;
+    const uint32_t m = mask >> (4 * q);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float4 v = *((m >> i) & 1u ? src + i * 256 : zero16);
+        w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+    // sets issue in program order on every path that loads them (a scheduler that moves one
+    // set's loads behind another's on one path makes the merged wait count the worst order)
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// sm_run for the search prologue's root prediction (FI = 0, OFF = 0), with the reload of the
+// register sets the representation ran on spread over the stages: a wave with `reload` set
+// issues set K + LEAD (sim stage K + LEAD of W, mask mk[K + LEAD]) in front of stage K.
+template <int T, int BNM, int LEAD, int K = 0>
+__device__ __forceinline__ void sm_run_reload_k(int n, float (&wr)[SM_MAX_SIM][16], int4 R, int xo, const int4* rec,
+                                                float* lds, const float2* bnp, bool reload, const float* W,
+                                                const uint32_t (&mk)[SM_MAX_SIM], const float4* zero16) {
+    if constexpr (K < SM_MAX_SIM) {
+        if (K < n) {
+            if constexpr (K + LEAD < SM_MAX_SIM)
+                if (reload) sm_load_set(wr[K + LEAD], W, K + LEAD, mk[K + LEAD], zero16);
+            const int4 Rn = sm_stage<T, 0, BNM>(wr[K], R, xo, rec + (K + 1) * (SM_SLOTS * 64), lds, nullptr,
+                                                bnp + K * (SM_SLOTS * 64));
+            sm_run_reload_k<T, BNM, LEAD, K + 1>(n, wr, Rn, xo, rec, lds, bnp, reload, W, mk, zero16);
+        }
+    }
+}
+template <int T, int BNM, int LEAD>
+__device__ __forceinline__ void sm_run_reload(int n, float (&wr)[SM_MAX_SIM][16], const int4* rec, float* lds,
+                                              const float2* bnp, bool reload, const float* W,
+                                              const uint32_t (&mk)[SM_MAX_SIM], const float4* zero16) {
+    const int4 R0 = rec[0];
+    sm_run_reload_k<T, BNM, LEAD>(n, wr, R0, sm_xoff<T>(R0), rec, lds, bnp, reload, W, mk, zero16);
+}
+
 template <int T, int BNM>
 __device__ __forceinline__ void small_body(const SmallParams& P) {
 #ifdef MZ_STAMPS
     unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long st_last = __builtin_amdgcn_s_memtime();
     unsigned long long w_acc[3] = {0, 0, 0};
+    const unsigned long long p_t0 = st_last;
+    unsigned long long p_mark[7] = {0, 0, 0, 0, 0, 0, 0};
 #endif
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int A = P.A, S = P.S, H = P.H;
@@ -308,62 +364,174 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
     const float2* bn_sim = bnl + sm_slot_row(tid);
     const float2* bn_root = bn_sim + P.n_sim * (SM_SLOTS * 64);
 
-    // ---- weight-image loads first: in flight under the setup copies.  The
-    // representation (SelfPlay.jl:234) runs on its own schedule; the sim
-    // stages it leaves free are preloaded, the rest reloaded after it.
+    // ---- the launch prologue.  A wave's vector loads issue no faster than the CU
+    // streams them (~28 B/clock; the image is ~256 KiB), so what follows a wave's image loads in
+    // program order runs after most of them have landed.  Hence:
+    //  * every wave but one loads its setup values (tables, stage records, biases, root inputs)
+    //    in front of its part of the image and consumes them behind its issue: a wave's loads
+    //    return in order, so none of them waits for a weight (unroll_body's form);
+    //  * one wave, NW, loads nothing but the legal bytes and draws the root's exploration noise
+    //    (Philox, f64 log / exp, a rejection loop: as long as the image's stream, and dependent
+    //    on the legal set alone) while the other seven stream and copy;
+    //  * the representation (SelfPlay.jl:234) runs on register sets RO .. RO + n_root, so a wave
+    //    with rows in it loads the root stages there first, then the sim stages 0 .. RO-1, on
+    //    which the root prediction starts while sets RO .. are reloaded under it;
+    //  * a wave with no row in any root stage (all its root masks clear: its records there have
+    //    .z = -1, no sum of its is kept) holds the sim stages in all sets from the start, only
+    //    counts itself in at the representation's barriers, and takes no part in the reload.
+    // NW is a wave of the last slot (the schedule fills slot 0 first, so it has no root rows and
+    // its image is issued behind the first barrier, under the representation); with root rows it
+    // would load in front of that barrier.  Loads are selected by source, not skipped, inside a
+    // path, so the waits in front of the stages stay counted.
+    constexpr int NW = 4 * (SM_SLOTS - 1);
+    static_assert(NW >= 4, "the noise wave is not one of the first slot's");
+    constexpr int CT = SM_THREADS - 64;                               // the copying threads
+    const int ci = tid < 64 * NW ? tid : tid - 64;                    // this thread among them
+    constexpr int RO = SM_MAX_SIM - SM_MAX_ROOT;
     float wr[SM_MAX_SIM][16];
-    sm_load<SM_MAX_SIM>(0, P.n_root, P.w_root, wr, P.nzm + P.n_sim, P.zero16);
-    sm_load<SM_MAX_SIM>(P.n_root, P.n_sim, P.w_sim, wr, P.nzm, P.zero16);
-    for (int i = tid; i < P.act_total; i += SM_THREADS) act[i] = 0.0f;
-    for (int i = tid; i < S + 2; i += SM_THREADS) { l_pbc[i] = P.pbc_tab[i]; l_sqrt[i] = P.sqrt_tab[i]; }
-    if (tid < A) l_aval[tid] = P.aval_tab[tid];
-    for (int i = tid; i < (int)pbterm_count(S); i += SM_THREADS) l_pbterm[i] = P.pbterm[i];
-    for (int i = tid; i < nrec * SM_REC_INTS; i += SM_THREADS) rec[i] = P.rec[i];
-    __syncthreads();
-    for (int i = tid; i < nrec * SM_SLOTS * 64; i += SM_THREADS)
-        rec[4 * i + 3] = __float_as_int(P.bias[i]);
-    if (P.bn)
-        for (int i = tid; i < nrec * SM_SLOTS * 64; i += SM_THREADS)
-            bnl[i] = make_float2(P.bias[nrec * SM_SLOTS * 64 + i], P.bias[2 * nrec * SM_SLOTS * 64 + i]);
-    // ---- root inputs
-    for (int i = tid; i < T * P.obs_feat; i += SM_THREADS) {
-        const int gl = i / P.obs_feat, k = i - gl * P.obs_feat;
-        const int ggl = tile0 + gl;
-        act[P.x_rep + k * T + gl] = ggl < P.G ? P.obs[(size_t)ggl * P.obs_feat + k] : 0.0f;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    uint32_t mk_sim[SM_MAX_SIM], mk_root[SM_MAX_ROOT];                // the wave's masks (scalar loads)
+    uint32_t any_root = 0;
+#pragma unroll
+    for (int k = 0; k < SM_MAX_SIM; ++k) mk_sim[k] = k < P.n_sim ? P.nzm[wv * SM_NZM_ST + k] : 0u;
+#pragma unroll
+    for (int k = 0; k < SM_MAX_ROOT; ++k) {
+        mk_root[k] = k < P.n_root ? P.nzm[wv * SM_NZM_ST + P.n_sim + k] : 0u;
+        any_root |= mk_root[k];
     }
-    for (int i = tid; i < T * NN; i += SM_THREADS) c_cache[i] = make_uint2(0u, 0u);
-    if (tid < 4) { c_hdr[tid] = make_int4(0, -1, 1, 0); c_mmx[tid] = make_float2(0.0f, 0.0f); c_skip[tid] = 0; }
-    if (tid < T && sel_ballot) c_stat[tid * NNS] = node_static(0, 0, 0, 1ull);   // the root: anc[0] = 1
+    const bool root_wave = any_root != 0;
+    auto image = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < SM_MAX_SIM; ++j) {
+            const int k = j < SM_MAX_ROOT ? j + RO : j - SM_MAX_ROOT;    // sets RO .. first, then 0 .. RO-1
+            const bool rs = root_wave && k >= RO;                         // a root stage, or (past n_root) nothing yet
+            sm_load_set(wr[k], rs ? P.w_root : P.w_sim, rs ? k - RO : k,
+                        rs ? mk_root[k >= RO ? k - RO : 0] : mk_sim[k], P.zero16);
+        }
+        P_MARK(0);
+    };
     int ver = 1;                                                  // wave 0: the tag of this lane's game
-    if (tree_thread && a == 0) {
-        uint32_t m = 0;
-        if (active)
-            for (int b = 0; b < A; ++b) if (P.legal[(size_t)gg * A + b]) m |= 1u << b;
-        sg_legal[g] = m;
-        sg_root_tp[g] = active ? P.to_play[gg] : 1;
-        sg_rootN[g] = 0; sg_rootW[g] = 0.0f;
-        sg_mmin[g] = INFINITY; sg_mmax[g] = -INFINITY;          // MinMaxStats(Inf, -Inf), SelfPlay.jl:251
-        sg_leaf_e[g] = 0; sg_leaf_a[g] = 0; sg_vtp[g] = 1; sg_depth[g] = 0;
+    if (wv != NW) {
+        const int nri = nrec * SM_SLOTS * 64;                         // int4 records (one per slot row)
+        constexpr int RPT = ((SM_MAX_SIM + SM_MAX_ROOT) * SM_SLOTS * 64 + CT - 1) / CT;
+        constexpr int PBT = 2;                   // pb_term pairs per thread held in registers (S <= 57)
+        const int npb = (int)pbterm_count(S), npb2 = npb >> 1;
+        // (a larger search: what the register batches do not hold is copied first, on its own round trip)
+        for (int i = ci + PBT * CT; i < npb2; i += CT)
+            reinterpret_cast<double2*>(l_pbterm)[i] = reinterpret_cast<const double2*>(P.pbterm)[i];
+        for (int i = ci + CT; i < S + 2; i += CT) { l_pbc[i] = P.pbc_tab[i]; l_sqrt[i] = P.sqrt_tab[i]; }
+        // all unconditional, with clamped indices: one count of loads in flight on every path
+        int rx[RPT], ry[RPT], rz[RPT];                                // (plain scalars, as unroll_body)
+        float bv[RPT], bg[RPT], bb[RPT];
+#pragma unroll
+        for (int u = 0; u < RPT; ++u) {
+            const int i = ci + u * CT;
+            const int ic = i < nri ? i : 0;
+            const int4 r = reinterpret_cast<const int4*>(P.rec)[ic];
+            rx[u] = r.x; ry[u] = r.y; rz[u] = r.z;
+            bv[u] = P.bias[ic];
+            if constexpr (BNM != 0) {            // (γ, β): sections of the bias image, present with P.bn
+                bg[u] = P.bias[P.bn ? nri + ic : 0];
+                bb[u] = P.bias[P.bn ? 2 * nri + ic : 0];
+            }
+        }
+        double pbx[PBT], pby[PBT];
+#pragma unroll
+        for (int u = 0; u < PBT; ++u) {
+            const int i = ci + u * CT;
+            const double2 v = reinterpret_cast<const double2*>(P.pbterm)[i < npb2 ? i : 0];
+            pbx[u] = v.x; pby[u] = v.y;
+        }
+        const double pbl = P.pbterm[npb - 1];                         // the odd entry (written if npb is odd)
+        const double pcv = P.pbc_tab[ci < S + 2 ? ci : 0], sqv = P.sqrt_tab[ci < S + 2 ? ci : 0];
+        const float avv = P.aval_tab[tid < A ? tid : 0];
+        // one observation element per thread of the first slot (T * obs_feat <= 256: a layer's
+        // fan-in is <= 64)
+        const int o_gl = tid / P.obs_feat, o_k = tid - o_gl * P.obs_feat;
+        const bool o_it = tid < T * P.obs_feat, o_in = o_it && tile0 + o_gl < P.G;
+        const float ov = P.obs[o_in ? (size_t)(tile0 + o_gl) * P.obs_feat + o_k : 0];
+        image();
+        // the setup values (landed in front of the image) go to LDS
+        for (int i = ci; i < P.act_total; i += CT)                    // (the observation rows: next line)
+            if (i < P.x_rep || i >= P.x_rep + T * P.obs_feat) act[i] = 0.0f;
+        if (o_it) act[P.x_rep + o_k * T + o_gl] = o_in ? ov : 0.0f;
+#pragma unroll
+        for (int u = 0; u < RPT; ++u) {                               // records with their biases merged
+            const int i = ci + u * CT;
+            if (i < nri) {
+                reinterpret_cast<int4*>(rec)[i] = make_int4(rx[u], ry[u], rz[u], __float_as_int(bv[u]));
+                if constexpr (BNM != 0)
+                    if (P.bn) bnl[i] = make_float2(bg[u], bb[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PBT; ++u) {
+            const int i = ci + u * CT;
+            if (i < npb2) reinterpret_cast<double2*>(l_pbterm)[i] = make_double2(pbx[u], pby[u]);
+        }
+        if (tid == 0 && (npb & 1)) l_pbterm[npb - 1] = pbl;
+        if (ci < S + 2) { l_pbc[ci] = pcv; l_sqrt[ci] = sqv; }
+        if (tid < A) l_aval[tid] = avv;
+        for (int i = ci; i < T * NN; i += CT) c_cache[i] = make_uint2(0u, 0u);
+        if (tid < 4) { c_hdr[tid] = make_int4(0, -1, 1, 0); c_mmx[tid] = make_float2(0.0f, 0.0f); c_skip[tid] = 0; }
+        if (tid < T && sel_ballot) c_stat[tid * NNS] = node_static(0, 0, 0, 1ull);   // the root: anc[0] = 1
+        P_MARK(1);
+        P_MARK(2);
+    } else {
+        // the noise wave: lanes 16 n_g + a as wave 0's 16 g + a
+        const int n_g = (tid - 64 * NW) >> 4, n_gg = tile0 + n_g;
+        const bool n_active = n_g < T && n_gg < P.G;
+        if (n_g < T) {
+            // the legal set, lane-parallel: lane a reads byte a, the group's OR is the mask
+            const uint8_t lgb = P.legal[n_active && a < A ? (size_t)n_gg * A + a : 0];
+            const int tpv = P.to_play[n_active ? n_gg : 0];
+            const uint32_t lmask = g16_or(n_active && a < A && lgb ? 1u << a : 0u);
+            if (a == 0) {
+                sg_legal[n_g] = lmask;
+                sg_root_tp[n_g] = n_active ? tpv : 1;
+                sg_rootN[n_g] = 0; sg_rootW[n_g] = 0.0f;
+                sg_mmin[n_g] = INFINITY; sg_mmax[n_g] = -INFINITY;  // MinMaxStats(Inf, -Inf), SelfPlay.jl:251
+                sg_leaf_e[n_g] = 0; sg_leaf_a[n_g] = 0; sg_vtp[n_g] = 1; sg_depth[n_g] = 0;
+            }
+            if (P.exploration && n_active)
+                sg_noise[16 * n_g + a] = root_noise_lane(lmask, a, A, P.seed, P.game_offset + (uint32_t)n_gg,
+                                                         P.rng_step, P.dirichlet_alpha, sg_stage + 16 * n_g);
+        }
+        P_MARK(2);
+        if (root_wave) image();
     }
     __syncthreads();
-
-    // the root's exploration noise depends only on the legal set: drawn here,
-    // lane-parallel, while the weight loads are in flight
-    if (P.exploration && active)
-        sg_noise[16 * g + a] = root_noise_lane(sg_legal[g], a, A, P.seed, gid, P.rng_step, P.dirichlet_alpha,
-                                               sg_stage + 16 * g);
-    sm_run<T, SM_MAX_SIM, 0, 0, BNM>(P.n_root, wr, rec_root, act, nullptr, bn_root);
+    if (root_wave) {
+        sm_run<T, SM_MAX_SIM, 0, RO, BNM>(P.n_root, wr, rec_root, act, nullptr, bn_root);
+    } else {
+        if (wv == NW) image();
+        for (int k = 0; k < P.n_root; ++k) __syncthreads();         // (a stage's barrier: sm_stage)
+    }
+    P_MARK(3);
+    // The sets the representation ran on take their sim stages (prediction ‖ dynamics weights:
+    // resident for the whole search) under the root prediction: sets RO, RO + 1 here, set K + RO
+    // + 2 in front of stage K (sm_run_reload), four loads a wave and stage, because a wave that
+    // issues the whole reload at once stands in the issue until most of it has streamed.
+    // The explicit vmcnt(0) costs nothing (sets 0 .. RO-1 were issued a representation ago) and
+    // tells the compiler so: without it the waits in front of the first stages are counted along
+    // the path without a reload, and on the path with one they drain it.
+    __builtin_amdgcn_s_waitcnt(0x0f70);          // vmcnt(0) alone (gfx9 encoding: expcnt 7, lgkmcnt 15)
+    if (root_wave) {
+#pragma unroll
+        for (int k = RO; k < RO + 2; ++k) sm_load_set(wr[k], P.w_sim, k, mk_sim[k], P.zero16);
+    }
+    P_MARK(4);
     for (int i = tid; i < T * H; i += SM_THREADS) {     // h -> hidden slot 0 and the prediction input
         const int gl = i / H, k = i - gl * H;
         const float h = act[P.h_out + k * T + gl];
         hid[(size_t)gl * NN * H + k] = h;
         act[P.x_pred + k * T + gl] = h;
     }
-    // prediction ‖ dynamics weights: resident for the whole search
-    sm_load<SM_MAX_SIM>(0, P.n_root < P.n_sim ? P.n_root : P.n_sim, P.w_sim, wr, P.nzm, P.zero16);
     __syncthreads();
     // prediction(h) for the root (:239); the dynamics half runs on zeros, unused
-    sm_run<T, SM_MAX_SIM, 0, 0, BNM>(P.n_sim, wr, rec_sim, act, nullptr, bn_sim);
+    sm_run_reload<T, BNM, RO + 2>(P.n_sim, wr, rec_sim, act, bn_sim, root_wave, P.w_sim, mk_sim, P.zero16);
+    __builtin_amdgcn_s_waitcnt(0x0f70);          // (every set has landed: none is pending in the loop's view)
+    P_MARK(5);
 
     const uint32_t legal = tree_thread ? sg_legal[g] : 0u;
     if (tree_thread) {   // expand_node!(root, legal, to_play, 0, policy, h) (:245)
@@ -378,6 +546,7 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
     if (P.exploration && active && a < A && ((legal >> a) & 1u))     // add_exploration_noise! (:102-109)
         tree.p(a) = tree.p(a) * (1.0f - P.exploration_eps) + sg_noise[16 * g + a] * P.exploration_eps;
     __syncthreads();
+    P_MARK(6);
     SM_STAMP(0);
 
     const SmFusedIn fin{hid, sg_leaf_e, sg_leaf_a, l_aval, NN, H, P.plane, P.x_pred, P.x_dyn};
@@ -585,6 +754,12 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
     if (P.stamps && (threadIdx.x == 0 || threadIdx.x == 128 || threadIdx.x == 192)) {
         const int k = threadIdx.x == 0 ? 0 : threadIdx.x == 128 ? 1 : 2;
         P.stamps[(gridDim.x + blockIdx.x) * 8 + k] = w_acc[k];
+    }
+    if (P.stamps && (threadIdx.x & 255) == 0) {
+        unsigned long long* pw = P.stamps + (gridDim.x + blockIdx.x) * 8 + (threadIdx.x == 0 ? 3 : 6);
+        pw[0] = p_mark[0] | p_mark[1] << 21 | p_mark[2] << 42;
+        pw[1] = p_mark[3] | p_mark[4] << 21 | p_mark[5] << 42;
+        if (threadIdx.x == 0) pw[2] = p_mark[6];
     }
 #endif
 }
