@@ -729,8 +729,9 @@ static int build_small(mz_handle* h) {
             else if (L.net == MZ_NET_PRED) out_off = L.chain == CH_HEAD1 ? lay[5] : lay[6];
             else out_off = L.chain == CH_HEAD1 ? lay[4] : lay[7];
         };
-        // int4 per [stage][slot][row]: {input base, kq, out | relu << 30 (-1 =
-        // unused), bias (filled on device)}; unused rows read offset 0 with
+        // int4 per [stage][slot][row] (mz_small_params.h): {address of the row's input
+        // element, quarter stride | flags, output address (-1 = unused), bias (filled on
+        // device)}, in bytes from the activation buffer; unused rows read offset 0 with
         // zero weights
         std::vector<int> rec((size_t)nrec * SM_REC_INTS, 0);
         for (size_t i = 0; i < rec.size(); i += 4) rec[i + 2] = -1;
@@ -742,16 +743,18 @@ static int build_small(mz_handle* h) {
                 io(set[i], in_off, out_off);
                 int* R = rec.data() + (size_t)(rec0 + st[i]) * SM_REC_INTS;
                 const int kq = 4 * ((L.in + 15) / 16);
-                // every row of the layer's 16-row groups carries the input base
-                // and kq (the DPP row broadcasts them); rows beyond L.out have
-                // zero weights and no output
+                // every row of the layer's 16-row groups carries its input element's
+                // address and the quarter stride (a layer starts on a 16-row group, so
+                // element row & 15 is the lane's within its DPP row); rows beyond L.out
+                // have zero weights and no output
                 const int rows = (L.out + 15) / 16 * 16;
+                const int flags = (L.act == MZ_ACT_RELU ? SM_REC_RELU : 0) | (L.bn ? SM_REC_BN : 0) |
+                                  (in_off == lay[2] ? SM_REC_PRED : 0);
                 for (int row = 0; row < rows; ++row) {
                     int* e = R + 4 * (sl[i] * 64 + 4 * b0[i] + row);
-                    e[0] = in_off;
-                    e[1] = kq;
-                    e[2] = row < L.out ? (out_off + row * T) | (L.act == MZ_ACT_RELU ? 1 << 30 : 0) |
-                                             (L.bn ? 1 << 29 : 0) : -1;
+                    e[0] = (in_off + (row & 15) * T) * 4;
+                    e[1] = kq * T * 4 | flags;
+                    e[2] = row < L.out ? (out_off + row * T) * 4 : -1;
                 }
             }
         };

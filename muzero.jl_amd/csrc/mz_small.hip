@@ -12,8 +12,8 @@
 // chain takes x[q*kq + j] from lane j of its DPP row as the row_newbcast
 // operand of v_fmac_f32_dpp (so the 16 rows of a DPP row must share one input
 // vector: the host schedules layers in 16-row groups).  permlane16/32 swaps
-// then form ((p0+p1)+(p2+p3)) in every lane, and DPP row 0 adds the bias,
-// applies the activation and writes the row.  A dependent fma costs a few
+// then form ((p0+p1)+(p2+p3)), game g's in DPP row g (sm_qsum), and DPP row
+// g < T adds the bias, applies the activation and writes game g's row.  A dependent fma costs a few
 // cycles where a dependent v_mfma_f32_4x4x1 costs 45
 // (tools/mfma_rate_probe.hip): the VALU is the latency-optimal unit here.
 // Tree (mz_tree_device.h) and hidden states live in LDS; the host builds the
@@ -81,11 +81,15 @@ __device__ __forceinline__ void sm_chain(const float (&w)[16], const float (&x)[
         // compiler also pads for the accumulator (an s_nop per pair), which
         // the interleave already separates by one instruction.  One s_nop 1
         // up front covers x written by VALU just before (the fused first stage).
+        // The one at the end: a permlane swap reads the accumulators next (sm_qsum),
+        // 2 wait states after a VALU write — which the compiler pads for only behind
+        // instructions of its own, not behind this block.
         asm volatile("s_nop 1\n\t"
                      SM_F2(0, "%4") SM_F2(1, "%5") SM_F2(2, "%6") SM_F2(3, "%7")
                      SM_F2(4, "%8") SM_F2(5, "%9") SM_F2(6, "%10") SM_F2(7, "%11")
                      SM_F2(8, "%12") SM_F2(9, "%13") SM_F2(10, "%14") SM_F2(11, "%15")
                      SM_F2(12, "%16") SM_F2(13, "%17") SM_F2(14, "%18") SM_F2(15, "%19")
+                     "s_nop 1"
                      : "+v"(acc[0]), "+v"(acc[1])
                      : "v"(x[0]), "v"(x[1]), "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "v"(w[4]), "v"(w[5]),
                        "v"(w[6]), "v"(w[7]), "v"(w[8]), "v"(w[9]), "v"(w[10]), "v"(w[11]), "v"(w[12]), "v"(w[13]),
@@ -94,6 +98,11 @@ __device__ __forceinline__ void sm_chain(const float (&w)[16], const float (&x)[
 #pragma unroll
         for (int g = 0; g < T; ++g) fmac_bcast<J>(acc[g], x[g], w[J]);
         sm_chain<T, J + 1>(w, x, acc);
+    } else if constexpr (T == 1) {           // (the wait states in front of the swaps, as above)
+        asm volatile("s_nop 1" : "+v"(acc[0]));
+    } else {
+        static_assert(T == 4, "sm_chain: T is 1, 2 or 4");
+        asm volatile("s_nop 1" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
     }
 }
 
@@ -107,17 +116,117 @@ __device__ __forceinline__ void sm_chain(const float (&w)[16], const float (&x)[
 // the step's a/|A| of game 0 (game g's at aval[g * NN]).
 struct SmFusedIn {
     const float* hid; const int* leaf_e; const int* leaf_a; const float* aval;
-    int NN, H, plane, x_pred, x_dyn;
+    int NN, H, plane;
 };
 
-// This thread's input offset in a stage with record R: x[q*kq + i] of the T
+// LDS by absolute byte address: the stage records carry absolute addresses
+// (sm_rec_abs), so a stage's input read and output write need no base add
+#define SM_LDS(type, addr) (*(__attribute__((address_space(3))) type*)(unsigned)(addr))
+__device__ __forceinline__ int sm_lds_addr(const void* p) {
+    return (int)(unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
+}
+// A host record (mz_small_params.h: .x, .z relative to the activation buffer)
+// as the kernel holds it in LDS, act_b = sm_lds_addr(act)
+__device__ __forceinline__ int4 sm_rec_abs(int rx, int ry, int rz, float bias, int act_b) {
+    return make_int4(rx + act_b, ry, rz >= 0 ? rz + act_b : rz, __float_as_int(bias));
+}
+
+// This thread's input address in a stage with record R: x[q*kq + i] of the T
 // games (rows beyond kq meet zero weights; the 64-row input buffers are zero
-// beyond K, so every step is exact); q·kq as a 24-bit multiply (full rate,
-// where a 32-bit one is quarter rate)
+// beyond K, so every step is exact).  One v_mad_u32_u24: .x is the row's
+// address of element i, the low 24 bits of .y the stride of a quarter (the
+// flag bits above them do not enter a 24-bit multiply)
+__device__ __forceinline__ int sm_xoff(int4 R) {      // (absolute LDS bytes)
+    const int q = (threadIdx.x >> 4) & 3;
+    return R.x + (int)__umul24((unsigned)q, (unsigned)R.y);
+}
+
+// The quarter sums ((p0+p1)+(p2+p3)) of the T games, game g's in DPP row g
+// (rows >= T hold no sum).  permlane16_swap(A, B) leaves A' = [A.r0, B.r0,
+// A.r2, B.r2], B' = [A.r1, B.r1, A.r3, B.r3] (r = 16-lane row), so swapping
+// two games' accumulators against each other puts game 0's p0+p1 in row 0,
+// game 1's in row 1 and the p2+p3 in rows 2, 3 of A' + B'; permlane32_swap
+// then brings the upper two rows under the lower two.  A swap overwrites both
+// operands: where only one is live the other is a spent register (`dead`, or
+// the odd half of the swap before), never a copy.
 template <int T>
-__device__ __forceinline__ int sm_xoff(int4 R) {      // (in bytes)
-    const int q = (threadIdx.x >> 4) & 3, i = threadIdx.x & 15;
-    return (R.x + ((int)__umul24((unsigned)q, (unsigned)R.y) + i) * T) * 4;
+__device__ __forceinline__ float sm_qsum(const float (&acc)[T], float dead) {
+    auto u = [](float v) { return __builtin_bit_cast(unsigned, v); };
+    auto f = [](unsigned v) { return __builtin_bit_cast(float, v); };
+    if constexpr (T == 4) {
+        const auto s01 = __builtin_amdgcn_permlane16_swap(u(acc[0]), u(acc[1]), false, false);
+        const float t01 = f(s01[0]) + f(s01[1]);
+        const auto s23 = __builtin_amdgcn_permlane16_swap(u(acc[2]), u(acc[3]), false, false);
+        const float t23 = f(s23[0]) + f(s23[1]);
+        const auto s = __builtin_amdgcn_permlane32_swap(u(t01), u(t23), false, false);
+        return f(s[0]) + f(s[1]);
+    } else {
+        const auto s1 = __builtin_amdgcn_permlane16_swap(u(acc[0]), u(T == 2 ? acc[T - 1] : dead), false, false);
+        const float t = f(s1[0]) + f(s1[1]);
+        const auto s2 = __builtin_amdgcn_permlane32_swap(u(t), s1[1], false, false);
+        return f(s2[0]) + f(s2[1]);
+    }
+}
+
+// The fused first stage's inputs (SmFusedIn) in two dependent LDS round trips,
+// every read unconditional with a clamped index: the caller's record and the
+// T leaf slots and actions (one read each: 16-entry blocks) are the first, h
+// and a/|A| the second; the cases are selects.  Every kept row of a schedule's
+// stage 0 is a first layer of prediction or dynamics (any other layer waits
+// for one), so a row with neither flag is an unused one whose sum is dropped.
+template <int T, int FI>
+__device__ __forceinline__ void sm_fused_in(int4 R, const SmFusedIn& fi, float (&x)[T]) {
+    constexpr int SH = T == 1 ? 2 : T == 2 ? 3 : 4;                  // the stride is kq·T·4
+    const int q = (threadIdx.x >> 4) & 3;
+    const int k = (int)(__umul24((unsigned)q, (unsigned)R.y) >> SH) + (int)(threadIdx.x & 15);
+    const int kc = k < fi.H ? k : fi.H - 1;
+    float hv[T], av[T];
+    if constexpr (FI == 1) {
+        int le[T], la[T];
+        if constexpr (T == 1) {
+            le[0] = fi.leaf_e[0]; la[0] = fi.leaf_a[0];
+        } else if constexpr (T == 2) {
+            const int2 e = *reinterpret_cast<const int2*>(fi.leaf_e), a = *reinterpret_cast<const int2*>(fi.leaf_a);
+            le[0] = e.x; le[1] = e.y; la[0] = a.x; la[1] = a.y;
+        } else {
+            const int4 e = *reinterpret_cast<const int4*>(fi.leaf_e), a = *reinterpret_cast<const int4*>(fi.leaf_a);
+            le[0] = e.x; le[1] = e.y; le[2] = e.z; le[3] = e.w; la[0] = a.x; la[1] = a.y; la[2] = a.z; la[3] = a.w;
+        }
+#pragma unroll
+        for (int g = 0; g < T; ++g) {      // (slot < 2^24, H <= 64: a 24-bit multiply)
+            hv[g] = fi.hid[(int)__umul24((unsigned)(g * fi.NN + le[g]), (unsigned)fi.H) + kc];
+            av[g] = fi.aval[la[g]];
+        }
+    } else {
+        if constexpr (T == 1) {
+            hv[0] = fi.hid[kc];
+        } else if constexpr (T == 2) {
+            const float2 v = *reinterpret_cast<const float2*>(fi.hid + kc * 2);
+            hv[0] = v.x; hv[1] = v.y;
+        } else {
+            const float4 v = *reinterpret_cast<const float4*>(fi.hid + kc * 4);
+            hv[0] = v.x; hv[1] = v.y; hv[2] = v.z; hv[3] = v.w;
+        }
+#pragma unroll
+        for (int g = 0; g < T; ++g) av[g] = fi.aval[g * fi.NN];
+    }
+    // all issued together, one wait (left to itself the compiler sinks a read into the
+    // lanes that use it, a divergent branch and a round trip of its own each)
+#pragma unroll
+    for (int g = 0; g < T; ++g) asm volatile("" : "+v"(hv[g]), "+v"(av[g]));
+    // prediction: h, 0 past H; dynamics: 2h, a/|A| on the action plane, 0 past it (h · 1 is h)
+    const bool pred = (R.y & SM_REC_PRED) != 0;
+    const float hs = pred ? 1.0f : 2.0f;
+    const bool in_h = k < fi.H, in_a = !pred && k < fi.H + fi.plane;
+#pragma unroll
+    for (int g = 0; g < T; ++g) {
+        const float tail = in_a ? av[g] : 0.0f;
+        x[g] = in_h ? hv[g] * hs : tail;
+    }
+    // x is written by VALU and read next through DPP inside sm_chain's asm, which the compiler
+    // does not pad for: 2 wait states (T = 2: the s_nop at the head of its block)
+    if constexpr (T == 1) asm volatile("s_nop 1" : "+v"(x[0]));
+    if constexpr (T == 4) asm volatile("s_nop 1" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]));
 }
 
 // One stage.  R = this thread's record of stage K, xo its input offset
@@ -127,34 +236,19 @@ __device__ __forceinline__ int sm_xoff(int4 R) {      // (in bytes)
 // BNM: 1 = the record's BatchNorm bit is tested (make_dense with BatchNorm, test mode), 0 = the
 // nets have no BatchNorm layer (the search kernels' plain instances: no test, no (γ, β) load)
 template <int T, int FI = 0, int BNM = 1>
-__device__ __forceinline__ int4 sm_stage(const float (&w)[16], int4 R, int& xo, const int4* rec_next, float* lds,
+__device__ __forceinline__ int4 sm_stage(const float (&w)[16], int4 R, int& xo, const int4* rec_next,
                                          const SmFusedIn* fi = nullptr, const float2* bnp = nullptr) {
     const int q = (threadIdx.x >> 4) & 3;
-    const float* xp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(lds) + xo);
     float x[T];
     if constexpr (FI != 0) {
-        const int k = (int)__umul24((unsigned)q, (unsigned)R.y) + (int)(threadIdx.x & 15);
-        const bool pred = R.x == fi->x_pred, dyn = R.x == fi->x_dyn;
-#pragma unroll
-        for (int g = 0; g < T; ++g) {
-            float hv, av;
-            if constexpr (FI == 1) {
-                const float* hp = fi->hid + ((size_t)g * fi->NN + fi->leaf_e[g]) * fi->H;
-                hv = k < fi->H ? hp[k] : 0.0f;
-                av = fi->aval[fi->leaf_a[g]];
-            } else {
-                hv = k < fi->H ? fi->hid[k * T + g] : 0.0f;
-                av = fi->aval[g * fi->NN];
-            }
-            x[g] = pred ? hv : dyn ? (k < fi->H ? hv * 2.0f : k < fi->H + fi->plane ? av : 0.0f) : xp[g];
-        }
+        sm_fused_in<T, FI>(R, *fi, x);
     } else if constexpr (T == 1) {
-        x[0] = xp[0];
+        x[0] = SM_LDS(const float, xo);
     } else if constexpr (T == 2) {
-        const float2 v = *reinterpret_cast<const float2*>(xp);
+        const sm_f32x2 v = SM_LDS(const sm_f32x2, xo);
         x[0] = v.x; x[1] = v.y;
     } else {
-        const float4 v = *reinterpret_cast<const float4*>(xp);
+        const sm_f32x4 v = SM_LDS(const sm_f32x4, xo);
         x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
     }
     const int4 Rn = *rec_next;
@@ -162,31 +256,17 @@ __device__ __forceinline__ int4 sm_stage(const float (&w)[16], int4 R, int& xo, 
 #pragma unroll
     for (int g = 0; g < T; ++g) acc[g] = 0.0f;
     sm_chain<T>(w, x, acc);
-    // ((p0+p1)+(p2+p3)) in every lane: with both operands equal, the two
-    // halves of a permlane swap are {own, partner} in row order, so their sum
-    // is p_even + p_odd in both rows of each pair
-#pragma unroll
-    for (int g = 0; g < T; ++g) {
-        const auto s1 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, acc[g]),
-                                                         __builtin_bit_cast(unsigned, acc[g]), false, false);
-        const float t = __builtin_bit_cast(float, (unsigned)s1[0]) + __builtin_bit_cast(float, (unsigned)s1[1]);
-        const auto s2 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, t),
-                                                         __builtin_bit_cast(unsigned, t), false, false);
-        acc[g] = __builtin_bit_cast(float, (unsigned)s2[0]) + __builtin_bit_cast(float, (unsigned)s2[1]);
-    }
-    // every DPP row now holds the T sums: DPP row q < T writes game q's row,
-    // so the T epilogues run side by side on different lanes
+    // DPP row q < T holds game q's sum and writes game q's row, so the T
+    // epilogues run side by side on different lanes
+    const float v = sm_qsum<T>(acc, x[0]);
     if (q < T && R.z >= 0) {
-        float v = acc[0];
-#pragma unroll
-        for (int g = 1; g < T; ++g) v = q == g ? acc[g] : v;
-        const int o = R.z & 0x1fffffff;
         float d = v + __int_as_float(R.w);
         if constexpr (BNM != 0)
-            if ((R.z >> 29) & 1) { const float2 gb = *bnp; d = mz_bn_apply(d, gb.x, gb.y); }
-        lds[o + q] = (R.z >> 30) != 0 ? mz_relu(d) : d;
+            if (R.y & SM_REC_BN) { const float2 gb = *bnp; d = mz_bn_apply(d, gb.x, gb.y); }
+        // (relu is the top flag: one unsigned compare)
+        SM_LDS(float, R.z + q * 4) = (unsigned)R.y >= (unsigned)SM_REC_RELU ? mz_relu(d) : d;
     }
-    xo = sm_xoff<T>(Rn);
+    xo = sm_xoff(Rn);
     asm volatile("" : "+v"(xo));     // formed here, not sunk below the barrier
     __syncthreads();
     return Rn;
@@ -195,14 +275,17 @@ __device__ __forceinline__ int4 sm_stage(const float (&w)[16], int4 R, int& xo, 
 // rec: this thread's record of stage 0 ([stage][slot][row] int4, stride 128)
 template <int T, int NMAX, int FI, int OFF, int BNM, int K = 0>
 __device__ __forceinline__ void sm_run_k(int n, const float (&wr)[NMAX][16], int4 R, int xo, const int4* rec,
-                                         float* lds, const SmFusedIn* fi, const float2* bnp) {
+                                         const SmFusedIn* fi, const float2* bnp) {
     if constexpr (K + OFF < NMAX) {
+        // the stage count stays a scalar register and the test a scalar compare where it
+        // stands (hoisted out of a caller's loop, the NMAX tests live there as lane masks)
+        asm volatile("" : "+s"(n));
         if (K < n) {
             const float2* bk = bnp + K * (SM_SLOTS * 64);
             const int4 Rn = K == 0 && FI != 0
-                ? sm_stage<T, FI, BNM>(wr[K + OFF], R, xo, rec + (K + 1) * (SM_SLOTS * 64), lds, fi, bk)
-                : sm_stage<T, 0, BNM>(wr[K + OFF], R, xo, rec + (K + 1) * (SM_SLOTS * 64), lds, nullptr, bk);
-            sm_run_k<T, NMAX, FI, OFF, BNM, K + 1>(n, wr, Rn, xo, rec, lds, fi, bnp);
+                ? sm_stage<T, FI, BNM>(wr[K + OFF], R, xo, rec + (K + 1) * (SM_SLOTS * 64), fi, bk)
+                : sm_stage<T, 0, BNM>(wr[K + OFF], R, xo, rec + (K + 1) * (SM_SLOTS * 64), nullptr, bk);
+            sm_run_k<T, NMAX, FI, OFF, BNM, K + 1>(n, wr, Rn, xo, rec, fi, bnp);
         }
     }
 }
@@ -211,10 +294,10 @@ __device__ __forceinline__ void sm_run_k(int n, const float (&wr)[NMAX][16], int
 // stage, 2 = the learner's (SmFusedIn).  Stage K runs on register set K + OFF.
 // bnp: this thread's (γ, β) column, laid out as `rec` (read only by BatchNorm rows).
 template <int T, int NMAX, int FI = 0, int OFF = 0, int BNM = 1>
-__device__ __forceinline__ void sm_run(int n, const float (&wr)[NMAX][16], const int4* rec, float* lds,
-                                       const SmFusedIn* fi, const float2* bnp) {
+__device__ __forceinline__ void sm_run(int n, const float (&wr)[NMAX][16], const int4* rec, const SmFusedIn* fi,
+                                       const float2* bnp) {
     const int4 R0 = rec[0];
-    sm_run_k<T, NMAX, FI, OFF, BNM>(n, wr, R0, sm_xoff<T>(R0), rec, lds, fi, bnp);
+    sm_run_k<T, NMAX, FI, OFF, BNM>(n, wr, R0, sm_xoff(R0), rec, fi, bnp);
 }
 
 // Weights of this thread's (slot, row, quarter) for stages 0..n-1 from the
@@ -270,24 +353,25 @@ __device__ __forceinline__ void sm_load_set(float (&w)[16], const float* W, int 
 // issues set K + LEAD (sim stage K + LEAD of W, mask mk[K + LEAD]) in front of stage K.
 template <int T, int BNM, int LEAD, int K = 0>
 __device__ __forceinline__ void sm_run_reload_k(int n, float (&wr)[SM_MAX_SIM][16], int4 R, int xo, const int4* rec,
-                                                float* lds, const float2* bnp, bool reload, const float* W,
+                                                const float2* bnp, bool reload, const float* W,
                                                 const uint32_t (&mk)[SM_MAX_SIM], const float4* zero16) {
     if constexpr (K < SM_MAX_SIM) {
+        asm volatile("" : "+s"(n));              // (a scalar test: sm_run_k)
         if (K < n) {
             if constexpr (K + LEAD < SM_MAX_SIM)
                 if (reload) sm_load_set(wr[K + LEAD], W, K + LEAD, mk[K + LEAD], zero16);
-            const int4 Rn = sm_stage<T, 0, BNM>(wr[K], R, xo, rec + (K + 1) * (SM_SLOTS * 64), lds, nullptr,
+            const int4 Rn = sm_stage<T, 0, BNM>(wr[K], R, xo, rec + (K + 1) * (SM_SLOTS * 64), nullptr,
                                                 bnp + K * (SM_SLOTS * 64));
-            sm_run_reload_k<T, BNM, LEAD, K + 1>(n, wr, Rn, xo, rec, lds, bnp, reload, W, mk, zero16);
+            sm_run_reload_k<T, BNM, LEAD, K + 1>(n, wr, Rn, xo, rec, bnp, reload, W, mk, zero16);
         }
     }
 }
 template <int T, int BNM, int LEAD>
-__device__ __forceinline__ void sm_run_reload(int n, float (&wr)[SM_MAX_SIM][16], const int4* rec, float* lds,
+__device__ __forceinline__ void sm_run_reload(int n, float (&wr)[SM_MAX_SIM][16], const int4* rec,
                                               const float2* bnp, bool reload, const float* W,
                                               const uint32_t (&mk)[SM_MAX_SIM], const float4* zero16) {
     const int4 R0 = rec[0];
-    sm_run_reload_k<T, BNM, LEAD>(n, wr, R0, sm_xoff<T>(R0), rec, lds, bnp, reload, W, mk, zero16);
+    sm_run_reload_k<T, BNM, LEAD>(n, wr, R0, sm_xoff(R0), rec, bnp, reload, W, mk, zero16);
 }
 
 template <int T, int BNM>
@@ -305,6 +389,7 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
     const int PS = 2 * (S + 2);
     const int nrec = P.n_sim + P.n_root;
     float* act = smem;                                           // act_total floats (multiple of 4)
+    const int act_b = sm_lds_addr(act);
     int* rec = reinterpret_cast<int*>(act + P.act_total);        // [nrec][SM_REC_INTS]
     float* hid = reinterpret_cast<float*>(rec + (nrec + 1) * SM_REC_INTS);   // [T][S+1][H] (+1: look-ahead slack)
     int* si = reinterpret_cast<int*>(hid + ((size_t)T * NN * H + 3) / 4 * 4);
@@ -459,7 +544,7 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
         for (int u = 0; u < RPT; ++u) {                               // records with their biases merged
             const int i = ci + u * CT;
             if (i < nri) {
-                reinterpret_cast<int4*>(rec)[i] = make_int4(rx[u], ry[u], rz[u], __float_as_int(bv[u]));
+                reinterpret_cast<int4*>(rec)[i] = sm_rec_abs(rx[u], ry[u], rz[u], bv[u], act_b);
                 if constexpr (BNM != 0)
                     if (P.bn) bnl[i] = make_float2(bg[u], bb[u]);
             }
@@ -502,7 +587,7 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
     }
     __syncthreads();
     if (root_wave) {
-        sm_run<T, SM_MAX_SIM, 0, RO, BNM>(P.n_root, wr, rec_root, act, nullptr, bn_root);
+        sm_run<T, SM_MAX_SIM, 0, RO, BNM>(P.n_root, wr, rec_root, nullptr, bn_root);
     } else {
         if (wv == NW) image();
         for (int k = 0; k < P.n_root; ++k) __syncthreads();         // (a stage's barrier: sm_stage)
@@ -529,7 +614,7 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
     }
     __syncthreads();
     // prediction(h) for the root (:239); the dynamics half runs on zeros, unused
-    sm_run_reload<T, BNM, RO + 2>(P.n_sim, wr, rec_sim, act, bn_sim, root_wave, P.w_sim, mk_sim, P.zero16);
+    sm_run_reload<T, BNM, RO + 2>(P.n_sim, wr, rec_sim, bn_sim, root_wave, P.w_sim, mk_sim, P.zero16);
     __builtin_amdgcn_s_waitcnt(0x0f70);          // (every set has landed: none is pending in the loop's view)
     P_MARK(5);
 
@@ -549,7 +634,7 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
     P_MARK(6);
     SM_STAMP(0);
 
-    const SmFusedIn fin{hid, sg_leaf_e, sg_leaf_a, l_aval, NN, H, P.plane, P.x_pred, P.x_dyn};
+    const SmFusedIn fin{hid, sg_leaf_e, sg_leaf_a, l_aval, NN, H, P.plane};
     int n_fast = 0;      // wave w < T (uniform): simulations whose leaf the ballot pass found
     // Per simulation, three workgroup barriers besides the 8 network stages:
     // wave 0 owns the trees' updates (T <= 4 games x 16 lanes); wave w < T
@@ -607,7 +692,7 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
         SM_STAMP(2);
         // ---- prediction(parent.h) ‖ dynamics(2h ⊕ a/|A|): the first stage
         // reads the parent's h from the hidden-state store (gather fused)
-        sm_run<T, SM_MAX_SIM, 1, 0, BNM>(P.n_sim, wr, rec_sim, act, &fin, bn_sim);
+        sm_run<T, SM_MAX_SIM, 1, 0, BNM>(P.n_sim, wr, rec_sim, &fin, bn_sim);
         SM_STAMP(3);
         const int e_new = s + 1;
         // expand (wave 2) runs beside the read-outs + backup (wave 0): they
@@ -801,6 +886,7 @@ __device__ __forceinline__ void unroll_body(const SmallUnrollParams& P, int lb, 
     const int K = P.K, A = P.A, H = P.H;
     const int nrec = P.n_sim + P.n_root;
     float* act = smem;
+    const int act_b = sm_lds_addr(act);
     int* rec = reinterpret_cast<int*>(act + P.act_total);
     float* aval = reinterpret_cast<float*>(rec + (nrec + 1) * SM_REC_INTS);    // [T][K+1] a/|A| per step
     float2* bnl = reinterpret_cast<float2*>(aval + 64);                     // [nrec][slot][64] (γ, β) (P.bn)
@@ -859,7 +945,7 @@ __device__ __forceinline__ void unroll_body(const SmallUnrollParams& P, int lb, 
 #pragma unroll
     for (int u = 0; u < RPT; ++u) {
         const int i = tid + u * SM_THREADS;
-        if (i < nri) reinterpret_cast<int4*>(rec)[i] = make_int4(rx[u], ry[u], rz[u], __float_as_int(bv[u]));
+        if (i < nri) reinterpret_cast<int4*>(rec)[i] = sm_rec_abs(rx[u], ry[u], rz[u], bv[u], act_b);
     }
     if (tid < SM_REC_INTS / 4) reinterpret_cast<int4*>(rec)[nri + tid] = make_int4(0, 0, -1, 0);   // slack stage
     if (P.bn)
@@ -873,7 +959,7 @@ __device__ __forceinline__ void unroll_body(const SmallUnrollParams& P, int lb, 
     const int4* rec_root = rec_sim + P.n_sim * (SM_SLOTS * 64);
     const float2* bn_sim = bnl + sm_slot_row(tid);
     const float2* bn_root = bn_sim + P.n_sim * (SM_SLOTS * 64);
-    sm_run<T, SM_MAX_SIM, 0, RO, BNM>(P.n_root, wr, rec_root, act, nullptr, bn_root);
+    sm_run<T, SM_MAX_SIM, 0, RO, BNM>(P.n_root, wr, rec_root, nullptr, bn_root);
     SM_STAMP(1);                                   // repr stages
     // reload the representation's sets; in flight under step 1's first RO stages
     sm_load<SM_MAX_SIM>(RO, RO + P.n_root < P.n_sim ? RO + P.n_root : P.n_sim, io.w_sim, wr, P.nzm, P.zero16);
@@ -882,9 +968,9 @@ __device__ __forceinline__ void unroll_body(const SmallUnrollParams& P, int lb, 
         // make_dynamics_input (:293-304) fused into the first stage: it reads
         // h_{i-1} (h_out, written by the previous step's last stage, a barrier
         // ago) and the step's a/|A|
-        const SmFusedIn fin{act + P.h_out, nullptr, nullptr, aval + (i - 1), K + 1, H, P.plane, P.x_pred, P.x_dyn};
+        const SmFusedIn fin{act + P.h_out, nullptr, nullptr, aval + (i - 1), K + 1, H, P.plane};
         SM_STAMP(3);                               // step inputs (none left: fused)
-        sm_run<T, SM_MAX_SIM, 2, 0, BNM>(P.n_sim, wr, rec_sim, act, &fin, bn_sim);
+        sm_run<T, SM_MAX_SIM, 2, 0, BNM>(P.n_sim, wr, rec_sim, &fin, bn_sim);
         SM_STAMP(4);                               // the 8 stages
         // raw outputs (logits, value, reward before their read-out
         // activations); mz_learner_grad_kernel applies softmax / tanh for all

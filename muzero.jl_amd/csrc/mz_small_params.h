@@ -15,6 +15,7 @@
 #endif
 #define SM_MAX_ROOT 6      // stages of the representation schedule
 
+typedef float sm_f32x2 __attribute__((ext_vector_type(2)));
 typedef float sm_f32x4 __attribute__((ext_vector_type(4)));
 
 // Register image of one stage: [slot][chunk c = j/4][thread t of the slot][4],
@@ -42,12 +43,22 @@ __host__ __device__ __forceinline__ size_t sm_widx(int stage, int slot, int q, i
 #define SM_NZM_ALLOC (SM_NZM_N + SM_MAX_SIM)
 
 // Per stage, the host-built record: one int4 per [slot][row] (copied to LDS)
-//   .x  input base of the row's layer in the activation buffer (0 if unused:
-//       the row's weights are zero and its output is dropped)
-//   .y  kq of the layer (k steps per quarter)
-//   .z  output offset of the row | relu << 30 | BatchNorm << 29, or -1 = unused row
+// for T games per workgroup (activations are [element][T] floats), in bytes:
+//   .x  address of input element i = row & 15 of the row's layer: (input base + i·T)·4
+//       (0 if unused: the row's weights are zero and its output is dropped)
+//   .y  bits 0..23: the stride of a k-quarter, kq·T·4 (kq k steps per quarter), so a thread
+//       of DPP row q reads at .x + q·.y, one 24-bit multiply-add that never sees the flags:
+//       SM_REC_RELU | SM_REC_BN | SM_REC_PRED (the layer reads the prediction input; for the
+//       fused first stages, whose other rows are dynamics' and which recover kq by a shift)
+//   .z  address of the row's output for game 0, (output base + row·T)·4, or -1 = unused row
 //   .w  bias bits (filled at kernel start from the re-gathered bias image)
+// The host's addresses are relative to the activation buffer; the kernels' one-pass record
+// merge adds the buffer's LDS address to .x and .z (sm_rec_abs), so the stages address LDS
+// absolutely.
 #define SM_REC_INTS (SM_SLOTS * 64 * 4)
+#define SM_REC_RELU (1 << 30)      // the top flag: relu is one unsigned compare of .y
+#define SM_REC_BN (1 << 29)
+#define SM_REC_PRED (1 << 28)
 
 struct SmallParams {
     int G, S, A, H, players, obs_feat, plane, exploration;

@@ -14,7 +14,13 @@
 //   (f) (d) with the quarter sums through wave-private LDS instead of the
 //       permlane swaps (partials stored, row 0 reads its four back);
 //   (g) (d) without the quarter sums (row 0 writes its own partial: the
-//       permlane chain's share of (d)).
+//       permlane chain's share of (d));
+//   (h) (d) in sm_stage's present form: the two games'
+//       accumulators swapped against each other (two swaps, two adds, DPP row q
+//       stores game q: no copies, no select), relu one unsigned compare of the
+//       record's .y, and the next stage's input address one v_mad_u32_u24 of the
+//       record's absolute address and quarter stride — the input read through it,
+//       at the element (d) reads (stride 0).  (d) itself forms no offset at all.
 // Prints s_memtime ticks per iteration (wave 0 lane 0, median over blocks).
 // Build: hipcc --offload-arch=gfx950 -O3 tools/barrier_probe.hip -o tools/barrier_probe
 #include <hip/hip_runtime.h>
@@ -43,14 +49,22 @@ extern "C" __global__ __launch_bounds__(512, 1) void probe(int mode, unsigned lo
     __shared__ int4 rec[2][512];
     __shared__ float4 part[2][2][256];                  // [buffer][game][element] the four quarter partials
     __shared__ float wpart[8][2][64];                    // (f): per wave, per game, the lanes' partials
+    __shared__ int4 rec2[2][512];                        // (h): records with absolute LDS addresses
     const int tid = threadIdx.x;
     buf[0][tid] = (float)tid; buf[1][tid] = 0.0f;
     buf[0][tid + 512] = 0.0f; buf[1][tid + 512] = 0.0f;
     rec[0][tid] = make_int4(0, 4, (1 << 30) | (tid & 255) * 2, __float_as_int(0.5f));
     rec[1][tid] = rec[0][tid];
+    for (int b = 0; b < 2; ++b)       // stage b reads buf[b] at (d)'s element (.x + q * 0) and writes buf[b ^ 1]
+        rec2[b][tid] = make_int4((int)(unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)&buf[b][0] +
+                                     ((tid * 7) & 1022) * 4,
+                                 0 | (1 << 30),
+                                 (int)(unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)&buf[b ^ 1][(tid & 255) * 2],
+                                 __float_as_int(0.5f));
     part[0][0][tid & 255] = make_float4(1.f, 2.f, 3.f, 4.f); part[0][1][tid & 255] = make_float4(1.f, 2.f, 3.f, 4.f);
     __syncthreads();
-    int4 R = rec[0][tid];
+    int4 R = mode == 7 ? rec2[0][tid] : rec[0][tid];
+    int xo = R.x + (int)__umul24((unsigned)((tid >> 4) & 3), (unsigned)R.y);
     const float bias_e = 0.25f;
     float acc = 0.0f;
     const float w = 1.0f + tid * 1e-7f;
@@ -73,6 +87,29 @@ extern "C" __global__ __launch_bounds__(512, 1) void probe(int mode, unsigned lo
             reinterpret_cast<float*>(&part[src ^ 1][0][row])[q] = a0;
             reinterpret_cast<float*>(&part[src ^ 1][1][row])[q] = a1;
             acc = a0 * 1e-3f;
+            __syncthreads();
+        } else if (mode == 7) {
+            typedef float f32x2 __attribute__((ext_vector_type(2)));
+            const int src = it & 1, q = (tid >> 4) & 3;
+            const f32x2 x = *(__attribute__((address_space(3))) const f32x2*)(unsigned)xo;
+            const int4 Rn = rec2[src ^ 1][tid];
+            float a0 = acc, a1 = 0.0f;
+            chain(w, x.x, x.y, a0, a1);
+            asm volatile("s_nop 1" : "+v"(a0), "+v"(a1));   // VALU write (in asm) -> permlane swap: 2 wait states
+            const auto s1 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a0),
+                                                             __builtin_bit_cast(unsigned, a1), false, false);
+            const float t = __builtin_bit_cast(float, (unsigned)s1[0]) + __builtin_bit_cast(float, (unsigned)s1[1]);
+            const auto s2 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, t), s1[1], false, false);
+            const float v = __builtin_bit_cast(float, (unsigned)s2[0]) + __builtin_bit_cast(float, (unsigned)s2[1]);
+            if (q < 2 && R.z >= 0) {
+                const float d = v + __int_as_float(R.w);
+                *(__attribute__((address_space(3))) float*)(unsigned)(R.z + q * 4) =
+                    (unsigned)R.y >= (1u << 30) ? fmaxf(d, 0.0f) : d;
+            }
+            xo = Rn.x + (int)__umul24((unsigned)q, (unsigned)Rn.y);
+            asm volatile("" : "+v"(xo));
+            R = Rn;
+            acc = v * 1e-3f;
             __syncthreads();
         } else {
             const int src = it & 1;
@@ -131,12 +168,13 @@ int main() {
     const int blocks = 256;
     unsigned long long* d; float* sink;
     hipMalloc(&d, blocks * 8); hipMalloc(&sink, 4096);
-    const char* names[7] = {"barrier only", "ds_write+barrier+ds_read", "+ 16-step x2 dpp fmac chain",
+    const char* names[8] = {"barrier only", "ds_write+barrier+ds_read", "+ 16-step x2 dpp fmac chain",
                             "+ sm_stage epilogue (record, permlane sums, row-0 bias/relu/store)",
                             "chain + partials stored, quarter sums by the consumer",
                             "(d) with the quarter sums through wave-private LDS",
-                            "(d) without the quarter sums"};
-    for (int mode = 0; mode < 7; ++mode) {
+                            "(d) without the quarter sums",
+                            "(d) as sm_stage now: sums across the games, one-instruction offset"};
+    for (int mode = 0; mode < 8; ++mode) {
         for (int rep = 0; rep < 2; ++rep) hipLaunchKernelGGL(probe, dim3(blocks), dim3(512), 0, 0, mode, d, sink);
         hipDeviceSynchronize();
         std::vector<unsigned long long> h(blocks);
