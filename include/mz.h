@@ -817,6 +817,11 @@ const char* mz_search_variant(const mz_handle* h);
  * (e.g. mz_runroll_chain_r+mz_runroll_pred_n1), for profiles; "none" before. */
 const char* mz_learner_variant(const mz_handle* h);
 
+/* Games per tile of the ResNet network kernels (rn_ng: the widest of 16, 8, 4,
+ * 2, 1 whose three plans fit the LDS with their k tables below LDS offset
+ * 32768, chosen at create); 0 for the FC nets.                              */
+int mz_resnet_tile_games(const mz_handle* h);
+
 /* Wait for the engine's work (the device, or the pair mz_set_sync_stream
  * named) and report a device fault.  A kernel that gives up waiting for a
  * cross-workgroup publish (a bounded poll, 2 s) sets a fault word instead of

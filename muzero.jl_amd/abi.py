@@ -126,6 +126,7 @@ SIGNATURES = {
     "mz_snapshot_load": (ctypes.c_int, [_VP, ctypes.c_char_p, _VP]),
     "mz_search_variant": (ctypes.c_char_p, [_VP]),
     "mz_learner_variant": (ctypes.c_char_p, [_VP]),
+    "mz_resnet_tile_games": (ctypes.c_int, [_VP]),
     "mz_sync": (ctypes.c_int, [_VP]),
 }
 
@@ -744,6 +745,10 @@ class Engine:
 
     def learner_variant(self):
         return self.lib.mz_learner_variant(self.h).decode()
+
+    def resnet_tile_games(self):
+        """Games per tile of the ResNet network kernels (0 for the FC nets)."""
+        return self.lib.mz_resnet_tile_games(self.h)
 
     def sync(self):
         self._check(self.lib.mz_sync(self.h), "mz_sync")

@@ -889,8 +889,8 @@ static std::vector<RSpec> rn_specs(const mz_config& c, const mz_resnet_hp& hp, i
         r.bnoff = n; n += (size_t)2 * cout;
         v.push_back(r);
     };
-    auto block = [&](int ch, int f, int k) { conv(ch, f, f, k, k); v.back().res_save = 1; conv(ch, f, f, k, k);
-                                             v.back().res_add = 1; };
+    auto block = [&](int ch, int f, int kw, int kh) { conv(ch, f, f, kw, kh); v.back().res_save = 1;
+                                                      conv(ch, f, f, kw, kh); v.back().res_add = 1; };
     auto dense = [&](int ch, int in, int out, int act) {
         RSpec r{ch, 0, in, out, 1, 1, act, 0, 0, 0, 0, 0, 0};
         r.woff = n; n += (size_t)in * out;
@@ -900,10 +900,10 @@ static std::vector<RSpec> rn_specs(const mz_config& c, const mz_resnet_hp& hp, i
     if (net == MZ_NET_REPR) {
         const int kw = hp.conv_kernel_size[0], kh = hp.conv_kernel_size[1];
         conv(0, C * (c.stacked_observations + 1) + c.stacked_observations, nf, kw, kh);
-        for (int i = 0; i < nb; ++i) block(0, nf, kw);
+        for (int i = 0; i < nb; ++i) block(0, nf, kw, kh);
     } else if (net == MZ_NET_PRED) {
         conv(0, nf, nf, 1, 1);
-        for (int i = 0; i < nb; ++i) block(0, nf, 1);
+        for (int i = 0; i < nb; ++i) block(0, nf, 1, 1);
         conv(1, nf, nvf, 1, 1);
         dense(1, P * nvf, hs, MZ_ACT_RELU);
         for (int i = 0; i < hp.depth_value; ++i) dense(1, hs, hs, MZ_ACT_RELU);
@@ -914,9 +914,9 @@ static std::vector<RSpec> rn_specs(const mz_config& c, const mz_resnet_hp& hp, i
         dense(2, hs, A, MZ_ACT_IDENTITY);
     } else {
         conv(0, nf + 1, nf, 1, 1);
-        for (int i = 0; i < nb; ++i) block(0, nf, 1);
+        for (int i = 0; i < nb; ++i) block(0, nf, 1, 1);
         conv(1, nf, nf, 1, 1);
-        for (int i = 0; i < nb; ++i) block(1, nf, 1);
+        for (int i = 0; i < nb; ++i) block(1, nf, 1, 1);
         conv(2, nf, nvf, 1, 1);
         dense(2, P * nvf, hs, MZ_ACT_RELU);
         for (int i = 0; i < hp.depth_value; ++i) dense(2, hs, hs, MZ_ACT_RELU);
@@ -1018,8 +1018,11 @@ static RPlan rn_plan(const mz_handle* h, const std::vector<RSpec>& sp, int net, 
     // K = nf + 1 first layer; X is dead once that layer has run)
     const int xsz = (std::max(in_feat * NG, net == MZ_NET_DYN && !sep_b2 ? big : 0) + 3) / 4 * 4;
     const int B2 = net == MZ_NET_DYN && sep_b2 ? region(big) : X + (xsz - big) / 4 * 4;
+    // the head convs write S0 (every conv off the trunk but the dynamics state head's tower, which
+    // runs in B2 / B1); their width is a hyperparameter of its own and may equal num_filters
     int headc = 0;
-    for (const RSpec& r : sp) if (r.chain && r.conv && r.cout != nf) headc = std::max(headc, r.cout * P * NG);
+    for (const RSpec& r : sp)
+        if (r.chain && r.conv && !(net == MZ_NET_DYN && r.chain == 1)) headc = std::max(headc, r.cout * P * NG);
     const int S0 = region(std::max(headc, hs * NG)), S1 = region(hs * NG), S2 = region(hs * NG);
     const int O0 = net == MZ_NET_PRED ? region(NG) : B0;             // REPR / DYN out0 = h (B0 / B2)
     const int O1 = net == MZ_NET_REPR ? 0 : region((net == MZ_NET_PRED ? h->A : 1) * NG);
@@ -1091,11 +1094,16 @@ static RPlan rn_plan(const mz_handle* h, const std::vector<RSpec>& sp, int net, 
     // layout never changes, so in-place residual blocks and aliased regions
     // stay consistent); the final outputs are checked plain below
     auto capable = [&](const RLayer& L) { return L.kk == 1 && L.K % 64 == 0; };
+    // (the k-blocked position of an element depends on the column count, so a region a conv
+    // writes, P·NG columns, and a Dense layer reads as its flattened features, NG columns,
+    // stays plain, where the two agree: a head conv whose P·cout is a multiple of 64)
     auto kb = [&](int off) {
-        bool any = false, all = true;
-        for (int j = 0; j < R.n; ++j)
-            if (R.L[j].in_off == off) { any = true; all &= capable(R.L[j]); }
-        return (int)(any && all);
+        bool any = false, all = true, dense_in = false, conv_out = false;
+        for (int j = 0; j < R.n; ++j) {
+            if (R.L[j].in_off == off) { any = true; all &= capable(R.L[j]); dense_in |= !R.L[j].spatial; }
+            if (R.L[j].out_off == off) conv_out |= R.L[j].spatial != 0;
+        }
+        return (int)(any && all && !(dense_in && conv_out));
     };
     R.in_kb = kb(X);
     for (int j = 0; j < R.n; ++j) {
@@ -1148,6 +1156,14 @@ static RPlan rn_plan(const mz_handle* h, const std::vector<RSpec>& sp, int net, 
     for (int j = 0; j < R.n; ++j) R.k[j] = rn_rk_pack(R.L[j]);
     if ((R.out0_kb && net == MZ_NET_PRED) || (R.out1_n && kb(R.out1_off))) R.n = -1;   // (never: read as plain)
     return R;
+}
+
+// The packed layer entry (rn_rk_pack) carries a layer's k table / offset table LDS offset in
+// 16 signed bits: a plan whose table lies past 32767 does not run (a narrower tile may)
+static bool rn_ktab_ok(const RPlan& R) {
+    for (int j = 0; j < R.n; ++j)
+        if (R.L[j].kk > 1 && R.L[j].ktab > 32767) return false;
+    return true;
 }
 
 // pUCT tables (libm log2/sqrt on the host: the values the oracle computes
@@ -1362,12 +1378,15 @@ int mz_engine_create_resnet(const mz_config* conf, const mz_resnet_hp* hyper, in
     for (int ng = 16; ng >= 1 && !h->rn_ng; ng /= 2) {
         int wi = 0;
         bool fits = true;
-        for (int n = 0; n < 3; ++n)
-            fits &= (size_t)rn_plan(h, sp[n], n, ng, h->flat_off[n] + (n == 0 ? h->ds_n : 0), wi,
-                                    nullptr).lds_floats * 4 <= kLdsMax;
+        for (int n = 0; n < 3; ++n) {
+            const RPlan R = rn_plan(h, sp[n], n, ng, h->flat_off[n] + (n == 0 ? h->ds_n : 0), wi, nullptr);
+            fits &= (size_t)R.lds_floats * 4 <= kLdsMax && rn_ktab_ok(R);
+        }
         if (fits) h->rn_ng = ng;
     }
-    if (!h->rn_ng) return bad("ResNet activations exceed the LDS even for one game per tile");
+    if (!h->rn_ng)
+        return bad("ResNet activations exceed the LDS even for one game per tile (or a k table lies past LDS "
+                   "offset 32767)");
     h->bn_s = sqrtf(1.0f + 1e-5f);
     int rc = 0;
 #define CK(x) do { if ((rc = (x)) != 0) { g_create_error = h->err; mz_engine_destroy(h); return rc; } } while (0)
@@ -1382,6 +1401,7 @@ int mz_engine_create_resnet(const mz_config* conf, const mz_resnet_hp* hyper, in
             h->rplan[n] = rn_plan(h, sp[n], n, h->rn_ng, h->flat_off[n] + (n == 0 ? h->ds_n : 0), wi, &sw, sep);
         }
         CK(h->rplan[n].n < 0 ? fail(h, "ResNet plan: a k-blocked output buffer") : 0);
+        CK(!rn_ktab_ok(h->rplan[n]) ? fail(h, "ResNet plan: a k table past LDS offset 32767") : 0);
         h->rn_lds[n] = (size_t)h->rplan[n].lds_floats * 4;
     }
     for (int n = 1; n < 3; ++n)                          // mz_rsearch_nets has no k-table path (NOKK)
@@ -1407,6 +1427,7 @@ int mz_engine_create_resnet(const mz_config* conf, const mz_resnet_hp* hyper, in
             h->rplan_l[n] = rn_plan(h, sp[n], n, ngl, h->flat_off[n] + (n == 0 ? h->ds_n : 0), wl, nullptr, sep,
                                     &h->rtab);
             CK(h->rplan_l[n].n < 0 ? fail(h, "ResNet plan: a k-blocked output buffer") : 0);
+            CK(!rn_ktab_ok(h->rplan_l[n]) ? fail(h, "ResNet learner plan: a k table past LDS offset 32767") : 0);
             h->rn_lds_l = std::max(h->rn_lds_l, (size_t)h->rplan_l[n].lds_floats * 4);
         }
         h->rd_chain = rd_chain_ok(h);
@@ -3038,6 +3059,8 @@ const char* mz_learner_variant(const mz_handle* h) {
     if (!h) return "";
     return h->last_lvariant.c_str();
 }
+
+int mz_resnet_tile_games(const mz_handle* h) { return h && h->kind == 1 ? h->rn_ng : 0; }
 
 // ------------------------------------------------ device self-play + replay
 }  // extern "C"

@@ -96,10 +96,10 @@ static OLayer* onet_conv(ONet* net, int part, int in, int out, int kw, int kh, i
 }
 
 /* resnet_block (Learning.jl:148-158): conv-BN-relu-conv-BN, + x, relu */
-static void onet_resblock(ONet* net, int part, int n, int k, int W, int H) {
-    OLayer* a = onet_conv(net, part, n, n, k, k, W, H, 1, MZ_ACT_RELU);
+static void onet_resblock(ONet* net, int part, int n, int kw, int kh, int W, int H) {
+    OLayer* a = onet_conv(net, part, n, n, kw, kh, W, H, 1, MZ_ACT_RELU);
     a->res_save = 1;
-    OLayer* b = onet_conv(net, part, n, n, k, k, W, H, 1, MZ_ACT_RELU);
+    OLayer* b = onet_conv(net, part, n, n, kw, kh, W, H, 1, MZ_ACT_RELU);
     b->res_add = 1;
 }
 
@@ -176,21 +176,21 @@ static void onet_build_resnet(ONet* net, int which, const mz_config* c, const mz
             int w = c->observation_shape[0], h = c->observation_shape[1];
             OLayer* l = onet_conv_s2(net, cin, cin, kw, kh, w, h);        /* :177 */
             w = l->W; h = l->H;
-            for (int i = 0; i < 2; ++i) onet_resblock(net, 0, cin, kw, w, h);
+            for (int i = 0; i < 2; ++i) onet_resblock(net, 0, cin, kw, kh, w, h);
             l = onet_conv_s2(net, cin, 2 * cin, kw, kh, w, h);            /* :179 */
             w = l->W; h = l->H;
-            for (int i = 0; i < 3; ++i) onet_resblock(net, 0, 2 * cin, kw, w, h);
+            for (int i = 0; i < 3; ++i) onet_resblock(net, 0, 2 * cin, kw, kh, w, h);
             onet_meanpool(net, 2 * cin, w, h);                            /* :181 */
             w = net->L[0][net->n[0] - 1].W; h = net->L[0][net->n[0] - 1].H;
-            for (int i = 0; i < 3; ++i) onet_resblock(net, 0, 2 * cin, kw, w, h);
+            for (int i = 0; i < 3; ++i) onet_resblock(net, 0, 2 * cin, kw, kh, w, h);
             onet_meanpool(net, 2 * cin, w, h);                            /* :183 */
             cin = 2 * cin;                                                /* :184: Conv(ksize, 2C => nf) */
         }
         onet_conv(net, 0, cin, nf, kw, kh, W, H, 1, MZ_ACT_RELU);
-        for (int i = 0; i < nb; ++i) onet_resblock(net, 0, nf, kw, W, H);
+        for (int i = 0; i < nb; ++i) onet_resblock(net, 0, nf, kw, kh, W, H);
     } else if (which == MZ_NET_PRED) {                                    /* :193-226 */
         onet_conv(net, 0, nf, nf, 1, 1, W, H, 1, MZ_ACT_RELU);
-        for (int i = 0; i < nb; ++i) onet_resblock(net, 0, nf, 1, W, H);
+        for (int i = 0; i < nb; ++i) onet_resblock(net, 0, nf, 1, 1, W, H);
         onet_conv(net, 1, nf, nvf, 1, 1, W, H, 1, MZ_ACT_RELU);           /* value head */
         onet_add(net, 1, P * nvf, hs, MZ_ACT_RELU);
         for (int i = 0; i < hp->depth_value; ++i) onet_add(net, 1, hs, hs, MZ_ACT_RELU);
@@ -202,9 +202,9 @@ static void onet_build_resnet(ONet* net, int which, const mz_config* c, const mz
         net->softmax_head2 = 1;
     } else {                                                              /* :228-255 */
         onet_conv(net, 0, nf + 1, nf, 1, 1, W, H, 1, MZ_ACT_RELU);        /* Q12: + the one action plane */
-        for (int i = 0; i < nb; ++i) onet_resblock(net, 0, nf, 1, W, H);
+        for (int i = 0; i < nb; ++i) onet_resblock(net, 0, nf, 1, 1, W, H);
         onet_conv(net, 1, nf, nf, 1, 1, W, H, 1, MZ_ACT_RELU);            /* state head */
-        for (int i = 0; i < nb; ++i) onet_resblock(net, 1, nf, 1, W, H);
+        for (int i = 0; i < nb; ++i) onet_resblock(net, 1, nf, 1, 1, W, H);
         onet_conv(net, 2, nf, nvf, 1, 1, W, H, 1, MZ_ACT_RELU);           /* reward head */
         onet_add(net, 2, P * nvf, hs, MZ_ACT_RELU);
         for (int i = 0; i < hp->depth_value; ++i) onet_add(net, 2, hs, hs, MZ_ACT_RELU);

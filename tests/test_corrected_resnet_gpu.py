@@ -47,17 +47,12 @@ def _batch(B, K, A, feat, rng):
                 gradient_scale=rng.integers(1, max(K, 1) + 1, B).astype(np.float32))
 
 
-@pytest.mark.parametrize("game,B,K,ir,per", [("ttt", 12, 3, True, False), ("ttt", 7, 0, False, True),
-                                             ("c4", 4, 2, True, True), ("atari", 3, 2, True, True)])
-def test_corrected_resnet_gradient_matches_torch(ttt, game, B, K, ir, per):
-    """atari: configs[4]'s nets, the downsampler (mz_dsbp_*) in front of the
-    representation's tail, 84x84x4 observations."""
+def _corrected_against_torch(conf, hyper, B, K, ir, per, ds=False):
+    """mz_learner_grad_dev in MZ_LEARN_CORRECTED mode against corrected_loss_and_grads: every net's data
+    gradient relative to its largest entry (ds: also the downsampler's slice on its own scale), the
+    losses and the read-outs."""
     import torch
     from muzero_jl_amd import abi
-    from muzero_jl_amd.games import atari_synth, connect4 as c4
-    mod = {"ttt": ttt, "c4": c4, "atari": atari_synth}[game]
-    conf = dataclasses.replace(mod.conf, batch_size=B, num_unroll_steps=K, intermediate_rewards=ir)
-    hyper = mod.resnet_hyper
     nets = _lively(conf, hyper, B + K)
     eng = abi.Engine(conf, hyper, device=0, max_games=8, rng_seed=1)
     for n, w in enumerate(nets):
@@ -91,7 +86,7 @@ def test_corrected_resnet_gradient_matches_torch(ttt, game, B, K, ir, per):
         assert scale > 1e-4, f"net {n}: no data gradient reached it"
         err = np.abs(gn - rn).max() / scale
         assert err < 1e-5, f"net {n}: data gradient rel. error {err:.3g}"
-        if n == 0 and game == "atari":               # the downsampler's own slice, on its own scale
+        if n == 0 and ds:                            # the downsampler's own slice, on its own scale
             nd = _ds_param_count(conf, hyper)
             sd = np.abs(rn[:nd]).max()
             assert sd > 1e-6, "no data gradient reached the downsampler"
@@ -107,6 +102,17 @@ def test_corrected_resnet_gradient_matches_torch(ttt, game, B, K, ir, per):
     if ir:
         np.testing.assert_allclose(pr, ref["rewards"], rtol=1e-5, atol=1e-6)
     eng.close()
+
+
+@pytest.mark.parametrize("game,B,K,ir,per", [("ttt", 12, 3, True, False), ("ttt", 7, 0, False, True),
+                                             ("c4", 4, 2, True, True), ("atari", 3, 2, True, True)])
+def test_corrected_resnet_gradient_matches_torch(ttt, game, B, K, ir, per):
+    """atari: configs[4]'s nets, the downsampler (mz_dsbp_*) in front of the
+    representation's tail, 84x84x4 observations."""
+    from muzero_jl_amd.games import atari_synth, connect4 as c4
+    mod = {"ttt": ttt, "c4": c4, "atari": atari_synth}[game]
+    conf = dataclasses.replace(mod.conf, batch_size=B, num_unroll_steps=K, intermediate_rewards=ir)
+    _corrected_against_torch(conf, mod.resnet_hyper, B, K, ir, per, ds=game == "atari")
 
 
 def test_corrected_resnet_learner_steps(ttt):

@@ -131,6 +131,8 @@ def test_resnet_learner_steps(ttt, B, K):
         lo = o.learner_step(st, batch, eta)
         if B >= 100:
             assert eng.learner_variant().endswith("+mz_runroll_pred"), eng.learner_variant()
+        else:                                        # the one-launch form: chain blocks, then the items
+            assert eng.learner_variant() == "mz_runroll_fused_r", eng.learner_variant()
         for g, w in zip(eng.debug_unroll(B), want):
             assert np.array_equal(g, w), f"step {t} unroll differs"
         assert np.array_equal(lg, lo), f"step {t} losses {lg} != oracle {lo}"   # same fold order: bit-exact
