@@ -426,12 +426,9 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
     // [4] per game: the select's start level (the last path's prefix the
     // recompute found unchanged; 0 = from the root)
     int* c_skip = reinterpret_cast<int*>(c_mmx + 4);
-    // the ballot select's node statics (mz_tree_device.h select_path_ballot):
-    // [T][NN] 16-byte records while the tree fits one wave (NN <= 64), else none
+    // the ballot select (mz_tree_device.h select_path_ballot) while the tree fits one wave
     const bool sel_ballot = NN <= 64;
-    const int NNS = sel_ballot ? NN : 0;
-    uint4* c_stat = reinterpret_cast<uint4*>(c_skip + 4);
-    float2* bnl = reinterpret_cast<float2*>(c_stat + T * NNS);    // [nrec][slot][64] BatchNorm (γ, β) (P.bn)
+    float2* bnl = reinterpret_cast<float2*>(c_skip + 4);          // [nrec][slot][64] BatchNorm (γ, β) (P.bn)
 
     const int tid = threadIdx.x;
     const int g = tid >> 4, a = tid & 15, lane = tid & 63;
@@ -559,7 +556,6 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
         if (tid < A) l_aval[tid] = avv;
         for (int i = ci; i < T * NN; i += CT) c_cache[i] = make_uint2(0u, 0u);
         if (tid < 4) { c_hdr[tid] = make_int4(0, -1, 1, 0); c_mmx[tid] = make_float2(0.0f, 0.0f); c_skip[tid] = 0; }
-        if (tid < T && sel_ballot) c_stat[tid * NNS] = node_static(0, 0, 0, 1ull);   // the root: anc[0] = 1
         P_MARK(1);
         P_MARK(2);
     } else {
@@ -636,6 +632,10 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
 
     const SmFusedIn fin{hid, sg_leaf_e, sg_leaf_a, l_aval, NN, H, P.plane};
     int n_fast = 0;      // wave w < T (uniform): simulations whose leaf the ballot pass found
+    // wave w < T: to_play at the root of its game (set in the prologue, constant for the launch)
+    const int rtp_w = __builtin_amdgcn_readfirstlane(sg_root_tp[wv < T ? wv : 0]);
+    // wave w < T, lane n: the statics of node n of its game (the ballot select's; the root's to start with)
+    NodeStat nst = node_stat_root(lane);
     // Per simulation, three workgroup barriers besides the 8 network stages:
     // wave 0 owns the trees' updates (T <= 4 games x 16 lanes); wave w < T
     // selects for game w, behind the recompute's barrier (the last simulation's
@@ -650,31 +650,29 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
                 const TreeView tw = tree_view(lds_tree + (size_t)w * P.tree_game_bytes, E, NN);
                 int* pw = sg_path + w * PS;
                 const uint2* cw = c_cache + w * NN;
-                const uint32_t verw = (uint32_t)c_hdr[w].z;
-                const int rtp = sg_root_tp[w];
+                uint32_t verw;                 // the game's tag (the ballot pass reads it with the entries)
                 SelectOut so{0, 0, 1, 0};
                 int D, e0;
                 uint32_t npc0;
                 bool found = false;
                 if (sel_ballot) {
-                    found = select_path_ballot(tw, cw, c_stat + w * NNS, verw, pw, s + 1, s + 1, rtp, lane, A,
-                                               P.players, so, D, e0, npc0);
+                    found = select_path_ballot(tw, cw, nst, &c_hdr[w].z, verw, pw, s + 1, s + 1, rtp_w,
+                                               lane, A, P.players, so, D, e0, npc0);
                 } else {                       // the tree outgrows one wave: the walk, from the skip-ahead level
+                    verw = (uint32_t)c_hdr[w].z;
                     D = c_skip[w];
                     e0 = D > 0 ? pw[2 * D + 1] : 0;
                     npc0 = D > 0 ? tw.nc(pw[2 * D]) : 0u;
                 }
                 if (!found && lane < 16) {
-                    so = select_path_cached(tw, cw, verw, pw, sg_rootN[w], rtp, sg_legal[w], sg_mmin[w], sg_mmax[w],
+                    so = select_path_cached(tw, cw, verw, pw, sg_rootN[w], rtp_w, sg_legal[w], sg_mmin[w], sg_mmax[w],
                                             lane, lane, A, P.players, l_pbterm, P.seed,
                                             P.game_offset + (uint32_t)(tile0 + w), P.rng_step, s, nullptr, nullptr, D,
                                             e0, npc0);
-                    if (sel_ballot && lane == 0) {          // the new node's statics (the walk outcome)
-                        const uint4 ps = c_stat[w * NNS + so.leaf_e];
-                        c_stat[w * NNS + s + 1] = node_static(so.leaf_e, so.depth, so.leaf_a,
-                                                              ((uint64_t)ps.y | ((uint64_t)ps.z << 32)) | (1ull << (s + 1)));
-                    }
                 }
+                if (sel_ballot && !found)                   // the new node's statics (the walk outcome, in lane 0)
+                    node_stat_set(nst, lane, s + 1, __builtin_amdgcn_readfirstlane(so.leaf_e),
+                                  __builtin_amdgcn_readfirstlane(so.depth), __builtin_amdgcn_readfirstlane(so.leaf_a));
                 if (lane == 0) { sg_leaf_e[w] = so.leaf_e; sg_leaf_a[w] = so.leaf_a; sg_vtp[w] = so.vtp; sg_depth[w] = so.depth; }
                 n_fast += found ? 1 : 0;
             }
@@ -701,9 +699,18 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
         if (tid < 64) {
             // ---- value / reward read-out activations, then backpropagate! (:190-217)
             if (active) {
-                // the backup's loads first (two players): in flight under the read-outs
+                // every load of this phase first, in flight under the read-outs: the game's
+                // words (none of them changes between the last stage's barrier and the writes
+                // below: wave 0 alone updates them, and the expansion beside it writes the new
+                // slot's edges only), then the leaf edge's word for its child link and the
+                // backup's path entries and records (two players)
                 const int tl = sg_vtp[g];
                 const int depth = sg_depth[g];
+                const int li = sg_leaf_e[g] * A + sg_leaf_a[g];
+                int rN = sg_rootN[g];
+                float rW = sg_rootW[g], mmin = sg_mmin[g], mmax = sg_mmax[g];
+                const int rtp = sg_root_tp[g];
+                const uint32_t lnc = tree.nc(li);
                 const BackupPre bpre = backup_preload(tree, path, depth, a);
                 // one activation per lane (even lanes the value, odd the reward, both
                 // f64 tanh chains run at once), then each quad's lanes 0 / 1 to all
@@ -720,22 +727,19 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
                 SM_STAMP(5);                    // stamp build: slot 5 = the read-out activations
                 W_STAMP0();
                 if (a == 0) {
-                    const int li = sg_leaf_e[g] * A + sg_leaf_a[g];
-                    tree.nc(li) = (tree.nc(li) & 0xffffu) | ((uint32_t)(e_new + 1) << 16);
+                    tree.nc(li) = (lnc & 0xffffu) | ((uint32_t)(e_new + 1) << 16);
                     tree.nr[e_new] = rew;
                     tree.ntp[e_new] = (int8_t)tl;
                     path[2 * depth + 1] = e_new;
                 }
                 __builtin_amdgcn_wave_barrier();
-                int rN = sg_rootN[g];
-                float rW = sg_rootW[g], mmin = sg_mmin[g], mmax = sg_mmax[g];
                 const uint32_t omin = __float_as_uint(mmin), omax = __float_as_uint(mmax);
                 if (P.players == 2)
-                    backup_path_pre(tree, path, bpre, depth, val, rew, e_new, tl, P.discount, rN, rW, sg_root_tp[g],
-                                    mmin, mmax, a, c_lvl + g * (S + 2), c_nN + g * NN);
+                    backup_path_pre(tree, path, bpre, depth, val, rew, e_new, tl, P.discount, rN, rW, rtp, mmin, mmax,
+                                    a, c_lvl + g * (S + 2), c_nN + g * NN);
                 else
-                    backup_path(tree, path, depth, val, tl, A, P.players, P.discount, rN, rW, sg_root_tp[g], mmin,
-                                mmax, a, c_lvl + g * (S + 2), c_nN + g * NN);
+                    backup_path(tree, path, depth, val, tl, A, P.players, P.discount, rN, rW, rtp, mmin, mmax, a,
+                                c_lvl + g * (S + 2), c_nN + g * NN);
                 const bool moved = __float_as_uint(mmin) != omin || __float_as_uint(mmax) != omax;
                 ver += moved ? 1 : 0;                     // min / max moved: every entry is stale
                 if (a == 0) {

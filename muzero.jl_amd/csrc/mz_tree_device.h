@@ -612,9 +612,11 @@ __device__ __forceinline__ SelectOut select_path_cached(const TreeView& t, const
 // cache says, for every expanded node, which child select would take, so the
 // selected path is a property of the whole table and one wave reads it off in
 // constant depth, one node per lane, instead of chasing it level by level.
-// Per node n its statics, fixed when n is created (one 16-byte record):
+// Per node n its statics, fixed when n is created: lane n of the selecting
+// wave keeps them in three registers for the whole search (NodeStat), so no
+// address of the pass depends on a load:
 //   .x  parent slot | depth << 8 | action into n << 16
-//   .y/.z  ancestor mask anc[n] = anc[par[n]] | 1 << n, anc[0] = 1
+//   .alo/.ahi  ancestor mask anc[n] = anc[par[n]] | 1 << n, anc[0] = 1
 // ok[n] = "n's parent has a current entry that chooses n"; with OK = ballot(ok)
 // | 1, node n lies on the selected path iff anc[n] is a subset of OK.  A parent
 // chooses one child, so the on-path nodes form a chain from the root; a child's
@@ -624,30 +626,46 @@ __device__ __forceinline__ SelectOut select_path_cached(const TreeView& t, const
 // the leaf is found.  Otherwise (a tie, a stale entry, the root before the
 // first backup) the caller continues with select_path_cached from level
 // D = dep[L], node e0 = L, npc0 = the nc word of the edge into L.
-__device__ __forceinline__ uint4 node_static(int par, int dep, int act, uint64_t anc) {
-    return make_uint4((uint32_t)par | ((uint32_t)dep << 8) | ((uint32_t)act << 16), (uint32_t)anc,
-                      (uint32_t)(anc >> 32), 0u);
+struct NodeStat { uint32_t x, alo, ahi; };
+// the statics of every lane's node before the first simulation: the root's in
+// lane 0 (anc[0] = 1); a lane without a node yet holds parent 0, whose entry
+// it reads and ignores
+__device__ __forceinline__ NodeStat node_stat_root(int lane) { return NodeStat{0u, lane == 0 ? 1u : 0u, 0u}; }
+// lane e_new takes the statics of the node about to be created under `par`
+// (par, dep, act wave-uniform; every lane of the wave calls it): the parent's
+// mask comes out of lane `par` by readlane
+__device__ __forceinline__ void node_stat_set(NodeStat& ns, int lane, int e_new, int par, int dep, int act) {
+    const uint64_t pa = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)ns.alo, par) |
+                        ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)ns.ahi, par) << 32);
+    const uint64_t an = pa | (1ull << e_new);
+    if (lane == e_new) {
+        ns.x = (uint32_t)par | ((uint32_t)dep << 8) | ((uint32_t)act << 16);
+        ns.alo = (uint32_t)an; ns.ahi = (uint32_t)(an >> 32);
+    }
 }
 
 // Called by all 64 lanes of one wave for one game (every argument wave-
-// uniform but `lane`); n_nodes = expanded nodes so far (1..64), e_new the slot
-// the leaf will be expanded into (its statics are written here when the leaf
-// is found).  Returns true with `so` set, or false with (D, e0, npc0).
-__device__ __forceinline__ bool select_path_ballot(const TreeView& t, const uint2* cache, uint4* stat, uint32_t ver,
-                                                   int* path, int n_nodes, int e_new, int root_tp, int lane, int A,
-                                                   int players, SelectOut& so, int& D, int& e0, uint32_t& npc0) {
+// uniform but `lane` and `ns`); n_nodes = expanded nodes so far (1..64), e_new
+// the slot the leaf will be expanded into (lane e_new takes its statics here
+// when the leaf is found).  Returns true with `so` set, or false with (D, e0,
+// npc0).  One LDS round trip: the game's tag `*tag` (only compared per lane,
+// returned in `ver`), the lane's own entry and its parent's.
+__device__ __forceinline__ bool select_path_ballot(const TreeView& t, const uint2* cache, NodeStat& ns, const int* tag,
+                                                   uint32_t& ver, int* path, int n_nodes, int e_new, int root_tp,
+                                                   int lane, int A, int players, SelectOut& so, int& D, int& e0,
+                                                   uint32_t& npc0) {
     const bool ex = lane < n_nodes;
     const int ln = ex ? lane : 0;
+    const int par = (int)(ns.x & 0xffu), dep = (int)((ns.x >> 8) & 0xffu), act = (int)(ns.x >> 16);
     uint2 ce = cache[ln];
-    uint4 st = stat[ln];
-    asm volatile("" : "+v"(ce.x), "+v"(ce.y), "+v"(st.x), "+v"(st.y), "+v"(st.z));   // both reads issued, one wait
-    const int par = (int)(st.x & 0xffu), dep = (int)((st.x >> 8) & 0xffu), act = (int)(st.x >> 16);
-    const uint2 cp = cache[par];                          // the parent's entry (the second LDS round trip)
+    uint2 cp = cache[par];                                // the parent's entry
+    ver = (uint32_t)*tag;
+    asm volatile("" : "+v"(ce.x), "+v"(ce.y), "+v"(cp.x), "+v"(cp.y), "+v"(ver));   // all issued, one wait
     const int ein = (int)__umul24((unsigned)par, (unsigned)A) + act;   // the edge into this node
     const bool cur = ex && (ce.x >> 5) == ver;
     const bool okl = ex && lane >= 1 && (cp.x >> 5) == ver && (cp.y >> 16) == (uint32_t)(lane + 1);
     const uint64_t OK = __builtin_amdgcn_ballot_w64(okl) | 1ull;
-    const uint64_t anc = (uint64_t)st.y | ((uint64_t)st.z << 32);
+    const uint64_t anc = (uint64_t)ns.alo | ((uint64_t)ns.ahi << 32);
     const bool on = ex && (anc & ~OK) == 0;
     const uint64_t ON = __builtin_amdgcn_ballot_w64(on);  // (bit 0 is always set: anc[0] = 1)
     const int L = 63 - __builtin_clzll(ON);
@@ -657,10 +675,9 @@ __device__ __forceinline__ bool select_path_ballot(const TreeView& t, const uint
     if (found) {
         const int la = (int)((uint32_t)__builtin_amdgcn_readlane((int)ce.x, L) & 31u);
         const int depth = D + 1;
-        if (lane == L) {
+        if (lane == L)
             *reinterpret_cast<int2*>(path + 2 * depth) = make_int2((int)__umul24((unsigned)L, (unsigned)A) + la, -1);
-            stat[e_new] = node_static(L, depth, la, anc | (1ull << e_new));
-        }
+        node_stat_set(ns, lane, e_new, L, depth, la);
         const int vtp = players == 2 ? ((root_tp - 1 + depth) & 1) + 1 : (root_tp - 1 + depth) % players + 1;
         so = SelectOut{L, la, vtp, depth};
     } else {
