@@ -402,6 +402,47 @@ int mz_expert_depth(mz_handle* h, int depth);
 int mz_expert_eval(mz_handle* h, int env_kind, int G, const uint8_t* boards, const int32_t* players, int depth,
                    int32_t* scores);
 
+/* The solved TicTacToe table: score(s, a, 9) of every board,
+ * so the depth-9 expert's move is a lookup, not a search.  The scores depend
+ * on the mover-relative position only: entry code = Σ_cell 3^cell · d, d = 0
+ * for an empty cell, 1 for the mover's stone, 2 for the other player's, cells
+ * in the byte planes' order; 3^9 = 19683 entries of nine int8 scores, -128
+ * for an illegal action (on the device each entry is padded to 16 bytes).
+ * Every code is filled, unreachable and finished boards with what the search
+ * kernel says of them: the fill is mz_expert_move's own depth-9 output over
+ * all codes, so table and search agree by construction.
+ *   mz_expert_table: a handle setting like mz_expert_depth (default off;
+ *     mz_selfplay_init and mz_snapshot_load keep it, snapshots do not carry
+ *     it).  on = 1 builds the table if the handle has none (host-synchronous,
+ *     once per handle; the table lives as long as the handle) and is refused
+ *     on a conf that cannot be TicTacToe (observation_shape (3,3,3), 9
+ *     actions); on = 0 stores the flag and frees nothing.
+ *     The lookup kernel replaces the search kernel's launch of an
+ *     MZ_OPP_EXPERT move (mz_selfplay_move in MZ_SP_EVAL, mz_test_play, the
+ *     test worker in mz_train_run) exactly when the switch is on, the env is
+ *     MZ_ENV_TICTACTOE and the effective depth is 9 (mz_expert_depth 0 or 9).
+ *     Same rows, same draw, same tie-break: the moves are bit for bit the
+ *     search kernel's.  mz_expert_eval always runs the search kernel.
+ *   mz_expert_table_get (parity): scores [19683][9] int8 (refused while no
+ *     table is built), *built 0|1, *in_use = 1 when the lookup would be
+ *     launched for the current env and depth.  Any pointer may be NULL.
+ *     Synchronises.                                                          */
+int mz_expert_table(mz_handle* h, int on);
+int mz_expert_table_get(mz_handle* h, void* scores, int32_t* built, int32_t* in_use);
+
+/* The judge's rule on given positions: row g is the move
+ * actions[g] (1-based) of players[g] on boards[g], judged at `depth`.  With
+ * c = score(s, a, depth) and b = the maximum over the legal actions' scores,
+ * a move adds {1, c == b, sgn(c) < sgn(b), b - c} to out4 = {moves judged,
+ * moves inside the expert's best set, moves that give away a win or a draw,
+ * total score deficit}.  Integers throughout: exact in any order.  Buffers
+ * and refusals as mz_expert_eval, plus an action that is not legal on its
+ * board.  Always the search kernel, in the judge mode evaluations use;
+ * synchronises; needs no mz_selfplay_init.  A host can judge any games it
+ * holds with it, e.g. those of mz_replay_get_game.                          */
+int mz_expert_judge(mz_handle* h, int env_kind, int G, const uint8_t* boards, const int32_t* players,
+                    const int32_t* actions, int depth, int64_t* out4);
+
 /* Evaluation tally since mz_selfplay_init: {games finished, MuZero wins,
  * opponent wins, draws}; the winner is read from the last move's reward
  * (TicTacToe with quirk Q14: the player to move after it; Connect4: the
@@ -465,13 +506,37 @@ int mz_eval_results(mz_handle* h, int64_t* out4);
  *     / mz_test_clear; counts [n][8], sums [n][3]; any pointer may be NULL.
  *     Synchronises.  mz_test_clear: total back to 0.
  *   mz_test_get_game (parity): test slot `slot`'s game of the last evaluation,
- *     layouts of mz_replay_get_game; synchronises.                            */
+ *     layouts of mz_replay_get_game; synchronises.
+ *   mz_test_audit: judge MuZero's moves of the following
+ *     evaluations by the expert's scores, the rule of mz_expert_judge at depth
+ *     D = mz_expert_depth (0: the env's default).  A handle setting, default
+ *     off, kept by mz_selfplay_init and mz_snapshot_load; refused on the
+ *     frame-stack env, and checked again by mz_test_play.  Judged: MuZero's
+ *     moves as above (to_play == muzero_player; every move with MZ_OPP_SELF)
+ *     of the slots that are not frozen, each by the action the search left
+ *     before mz_sp_commit, i.e. after temperature sampling.  One launch per
+ *     move: the expert's own launch with MZ_OPP_EXPERT (it judges MuZero's
+ *     turns and moves on the others), one more otherwise; the lookup kernel
+ *     where the solved table is in use, else the search kernel.  Games and
+ *     records are those of the same evaluation with judging off, bit for bit.
+ *     The sums {moves judged, in the expert's best set, win or draw given
+ *     away, score deficit} go to row e % MZ_TEST_RECORDS of a second device
+ *     ring int64 [MZ_TEST_RECORDS][4], allocated by the first evaluation that
+ *     judges and zeroed on the stream at its start.  An evaluation with
+ *     judging off issues no launch or memset it did not issue before.
+ *   mz_test_audit_results: audit [n][4], the rows of the evaluations
+ *     mz_test_results returns, in its order: row i of both belongs to the same
+ *     evaluation.  An evaluation run with judging off reads {-1, 0, 0, 0}.
+ *     total and audit may be NULL.  Synchronises.  mz_test_clear resets both
+ *     rings.                                                                  */
 enum { MZ_TEST_RECORDS = 1024 };
 int mz_test_config(mz_handle* h, int32_t games, int opponent, int muzero_player);
 int mz_test_play(mz_handle* h, int64_t training_step, uint32_t rng_step0, uint32_t game_offset,
                  float temperature, void* stream);
 int mz_test_results(mz_handle* h, int64_t* total, int64_t* counts, double* sums, int32_t max_records);
 int mz_test_clear(mz_handle* h);
+int mz_test_audit(mz_handle* h, int on);
+int mz_test_audit_results(mz_handle* h, int64_t* total, int64_t* audit, int32_t max_records);
 int mz_test_get_game(mz_handle* h, int32_t slot, int32_t* T, uint8_t* obs, int32_t* actions, float* rewards,
                      int32_t* to_play, float* child_visits, float* root_values);
 
@@ -799,9 +864,10 @@ int mz_checkpoint_load(mz_handle* h, const char* path, int64_t* training_step);
  * written into the metadata for information, and the loading host applies its
  * own (its mz_selfplay_mode, mz_expert_depth and opponent weight set survive
  * the load; the depth and the opponent set are not written to the file).
- * The test worker's settings (mz_test_config, mz_train_set_test) and its
- * record ring are handle settings too: not written, and they survive the load;
- * the test slots are re-created by the next mz_test_play.
+ * The test worker's settings (mz_test_config, mz_train_set_test,
+ * mz_test_audit) and its record and audit rings are handle settings too, as
+ * are mz_expert_table's switch and table: not written, and they survive the
+ * load; the test slots are re-created by the next mz_test_play.
  * At world > 1 each rank saves
  * and loads its own file; the host orders the calls.                          */
 int mz_snapshot_save(mz_handle* h, const char* path, int64_t training_step);

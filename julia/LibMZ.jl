@@ -183,6 +183,32 @@ function expert_eval(e::Engine, env::Cint, boards::Matrix{UInt8}, players::Vecto
                    e.h, env, size(boards, 2), boards, players, depth, scores))
     scores
 end
+# the solved TicTacToe table (DESIGN §18.1): a handle setting; on: built once, and the depth-9 TicTacToe
+# expert's move is a lookup (bit for bit the search's)
+expert_table!(e::Engine, on::Bool=true) =
+    check(e, ccall((:mz_expert_table, libmz), Cint, (Ptr{Cvoid}, Cint), e.h, on ? 1 : 0))
+"""expert_table_get(e) — (scores Int8 (9, 19683) or nothing, built, in_use): column code + 1, code = Σ 3^cell · d
+(d = 0 empty, 1 the mover's stone, 2 the other's), holds score(s, a, 9), -128 for an illegal action."""
+function expert_table_get(e::Engine)
+    built = Ref{Int32}(0); in_use = Ref{Int32}(0)
+    check(e, ccall((:mz_expert_table_get, libmz), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int32}, Ref{Int32}),
+                   e.h, C_NULL, built, in_use))
+    built[] == 0 && return (nothing, false, in_use[] != 0)
+    scores = Matrix{Int8}(undef, 9, 19683)
+    check(e, ccall((:mz_expert_table_get, libmz), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int32}, Ref{Int32}),
+                   e.h, scores, built, in_use))
+    (scores, true, in_use[] != 0)
+end
+"""expert_judge(e, env, boards (W*H*3, G), players (G), actions (G, 1-based), depth) — the judge's rule on given
+moves: (moves judged, in the expert's best set, win or draw given away, score deficit)."""
+function expert_judge(e::Engine, env::Cint, boards::Matrix{UInt8}, players::Vector{Int32}, actions::Vector{Int32},
+                      depth::Integer)
+    out = zeros(Int64, 4)
+    check(e, ccall((:mz_expert_judge, libmz), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Cint, Ptr{Int64}),
+                   e.h, env, size(boards, 2), boards, players, actions, depth, out))
+    out
+end
 # OPP_NETWORK: the opponent's weight set (a handle setting; complete after all three nets, one
 # opponent_from! or one opponent_load!), then selfplay_mode!(e, SP_EVAL; opponent=OPP_NETWORK, mzp=...)
 function opponent_set_weights!(e::Engine, net::Cint, chain)
@@ -292,6 +318,17 @@ function test_results(e::Engine; max_records=1024)
     total[], counts[:, 1:n], sums[:, 1:n]
 end
 test_clear!(e::Engine) = check(e, ccall((:mz_test_clear, libmz), Cint, (Ptr{Cvoid},), e.h))
+# judge MuZero's moves of the following evaluations by the expert's scores (DESIGN §20.1): a handle setting
+test_audit!(e::Engine, on::Bool=true) =
+    check(e, ccall((:mz_test_audit, libmz), Cint, (Ptr{Cvoid}, Cint), e.h, on ? 1 : 0))
+# (evaluations so far, audit (4, n): moves judged, in the best set, win or draw given away, score deficit) of the
+# records test_results returns, column for column; (-1, 0, 0, 0): that evaluation ran with judging off
+function test_audit_results(e::Engine; max_records=1024)
+    total = Ref{Int64}(0); audit = zeros(Int64, 4, max_records)
+    check(e, ccall((:mz_test_audit_results, libmz), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Int32),
+                   e.h, total, audit, max_records))
+    total[], audit[:, 1:min(max_records, total[], 1024)]
+end
 function test_get_game(e::Engine, slot, osz, A, max_moves)   # test slot `slot`'s game of the last evaluation
     T = Ref{Int32}(0); M = max_moves + 1
     obs = zeros(UInt8, osz, M); act = zeros(Int32, M); rew = zeros(Float32, M); tp = zeros(Int32, M)

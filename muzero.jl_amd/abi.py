@@ -27,6 +27,9 @@ TEST_RECORDS = 1024                              # MZ_TEST_RECORDS: the test wor
 TEST_COUNT_FIELDS = ("training_step", "games", "muzero_wins", "opponent_wins", "draws", "moves", "value_moves",
                      "rng_step0")
 TEST_SUM_FIELDS = ("reward_muzero", "reward_opponent", "value_sum")
+# one audit row (mz_test_audit_results, mz_expert_judge); judged == -1: the evaluation ran with judging off
+TEST_AUDIT_FIELDS = ("judged", "best", "blunders", "deficit")
+TTT_CODES = 19683                                # the solved TicTacToe table's entries (mz_expert_table)
 
 _lib = None
 
@@ -78,6 +81,9 @@ SIGNATURES = {
     "mz_selfplay_mode": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "mz_expert_depth": (ctypes.c_int, [_VP, ctypes.c_int]),
     "mz_expert_eval": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP, ctypes.c_int, _VP]),
+    "mz_expert_table": (ctypes.c_int, [_VP, ctypes.c_int]),
+    "mz_expert_table_get": (ctypes.c_int, [_VP, _VP, _VP, _VP]),
+    "mz_expert_judge": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, ctypes.c_int, _VP]),
     "mz_opponent_weights_set": (ctypes.c_int, [_VP, ctypes.c_int, _VP, ctypes.c_size_t]),
     "mz_opponent_weights_get": (ctypes.c_int, [_VP, ctypes.c_int, _VP, ctypes.c_size_t]),
     "mz_opponent_from": (ctypes.c_int, [_VP, ctypes.c_int, _VP]),
@@ -87,6 +93,8 @@ SIGNATURES = {
     "mz_test_play": (ctypes.c_int, [_VP, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, _VP]),
     "mz_test_results": (ctypes.c_int, [_VP, _VP, _VP, _VP, ctypes.c_int32]),
     "mz_test_clear": (ctypes.c_int, [_VP]),
+    "mz_test_audit": (ctypes.c_int, [_VP, ctypes.c_int]),
+    "mz_test_audit_results": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int32]),
     "mz_test_get_game": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mz_train_set_test": (ctypes.c_int, [_VP, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float]),
     "mz_replay_counts": (ctypes.c_int, [_VP, _VP, _VP]),
@@ -446,6 +454,37 @@ class Engine:
                     "mz_expert_eval")
         return out
 
+    def expert_table(self, on=True):
+        """The solved TicTacToe table: a handle setting, default off.  on: the table is built
+        if the handle has none (host-synchronous), and the depth-9 TicTacToe expert's move becomes a lookup."""
+        self._check(self.lib.mz_expert_table(self.h, int(bool(on))), "mz_expert_table")
+
+    def expert_table_get(self, scores=True):
+        """(table int8 (19683, 9) or None, built, in_use): entry code = sum of 3^cell * d (d = 0 empty, 1 the
+        mover's stone, 2 the other's) holds score(s, a, 9), -128 for an illegal action; in_use: the lookup
+        would be launched for the current env and depth.  scores=False: the flags only (table None); asking
+        for the scores of a handle that has built no table is refused."""
+        built, in_use = ctypes.c_int32(), ctypes.c_int32()
+        table = np.zeros((TTT_CODES, 9), np.int8) if scores else None
+        self._check(self.lib.mz_expert_table_get(self.h, _p(table), ctypes.byref(built), ctypes.byref(in_use)),
+                    "mz_expert_table_get")
+        return table, bool(built.value), bool(in_use.value)
+
+    def expert_judge(self, env_kind, boards, players, actions, depth):
+        """The judge's rule on given moves (boards (G, W*H*3), players (G,), 1-based actions (G,)) at `depth`:
+        (moves judged, in the expert's best set, win or draw given away, score deficit) as ints."""
+        b = np.ascontiguousarray(boards, np.uint8)
+        b = b.reshape(1, -1) if b.ndim == 1 else b
+        p = np.ascontiguousarray(players, np.int32).reshape(-1)
+        a = np.ascontiguousarray(actions, np.int32).reshape(-1)
+        want = {ENV_TICTACTOE: 27, ENV_CONNECT4: 126}.get(env_kind)     # any other env: the library refuses it
+        if want is not None and (b.shape[1] != want or p.size != b.shape[0] or a.size != b.shape[0]):
+            raise MzError(f"mz_expert_judge: boards must be (G, {want}) with G players and G actions")
+        out = np.zeros(4, np.int64)
+        self._check(self.lib.mz_expert_judge(self.h, env_kind, b.shape[0], _p(b), _p(p), _p(a), depth, _p(out)),
+                    "mz_expert_judge")
+        return tuple(int(x) for x in out)
+
     # ---- the opponent's weight set of OPP_NETWORK (DESIGN §19): a handle setting
     def opponent_set_weights(self, net, flat):
         """One net of the opponent set (Flux order, as set_weights); complete after all three."""
@@ -504,6 +543,20 @@ class Engine:
 
     def test_clear(self):
         self._check(self.lib.mz_test_clear(self.h), "mz_test_clear")
+
+    def test_audit(self, on=True):
+        """Judge MuZero's moves of the following evaluations by the expert's scores: a handle
+        setting, default off."""
+        self._check(self.lib.mz_test_audit(self.h, int(bool(on))), "mz_test_audit")
+
+    def test_audit_results(self, max_records=TEST_RECORDS):
+        """(evaluations since create / test_clear, int64 (n, 4) audit rows TEST_AUDIT_FIELDS of the records
+        test_results returns, in its order; (-1, 0, 0, 0): that evaluation ran with judging off)."""
+        total = ctypes.c_int64()
+        audit = np.zeros((max(max_records, 1), 4), np.int64)
+        self._check(self.lib.mz_test_audit_results(self.h, ctypes.byref(total), _p(audit), max_records),
+                    "mz_test_audit_results")
+        return int(total.value), audit[:min(max_records, total.value, TEST_RECORDS)].copy()
 
     def test_get_game(self, slot):
         """Test slot `slot`'s game of the last evaluation as a selfplay.GameHistory."""

@@ -203,6 +203,9 @@ struct mz_handle {
     std::string tr_ckpt_path;               // mz_train_set_networks_path: periodic checkpoints
     int sp_eval = 0, sp_opp = MZ_OPP_SELF, sp_mzp = 1;    // mz_selfplay_mode
     int sp_expert_depth = 0;                              // mz_expert_depth (0: the env's default)
+    // the solved TicTacToe table (mz_expert_table): the handle's, built by the first on = 1
+    bool xtable_on = false;
+    int8_t* d_xtable = nullptr;                           // [MZX_TTT_CODES][MZX_TTT_ENTRY]
     long long* d_eval = nullptr;                          // [4] evaluation tally
     // the test worker (mz_test_*).  Handle settings: mz_test_config, mz_train_set_test.
     // The record ring stays with the handle (allocated by the first mz_test_play); the test slots
@@ -212,6 +215,11 @@ struct mz_handle {
     long long* d_test_counts = nullptr;                   // [MZ_TEST_RECORDS][8]
     double* d_test_sums = nullptr;                        // [MZ_TEST_RECORDS][3]
     int64_t test_total = 0;                               // evaluations since create / mz_test_clear
+    // judging (mz_test_audit): the audit ring beside the records, allocated by the first
+    // evaluation that judges; which rows hold an audit is host bookkeeping
+    bool test_audit = false;
+    long long* d_test_audit = nullptr;                    // [MZ_TEST_RECORDS][4]
+    std::vector<uint8_t> test_audited = std::vector<uint8_t>(MZ_TEST_RECORDS, 0);
     struct TestSlots {
         int E = 0;                                        // 0: not allocated
         bool played = false;                              // an evaluation's games are in `hist`
@@ -3243,6 +3251,12 @@ static int expert_depth_of(const mz_handle* h, int env_kind) {
     return h->sp_expert_depth ? h->sp_expert_depth : env_kind == MZ_ENV_TICTACTOE ? 9 : 4;
 }
 
+// the lookup (mz_expert_table_move) stands in for the search exactly when the switch is on, the env is
+// TicTacToe and the effective depth is the table's 9
+static bool expert_table_in_use(const mz_handle* h) {
+    return h->xtable_on && h->d_xtable && h->sp_env == MZ_ENV_TICTACTOE && expert_depth_of(h, h->sp_env) == 9;
+}
+
 static void wset_swap(mz_handle* h, mz_handle::WSet& w);
 
 // MZ_OPP_NETWORK: the opponent search's outputs, part of the self-play state (a snapshot load
@@ -3259,8 +3273,11 @@ static int opp_io(mz_handle* h) {
 // One move of S's rows up to the commit, shared by mz_selfplay_move (the self-play slots) and
 // mz_test_play (the test slots): mz_sp_prepare -> the search on the engine's io with the handle's
 // current nets -> mz_expert_move, or the opponent's search (outputs cv2 / rv2 / act2) and mz_sp_pick
-// -> mz_sp_commit.  The keys, the temperature and the mode are S's.
-static int sp_move_body(mz_handle* h, const SpParams& S, float* cv2, float* rv2, int32_t* act2, hipStream_t st) {
+// -> mz_sp_commit.  The keys, the temperature and the mode are S's.  `judge` (a judging evaluation of
+// mz_test_play; null everywhere else): the audit row, which the expert's launch feeds on MuZero's turns
+// from the action the search left in d_act; with another opponent that launch is made for the judge alone.
+static int sp_move_body(mz_handle* h, const SpParams& S, float* cv2, float* rv2, int32_t* act2, hipStream_t st,
+                        long long* judge = nullptr) {
     const int G = S.G;
     const dim3 waves((G + 3) / 4);
     hipLaunchKernelGGL(mz_sp_prepare, waves, dim3(256), 0, st, S);
@@ -3268,9 +3285,14 @@ static int sp_move_body(mz_handle* h, const SpParams& S, float* cv2, float* rv2,
     int rc = search_dev(h, G, h->d_obs, h->d_legal, h->d_tp, 1, S.step, S.game_offset, S.temperature, h->d_cv,
                         h->d_rv, h->d_act, st, S.temp_g);
     if (rc) return rc;
-    if (S.eval && S.opponent == MZ_OPP_EXPERT) {     // the expert's turns: its move replaces the search's action
-        ExpertArgs X{expert_depth_of(h, h->sp_env), h->d_act, nullptr};
-        hipLaunchKernelGGL(mz_expert_move, waves, dim3(256), 0, st, S, X);
+    if ((S.eval && S.opponent == MZ_OPP_EXPERT) || judge) {   // the expert's turns: its move replaces the search's action
+        ExpertArgs X{expert_depth_of(h, h->sp_env), h->d_act, nullptr, nullptr, judge};
+        if (expert_table_in_use(h)) {                // the solved table: a lookup in place of the search
+            X.table = h->d_xtable;
+            hipLaunchKernelGGL(mz_expert_table_move, waves, dim3(256), 0, st, S, X);
+        } else {
+            hipLaunchKernelGGL(mz_expert_move, waves, dim3(256), 0, st, S, X);
+        }
     }
     if (S.eval && S.opponent == MZ_OPP_NETWORK) {    // the same search with the opponent's nets; its turns take
         wset_swap(h, h->opp);                        // that search's whole result
@@ -3453,6 +3475,109 @@ int mz_expert_eval(mz_handle* h, int env_kind, int G, const uint8_t* boards, con
     return 0;
 }
 
+// the fill: the search kernel's own depth-9 scores of every code, packed
+static int expert_table_build(mz_handle* h) {
+    const int n = MZX_TTT_CODES;
+    MZ_TRY(h, dalloc(h, &h->d_xtable, (size_t)n * MZX_TTT_ENTRY));
+    uint8_t* d_b = nullptr; int32_t* d_p = nullptr; int32_t* d_s = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_b), (size_t)n * 27);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_p), (size_t)n * 4);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_s), (size_t)n * 9 * 4);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(mz_expert_table_rows, dim3((n + 255) / 256), dim3(256), 0, h->stream, d_b, d_p, 0, n);
+        SpParams S;
+        std::memset(&S, 0, sizeof(S));
+        S.G = n; S.env = MZ_ENV_TICTACTOE; S.W = 3; S.H = 3; S.osz = 27; S.A = 9; S.board = d_b; S.player = d_p;
+        ExpertArgs X{9, nullptr, d_s};
+        hipLaunchKernelGGL(mz_expert_move, dim3((n + 3) / 4), dim3(256), 0, h->stream, S, X);
+        hipLaunchKernelGGL(mz_expert_table_pack, dim3((n * MZX_TTT_ENTRY + 255) / 256), dim3(256), 0, h->stream,
+                           (const int32_t*)d_s, h->d_xtable, 0, n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    (void)hipFree(d_b); (void)hipFree(d_p); (void)hipFree(d_s);
+    if (e != hipSuccess) { (void)dfree(h, h->d_xtable); h->d_xtable = nullptr; }
+    MZ_TRY(h, e);
+    return 0;
+}
+
+int mz_expert_table(mz_handle* h, int on) {
+    if (!h) return -2;
+    if (on != 0 && on != 1) return fail(h, "expert table: on must be 0 or 1");
+    if (on) {
+        if (int rc = sp_env_check(h, MZ_ENV_TICTACTOE)) return rc;   // this conf can never play TicTacToe
+        if (!h->d_xtable) {
+            MZ_TRY(h, hipSetDevice(h->device));
+            MZ_SYNC(h);
+            if (expert_table_build(h)) return -1;
+        }
+    }
+    h->xtable_on = on != 0;
+    return 0;
+}
+
+int mz_expert_table_get(mz_handle* h, void* scores, int32_t* built, int32_t* in_use) {
+    if (!h) return -2;
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);
+    if (built) *built = h->d_xtable != nullptr;
+    if (in_use) *in_use = expert_table_in_use(h);
+    if (scores) {
+        if (!h->d_xtable) return fail(h, "expert table: not built (mz_expert_table(h, 1) first)");
+        std::vector<int8_t> t((size_t)MZX_TTT_CODES * MZX_TTT_ENTRY);
+        MZ_TRY(h, hipMemcpy(t.data(), h->d_xtable, t.size(), hipMemcpyDeviceToHost));
+        int8_t* out = static_cast<int8_t*>(scores);
+        for (int c = 0; c < MZX_TTT_CODES; ++c)
+            for (int a = 0; a < 9; ++a) out[(size_t)c * 9 + a] = t[(size_t)c * MZX_TTT_ENTRY + a];
+    }
+    return 0;
+}
+
+int mz_expert_judge(mz_handle* h, int env_kind, int G, const uint8_t* boards, const int32_t* players,
+                    const int32_t* actions, int depth, int64_t* out4) {
+    if (!h || !boards || !players || !actions || !out4) return -2;
+    if (int rc = sp_env_check(h, env_kind)) return rc;
+    if (env_kind == MZ_ENV_ATARI) return fail(h, "expert: needs a two-player board env");
+    if (G < 1) return fail(h, "expert: G must be >= 1");
+    if (depth < 1 || depth > MZX_MAX_DEPTH) return fail(h, "expert: depth must be in 1..9");
+    const int A = h->A, osz = 3 * mzx_cells(env_kind);
+    for (int g = 0; g < G; ++g) {
+        ExpertPos pos;
+        if (players[g] != 1 && players[g] != 2) return fail(h, "expert: player must be 1 or 2");
+        if (!mzx_pos_from_planes(env_kind, boards + (size_t)g * osz, players[g], &pos))
+            return fail(h, "expert: every cell must be set in exactly one plane");
+        if (actions[g] < 1 || actions[g] > A || !((mzx_legal(pos) >> (actions[g] - 1)) & 1u))
+            return fail(h, "expert: action not legal on its board");
+    }
+    MZ_TRY(h, hipSetDevice(h->device));
+    uint8_t* d_b = nullptr; int32_t* d_p = nullptr; int32_t* d_a = nullptr; long long* d_j = nullptr;
+    long long j[4] = {0, 0, 0, 0};
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_b), (size_t)G * osz);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_p), (size_t)G * 4);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_a), (size_t)G * 4);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_j), sizeof(j));
+    if (e == hipSuccess) e = hipMemcpy(d_b, boards, (size_t)G * osz, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_p, players, (size_t)G * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_a, actions, (size_t)G * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_j, j, sizeof(j), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        SpParams S;
+        std::memset(&S, 0, sizeof(S));
+        S.G = G; S.env = env_kind; S.W = h->conf.observation_shape[0]; S.H = h->conf.observation_shape[1];
+        S.osz = osz; S.A = A; S.board = d_b; S.player = d_p;
+        S.opponent = MZ_OPP_SELF;                   // every row is judged
+        ExpertArgs X{depth, d_a, nullptr, nullptr, d_j};
+        hipLaunchKernelGGL(mz_expert_move, dim3((G + 3) / 4), dim3(256), 0, h->stream, S, X);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = hipMemcpy(j, d_j, sizeof(j), hipMemcpyDeviceToHost);
+    (void)hipFree(d_b); (void)hipFree(d_p); (void)hipFree(d_a); (void)hipFree(d_j);
+    MZ_TRY(h, e);
+    for (int i = 0; i < 4; ++i) out4[i] = j[i];
+    return 0;
+}
+
 int mz_eval_results(mz_handle* h, int64_t* out4) {
     if (!h || !out4) return -2;
     if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
@@ -3531,9 +3656,11 @@ int mz_test_play(mz_handle* h, int64_t training_step, uint32_t rng_step0, uint32
     if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
     if (h->test_E < 1) return fail(h, "mz_test_play: no test slots (mz_test_config with games >= 1 first)");
     if (int rc = test_check(h, h->test_E, h->test_opp, h->test_mzp)) return rc;
+    if (h->test_audit && h->sp_env == MZ_ENV_ATARI) return fail(h, "expert: needs a two-player board env");
     MZ_TRY(h, hipSetDevice(h->device));
     hipStream_t st = stream_of(h, stream);
     if (test_alloc(h)) return -1;
+    if (h->test_audit && !h->d_test_audit) MZ_TRY(h, dalloc(h, &h->d_test_audit, (size_t)MZ_TEST_RECORDS * 4));
     const mz_handle::TestSlots& t = h->ts;
     SpParams S = sp_params(h, true);
     S.game_offset = game_offset; S.reset_step = 0xFFFFFFFFu;
@@ -3544,10 +3671,14 @@ int mz_test_play(mz_handle* h, int64_t training_step, uint32_t rng_step0, uint32
               h->conf.players};
     hipLaunchKernelGGL(mz_test_begin, dim3((t.E + 3) / 4), dim3(256), 0, st, S, R);
     MZ_TRY(h, hipGetLastError());
+    // judging (mz_test_audit): the evaluation's audit row, zeroed on the stream; off: nothing is issued
+    long long* judge = h->test_audit ? h->d_test_audit + slot * 4 : nullptr;
+    if (judge) MZ_TRY(h, hipMemsetAsync(judge, 0, 4 * sizeof(long long), st));
+    h->test_audited[slot] = judge != nullptr;
     // the host never learns when every slot is done: always T moves, the frozen slots as dummy rows
     for (int m = 0; m < h->sp_T; ++m) {
         S.step = rng_step0 + (uint32_t)m;
-        if (int rc = sp_move_body(h, S, t.cv2, t.rv2, t.act2, st)) return rc;
+        if (int rc = sp_move_body(h, S, t.cv2, t.rv2, t.act2, st, judge)) return rc;
         hipLaunchKernelGGL(mz_test_tally, dim3(1), dim3(1024), 0, st, S, R);
         MZ_TRY(h, hipGetLastError());
     }
@@ -3577,6 +3708,33 @@ int mz_test_results(mz_handle* h, int64_t* total, int64_t* counts, double* sums,
 int mz_test_clear(mz_handle* h) {
     if (!h) return -2;
     h->test_total = 0;
+    std::fill(h->test_audited.begin(), h->test_audited.end(), (uint8_t)0);
+    return 0;
+}
+
+int mz_test_audit(mz_handle* h, int on) {
+    if (!h) return -2;
+    if (on != 0 && on != 1) return fail(h, "mz_test_audit: on must be 0 or 1");
+    if (on && h->sp_env == MZ_ENV_ATARI) return fail(h, "expert: needs a two-player board env");
+    h->test_audit = on != 0;
+    return 0;
+}
+
+int mz_test_audit_results(mz_handle* h, int64_t* total, int64_t* audit, int32_t max_records) {
+    if (!h) return -2;
+    if (max_records < 0) return fail(h, "mz_test_audit_results: max_records must be >= 0");
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);
+    if (total) *total = h->test_total;
+    const int64_t held = std::min<int64_t>(h->test_total, MZ_TEST_RECORDS);
+    const int64_t n = std::min<int64_t>(max_records, held);
+    for (int64_t i = 0; audit && i < n; ++i) {      // mz_test_results' rows, in its order
+        const size_t slot = (size_t)((h->test_total - n + i) % MZ_TEST_RECORDS);
+        long long a[4] = {-1, 0, 0, 0};             // an evaluation run with judging off
+        if (h->test_audited[slot])
+            MZ_TRY(h, hipMemcpy(a, h->d_test_audit + slot * 4, sizeof(a), hipMemcpyDeviceToHost));
+        for (int k = 0; k < 4; ++k) audit[i * 4 + k] = a[k];
+    }
     return 0;
 }
 

@@ -72,6 +72,28 @@ MZX_HD bool mzx_pos_from_planes(int env, const uint8_t* planes, int player, Expe
     return true;
 }
 
+// The solved TicTacToe table's index: code = Σ_cell 3^cell · d,
+// d = 0 empty / 1 the mover's stone / 2 the other player's; 3^9 = 19683 codes.
+// The scores read {me, opp, env} only, so one entry serves both players.
+enum { MZX_TTT_CODES = 19683, MZX_TTT_ENTRY = 16 };       // an entry: nine int8 scores padded to 16 bytes
+MZX_HD int mzx_ttt_code(const ExpertPos& pos) {
+    int code = 0;
+    for (int c = 8; c >= 0; --c)
+        code = 3 * code + (int)((pos.me >> c) & 1ull) + 2 * (int)((pos.opp >> c) & 1ull);
+    return code;
+}
+MZX_HD ExpertPos mzx_ttt_decode(int code) {
+    ExpertPos pos;
+    pos.me = 0; pos.opp = 0; pos.env = MZX_TICTACTOE;
+    for (int c = 0; c < 9; ++c) {
+        const int d = code % 3;
+        code /= 3;
+        pos.me |= (uint64_t)(d == 1) << c;
+        pos.opp |= (uint64_t)(d == 2) << c;
+    }
+    return pos;
+}
+
 // legal actions of a position that is not finished: bit a - 1 for action a
 MZX_HD uint32_t mzx_legal(const ExpertPos& pos) {
     const uint64_t e = ~(pos.me | pos.opp);

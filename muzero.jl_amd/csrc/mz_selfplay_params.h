@@ -127,6 +127,14 @@ struct ExpertArgs {
     int32_t* act;               // self-play mode (scores == null): [G] the search's actions; the rows whose
                                 // mover is not muzero_player get the expert's
     int32_t* scores;            // eval mode: [G][A] score(s, a, D) of every row, -128 for an illegal action
+    // mz_expert_table_move only: the solved TicTacToe table, [19683] entries of 16 bytes,
+    // the first nine of each = score(s, a, 9) as int8 (mz_expert_rules.h: mzx_ttt_code)
+    const int8_t* table;
+    // judge mode, self-play mode only; null in every launch outside a judging evaluation
+    // and mz_expert_judge: the audit row {moves judged, in the best set, outcome given away, score
+    // deficit}.  MuZero's rows (mover == muzero_player, every row with MZ_OPP_SELF) add the four terms
+    // of act[g]; the other rows get the expert's move only with MZ_OPP_EXPERT.
+    long long* judge;
 };
 
 // mz_sp_pick (mz_selfplay.hip): MZ_OPP_NETWORK's choice between the two searches of one move.
@@ -164,6 +172,9 @@ extern "C" __global__ void mz_sp_order(SpParams S);
 extern "C" __global__ void mz_sp_store(SpParams S);
 extern "C" __global__ void mz_sp_reset(SpParams S);
 extern "C" __global__ void mz_expert_move(SpParams S, ExpertArgs X);
+extern "C" __global__ void mz_expert_table_move(SpParams S, ExpertArgs X);
+extern "C" __global__ void mz_expert_table_rows(uint8_t* boards, int32_t* players, int c0, int n);
+extern "C" __global__ void mz_expert_table_pack(const int32_t* scores, int8_t* table, int c0, int n);
 extern "C" __global__ void mz_sp_pick(SpParams S, PickArgs X);
 extern "C" __global__ void mz_test_begin(SpParams S, TestRec R);
 extern "C" __global__ void mz_test_tally(SpParams S, TestRec R);

@@ -9,6 +9,9 @@ For a live position s with player p to move and a depth d >= 1:
                    win of the other player, else -V(s', d - 1);
   V(s, 0) = 0,  V(s, d) = max over the legal a of score(s, a, d).
 The expert plays the k-th (ascending) of the actions with the maximal score.
+
+Also here: the solved TicTacToe table's mirror (ttt_code,
+ttt_decode, solved_table) and the judge's rule for one move (§20.1: judge_move).
 """
 import numpy as np
 
@@ -112,6 +115,90 @@ def expert_scores(name, board, player, depth):
     for a in legal(c):
         out[a] = _score(name, legal, step, c, int(player), a, int(depth))
     return out
+
+
+TTT_CODES = 3 ** 9
+_TTT_FULL = 0x1FF
+_TTT_LINE_MASKS = tuple(sum(1 << c for c in l) for l in _LINES)
+
+
+def ttt_code(board, player):
+    """The solved table's index of a TicTacToe position: the sum
+    over the cells of 3^cell * d, d = 0 empty / 1 the mover's stone / 2 the
+    other player's, cells in the planes' order."""
+    c = _cells("tictactoe", board)
+    if player not in (1, 2):
+        raise ValueError("expert: player must be 1 or 2")
+    return sum(3 ** k * (0 if x == 0 else 1 if x == player else 2) for k, x in enumerate(c))
+
+
+def ttt_decode(code, player=1):
+    """The [p1, p2, empty] planes (uint8 (27,)) of table index `code` with `player` to move."""
+    b = np.zeros(27, np.uint8)
+    for k in range(9):
+        code, d = divmod(code, 3)
+        b[18 + k if d == 0 else 9 * ((player if d == 1 else 3 - player) - 1) + k] = 1
+    return b
+
+
+_solved = {}
+
+
+def _solved_value(me, opp, d):
+    """V(s, d) of the mover-relative position (me, opp: cell bit masks), from the definition."""
+    if d == 0:
+        return 0
+    key = (me, opp, d)
+    v = _solved.get(key)
+    if v is None:
+        v = max(_solved_score(me, opp, a, d) for a in range(9) if not (me | opp) >> a & 1)
+        _solved[key] = v
+    return v
+
+
+def _solved_score(me, opp, a, d):
+    mine = me | 1 << a
+    if any(opp & m == m for m in _TTT_LINE_MASKS):       # Q14: the player now to move holds a line and wins
+        return -d
+    if mine | opp == _TTT_FULL:
+        return 0
+    return -_solved_value(opp, mine, d - 1)
+
+
+_table = None
+
+
+def solved_table():
+    """score(s, a, 9) of all 3^9 mover-relative TicTacToe boards, int8 (19683, 9), ILLEGAL for an occupied
+    cell: the mirror of the device's solved table (mz_expert_table), written from the definition.  Every
+    code is filled, unreachable and finished boards too, each move scored as if the game were still on."""
+    global _table
+    if _table is None:
+        t = np.full((TTT_CODES, 9), ILLEGAL, np.int8)
+        for code in range(TTT_CODES):
+            me = opp = 0
+            x = code
+            for k in range(9):
+                x, d = divmod(x, 3)
+                me |= (d == 1) << k
+                opp |= (d == 2) << k
+            for a in range(9):
+                if not (me | opp) >> a & 1:
+                    t[code, a] = _solved_score(me, opp, a, 9)
+        t.setflags(write=False)
+        _table = t
+    return _table
+
+
+def judge_move(scores, action):
+    """The judge's four terms of the 1-based `action` given its position's scores:
+    (1, c == b, sgn(c) < sgn(b), b - c) with c the action's score and b the best legal score."""
+    scores = np.asarray(scores)
+    c = int(scores[action - 1])
+    if c == ILLEGAL:
+        raise ValueError("expert: action not legal on its board")
+    b = int(scores[scores != ILLEGAL].max())
+    return 1, int(c == b), int(np.sign(c) < np.sign(b)), b - c
 
 
 def expert_pick(scores, r):

@@ -14,7 +14,7 @@ from typing import List, Optional
 import numpy as np
 
 from .config import stacked_features
-from .games.expert import DEFAULT_DEPTH, expert_pick, expert_scores
+from .games.expert import DEFAULT_DEPTH, expert_pick, expert_scores, judge_move, solved_table, ttt_code
 from .rng import rng_below, rng_u32
 
 MZ_RNG_OPPONENT = 7                                               # include/mz_detmath.h
@@ -243,6 +243,25 @@ def evaluation_record(histories, env_name, opponent, muzero_player, players, tra
     return rec
 
 
+def evaluation_audit(histories, env_name, opponent, muzero_player, depth=None):
+    """The audit row of one evaluation (mz_test_audit) from its games: MuZero's moves (the
+    records with to_play == muzero_player, every record when the opponent is "self"), each judged on the
+    board it was made on by the expert's scores at `depth` (None: the env's default).  With c the
+    move's score and b the best legal score a move adds (1, c == b, sgn(c) < sgn(b), b - c) to (moves
+    judged, in the expert's best set, win or draw given away, score deficit).  Integers: exact."""
+    depth = depth or DEFAULT_DEPTH[env_name]
+    table = solved_table() if env_name == "tictactoe" and depth == 9 else None
+    out = [0, 0, 0, 0]
+    for h in histories:
+        for board, tp, a in zip(h.observation_history, h.to_play_history, h.action_history):
+            if opponent != "self" and tp != muzero_player:
+                continue
+            scores = table[ttt_code(board, tp)] if table is not None else expert_scores(env_name, board, tp, depth)
+            for k, x in enumerate(judge_move(scores, a)):
+                out[k] += x
+    return tuple(out)
+
+
 def env_name_of(env_cls):
     """game_winner's name of a batched env class: "tictactoe", "connect4" or "atari"."""
     if getattr(env_cls, "FRAME_STACK", 0):
@@ -251,16 +270,20 @@ def env_name_of(env_cls):
 
 
 def evaluate(engine, env_cls, E, opponent="self", muzero_player=1, rng_step0=0, game_offset=0, temperature=0.0,
-             training_step=0, expert_depth=None, opponent_engine=None):
+             training_step=0, expert_depth=None, opponent_engine=None, audit=False):
     """One evaluation of the test worker on the host: E slots play one game each (move m keyed
-    rng_step0 + m, game_offset); returns (the histories in slot order, their evaluation_record)."""
+    rng_step0 + m, game_offset); returns (the histories in slot order, their evaluation_record), and
+    with audit=True their evaluation_audit at expert_depth as a third item."""
     sp = BatchedSelfPlay(engine, env_cls, E, game_offset=game_offset, step0=rng_step0, opponent=opponent,
                          muzero_player=muzero_player, expert_depth=expert_depth, opponent_engine=opponent_engine)
     histories = sp.play_games(temperature)
     players = engine.conf.players                      # Config.players lists the player ids
-    return histories, evaluation_record(histories, env_name_of(env_cls), opponent, muzero_player,
-                                        players if isinstance(players, int) else len(players), training_step,
-                                        rng_step0)
+    name = env_name_of(env_cls)
+    rec = evaluation_record(histories, name, opponent, muzero_player,
+                            players if isinstance(players, int) else len(players), training_step, rng_step0)
+    if audit:
+        return histories, rec, evaluation_audit(histories, name, opponent, muzero_player, expert_depth)
+    return histories, rec
 
 
 def random_positions(env_cls, G, seed=0, max_plies=6):

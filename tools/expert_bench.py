@@ -15,6 +15,13 @@ and for each expert leg the extra time over the same env's random leg as a
 fraction of that random move.  Run it once more under
 `rocprofv3 --kernel-trace --stats -- python tools/expert_bench.py --moves 50`
 for mz_expert_move's own kernel time.
+
+--table adds, in the same job: the build of the solved TicTacToe
+table (mz_expert_table(1) on fresh handles: the first call, then the median of
+5 more; host wall clock around the host-synchronous call, the device idle
+before it) and the two TicTacToe expert legs again with the table on
+(expert_d9_steady_table, expert_d9_first_move_table), each with its ratio to
+the same job's table-off leg.  Without the flag the output is what it was.
 """
 import argparse
 import dataclasses
@@ -34,7 +41,7 @@ from muzero_jl_amd.games import connect4, tictactoe  # noqa: E402
 from muzero_jl_amd.networks import init_nets  # noqa: E402
 
 
-def leg(eng, env_kind, G, stream, opponent, depth, mzp, warmup, moves, fresh):
+def leg(eng, env_kind, G, stream, opponent, depth, mzp, warmup, moves, fresh, table=False):
     sp = stream.cuda_stream
 
     def init():
@@ -43,6 +50,8 @@ def leg(eng, env_kind, G, stream, opponent, depth, mzp, warmup, moves, fresh):
 
     init()
     eng.expert_depth(depth)
+    if env_kind == abi.ENV_TICTACTOE:
+        eng.expert_table(table)                       # off: the flag only, the launches are the search kernel's
     step = 0
     for _ in range(warmup):
         if fresh:
@@ -64,11 +73,27 @@ def leg(eng, env_kind, G, stream, opponent, depth, mzp, warmup, moves, fresh):
             "ms_max": round(float(ms.max()), 4), "games": eng.eval_results()[0]}
 
 
+def table_build(conf, hyper, G, fresh=6):
+    """mz_expert_table(1) on fresh handles: ms of the first call and the median of the others."""
+    import time
+    ms = []
+    for _ in range(fresh):
+        eng = abi.Engine(conf, hyper, device=0, max_games=G, rng_seed=7)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        eng.expert_table(True)
+        ms.append((time.perf_counter() - t0) * 1e3)
+        eng.close()
+    return {"first_ms": round(ms[0], 3), "median_ms": round(float(np.median(ms[1:])), 3),
+            "all_ms": [round(x, 3) for x in ms]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--games", type=int, default=512)
     ap.add_argument("--moves", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--table", action="store_true", help="also: the solved table's build time and the table-on legs")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     G = args.games
@@ -90,9 +115,16 @@ def main():
         out = {}
         for tag, opp, depth, mzp, fresh in legs:
             out[tag] = leg(eng, env_kind, G, stream, opp, depth, mzp, args.warmup, args.moves, fresh)
+        if args.table and name == "tictactoe":
+            for tag, opp, depth, mzp, fresh in legs:
+                if opp == abi.OPP_EXPERT:
+                    r = leg(eng, env_kind, G, stream, opp, depth, mzp, args.warmup, args.moves, fresh, table=True)
+                    r["over_table_off"] = round(r["ms_median"] / out[tag]["ms_median"], 4)
+                    out[tag + "_table"] = r
+            out["table_build"] = table_build(conf, mod.hyper, G)
         for tag, r in out.items():
             if tag.startswith("expert"):
-                base = out["random_first_move" if tag.endswith("first_move") else "random_steady"]["ms_median"]
+                base = out["random_first_move" if "first_move" in tag else "random_steady"]["ms_median"]
                 r["extra_ms"] = round(r["ms_median"] - base, 4)
                 r["extra_over_random_move"] = round((r["ms_median"] - base) / base, 4)
         res["legs"][name] = {"num_iters": conf.num_iters, **out}
