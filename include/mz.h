@@ -888,6 +888,14 @@ const char* mz_learner_variant(const mz_handle* h);
  * 32768, chosen at create); 0 for the FC nets.                              */
 int mz_resnet_tile_games(const mz_handle* h);
 
+/* Whether mz_downsample_kernel stages the observation in LDS for its first
+ * layer (DsPlan.stage_in, chosen at create: 1 when the observation's floats
+ * are a multiple of 4, two activation buffers plus every conv's parameters
+ * fit in them, and the staged layout fits the LDS; 0 when layer 0 reads the
+ * observation from HBM); -1 without a downsampler (ResNetHP.downsample unset,
+ * or the FC nets).                                                           */
+int mz_downsample_staged(const mz_handle* h);
+
 /* Wait for the engine's work (the device, or the pair mz_set_sync_stream
  * named) and report a device fault.  A kernel that gives up waiting for a
  * cross-workgroup publish (a bounded poll, 2 s) sets a fault word instead of

@@ -164,6 +164,10 @@ end
 learner_mode!(e::Engine, mode::Cint) =
     check(e, ccall((:mz_learner_set_mode, libmz), Cint, (Ptr{Cvoid}, Cint), e.h, mode))
 
+"""downsample_staged(e) — 1 / 0: the downsampler stages the observation in LDS for its first layer or reads it
+from HBM (chosen at create); -1 without a downsampler."""
+downsample_staged(e::Engine) = ccall((:mz_downsample_staged, libmz), Cint, (Ptr{Cvoid},), e.h)
+
 # ---- device self-play and replay shard (play_game's loop body + ReplayBuffer.jl on the GPU)
 selfplay_init!(e::Engine, env::Cint, G, replay_games) =
     check(e, ccall((:mz_selfplay_init, libmz), Cint, (Ptr{Cvoid}, Cint, Cint, Cint), e.h, env, G, replay_games))

@@ -135,6 +135,7 @@ SIGNATURES = {
     "mz_search_variant": (ctypes.c_char_p, [_VP]),
     "mz_learner_variant": (ctypes.c_char_p, [_VP]),
     "mz_resnet_tile_games": (ctypes.c_int, [_VP]),
+    "mz_downsample_staged": (ctypes.c_int, [_VP]),
     "mz_sync": (ctypes.c_int, [_VP]),
 }
 
@@ -802,6 +803,10 @@ class Engine:
     def resnet_tile_games(self):
         """Games per tile of the ResNet network kernels (0 for the FC nets)."""
         return self.lib.mz_resnet_tile_games(self.h)
+
+    def downsample_staged(self):
+        """1 / 0: the downsampler stages the observation in LDS or reads it from HBM; -1 without one."""
+        return self.lib.mz_downsample_staged(self.h)
 
     def sync(self):
         self._check(self.lib.mz_sync(self.h), "mz_sync")

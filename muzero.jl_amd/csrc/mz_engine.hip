@@ -3067,6 +3067,7 @@ const char* mz_learner_variant(const mz_handle* h) {
 }
 
 int mz_resnet_tile_games(const mz_handle* h) { return h && h->kind == 1 ? h->rn_ng : 0; }
+int mz_downsample_staged(const mz_handle* h) { return h && h->kind == 1 && h->ds ? h->dsplan.stage_in : -1; }
 
 // ------------------------------------------------ device self-play + replay
 }  // extern "C"

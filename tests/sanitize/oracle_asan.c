@@ -6,8 +6,9 @@
  * loop (play_game, save_game FIFO, get_batch / make_target, the learner step
  * and ADAM, ora_train_loop), searches with tree dumps on the FC and ResNet
  * TicTacToe nets and the Connect4 FC net, PER sampling and priority updates,
- * evaluation play, and the Atari downsampler forward.  A sanitizer report
- * aborts; exit 0 = clean.  Built and run by tests/test_sanitizers.py. */
+ * evaluation play, the Atari downsampler forward, and the downsampler off
+ * its preset (a non-square kernel, a stacked input: forward, search, learner
+ * step).  A sanitizer report aborts; exit 0 = clean.  Built and run by tests/test_sanitizers.py. */
 #include "../../oracle/mz_oracle.c"
 
 #include <stdio.h>
@@ -75,6 +76,43 @@ static void search(const mz_config* c, const ora_nethp* hp, int G, int feat) {
         if (act[g] < 1 || act[g] > A) { fprintf(stderr, "bad action\n"); exit(1); }
     free(P0); free(P1); free(P2); free(obs); free(legal); free(tp); free(cv); free(rv); free(act);
     free(eN); free(ech); free(ntp); free(eW); free(eP); free(eR);
+}
+
+/* the downsampling representation at one shape: the forward of one observation; with `all` also a search of
+ * 3 games and one ref_semantics learner step (B = 3, K = 2) */
+static void downsampler(int W, int Hh, int C, int stack, int kw, int kh, int A, int all) {
+    mz_config c = ttt_conf(4);
+    c.observation_shape[0] = W; c.observation_shape[1] = Hh; c.observation_shape[2] = C;
+    c.action_space_size = A; c.players = 1; c.stacked_observations = stack;
+    c.num_unroll_steps = 2; c.batch_size = 3;
+    ora_nethp r = rn_hp(1);
+    r.rn.num_blocks = all ? 1 : 2; r.rn.conv_kernel_size[0] = kw; r.rn.conv_kernel_size[1] = kh;
+    const int feat = W * Hh * (C * (stack + 1) + stack);
+    float* P[3];
+    size_t n[3], ntot = 0;
+    for (int k = 0; k < 3; ++k) { n[k] = ora_param_count(&c, &r, k); ntot += n[k]; P[k] = params(&c, &r, k, 0.05f); }
+    const int B = c.batch_size, K = c.num_unroll_steps, H = ora_hidden_size(&c, &r);
+    float* x = malloc(4 * (size_t)B * feat);
+    for (int i = 0; i < B * feat; ++i) x[i] = frand() + 0.5f;
+    float* out = malloc(4 * (size_t)H);
+    ora_net_forward(&c, &r, MZ_NET_REPR, P[0], x, 1, out, NULL);
+    printf("downsampler forward %dx%dx%d stack %d kernel (%d,%d): hidden %d\n", W, Hh, C, stack, kw, kh, H);
+    if (all) {
+        search(&c, &r, 3, feat);
+        float *m = calloc(ntot, 4), *v = calloc(ntot, 4);
+        double bp[2] = {0.9, 0.999};
+        float *act = malloc(4 * B * (K + 1)), *tv = malloc(4 * B * (K + 1)), *tp = malloc(4 * (size_t)B * (K + 1) * A);
+        float *gs = malloc(4 * B), losses[8];
+        for (int i = 0; i < B * (K + 1); ++i) { act[i] = (float)(1 + i % A); tv[i] = frand(); }
+        for (int i = 0; i < B * (K + 1) * A; ++i) tp[i] = 1.0f / (float)A;
+        for (int i = 0; i < B; ++i) gs[i] = (float)(1 + i % K);
+        ora_learner_step(&c, &r, P[0], P[1], P[2], m, v, bp, B, x, act, tv, tp, gs, 1e-3, losses);
+        for (int i = 0; i < 6; ++i)
+            if (!(losses[i] == losses[i])) { fprintf(stderr, "learner step: loss %d is NaN\n", i); exit(1); }
+        free(m); free(v); free(act); free(tv); free(tp); free(gs);
+    }
+    for (int k = 0; k < 3; ++k) free(P[k]);
+    free(x); free(out);
 }
 
 int main(void) {
@@ -148,21 +186,11 @@ int main(void) {
         search(&c4, &f4, 3, 6 * 7 * 7);
     }
     /* 4. the Atari downsampler forward (84x84x4 -> 6x6) */
-    {
-        mz_config c = ttt_conf(2);
-        c.observation_shape[0] = 84; c.observation_shape[1] = 84; c.observation_shape[2] = 4;
-        c.action_space_size = 18; c.players = 1; c.stacked_observations = 0;
-        ora_nethp r = rn_hp(1);
-        float* P0 = params(&c, &r, 0, 0.05f);
-        const int feat = 84 * 84 * 4;
-        float* x = malloc(4 * (size_t)feat);
-        for (int i = 0; i < feat; ++i) x[i] = frand() + 0.5f;
-        const int H = ora_hidden_size(&c, &r);
-        float* out = malloc(4 * (size_t)H);
-        ora_net_forward(&c, &r, MZ_NET_REPR, P0, x, 1, out, NULL);
-        printf("downsampler forward: hidden %d\n", H);
-        free(P0); free(x); free(out);
-    }
+    downsampler(84, 84, 4, 0, 3, 3, 18, 0);
+    /* 5. off the preset (tests/downsample_shapes.py): k53's non-square kernel on a non-square board, and c3s's
+     * stacked input (C = 3, 4995 features) — the forward, a search and a learner step each */
+    downsampler(36, 41, 2, 0, 5, 3, 6, 1);
+    downsampler(37, 45, 1, 1, 3, 3, 9, 1);
     printf("oracle_asan: clean\n");
     return 0;
 }

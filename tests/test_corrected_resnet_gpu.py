@@ -47,10 +47,10 @@ def _batch(B, K, A, feat, rng):
                 gradient_scale=rng.integers(1, max(K, 1) + 1, B).astype(np.float32))
 
 
-def _corrected_against_torch(conf, hyper, B, K, ir, per, ds=False):
+def _corrected_against_torch(conf, hyper, B, K, ir, per, ds=False, observation=None):
     """mz_learner_grad_dev in MZ_LEARN_CORRECTED mode against corrected_loss_and_grads: every net's data
     gradient relative to its largest entry (ds: also the downsampler's slice on its own scale), the
-    losses and the read-outs."""
+    losses and the read-outs.  observation: the batch's (B, features) observations instead of 0/1 planes."""
     import torch
     from muzero_jl_amd import abi
     nets = _lively(conf, hyper, B + K)
@@ -63,6 +63,9 @@ def _corrected_against_torch(conf, hyper, B, K, ir, per, ds=False):
         conf.observation_shape[0] * conf.observation_shape[1] * conf.stacked_observations
     rng = np.random.default_rng(B)
     batch = _batch(B, K, A, feat, rng)
+    if observation is not None:
+        assert observation.shape == (B, feat)
+        batch["observation"] = observation
     wts = (rng.random(B).astype(np.float32) * 0.9 + 0.1) if per else None
     dev = [torch.from_numpy(np.ascontiguousarray(batch[k])).cuda() for k in
            ("observation", "actions", "target_values", "target_rewards", "target_policies", "gradient_scale")]
