@@ -822,6 +822,74 @@ int mz_train_move(mz_handle* h, uint32_t move, uint32_t game_offset, int64_t* nf
 int mz_train_learn(mz_handle* h, int64_t steps, float* losses_dev, int64_t* state_out, void* stream);
 int mz_train_weights_get(mz_handle* h, int which, int net, float* flat, size_t n);
 
+/* ---- The run log: per-interval loss and self-play records ------
+ * The shared storage of the reference's job sketch (src/muzero.jl:11-33, "Write
+ * everything in TensorBoard"; Learning.jl:416-424 prints the three losses at
+ * every checkpoint), kept on the device: nothing is read back, nothing waits
+ * on the host, and a job with the log on is bit for bit the job without it.
+ *   mz_train_set_log: interval > 0 switches the log on, 0 (the default) off.
+ *     A handle setting like mz_train_set_test's: mz_selfplay_init and
+ *     mz_snapshot_load keep it, snapshots do not carry it.  The first interval
+ *     > 0 allocates the accumulators, the loss rows of one learner chunk and
+ *     the record ring; they live with the handle.  Switching the log on (from
+ *     off) zeroes the accumulators and takes the games the shard has seen so
+ *     far as not this log's; so do mz_selfplay_init and a passing
+ *     mz_snapshot_load (the file's games are not this log's).  The ring and
+ *     the record count survive all three.  Refused: a negative interval.
+ *     With the log on, every move of mz_train_run / mz_train_move in
+ *     MZ_SP_TRAIN mode is followed by one launch of mz_log_games, which folds
+ *     the shard games numbered max(logged_upto, played - held) + 1 .. played
+ *     (its own saves, and games mz_replay_save_game put in since the last
+ *     move); games that were evicted before a fold reached them are counted as
+ *     missed.  Every learner chunk of mz_train_run / mz_train_learn (up to 256
+ *     steps) writes each step's six losses to the handle's rows and is
+ *     followed by one launch of mz_log_steps; losses_dev gets a copy of the
+ *     last row.  After a move's (mz_train_run) or a call's (mz_train_learn)
+ *     learner steps took the learner from t0 to t1 with t1 / interval > t0 /
+ *     interval, one launch of mz_log_commit writes one record and zeroes the
+ *     accumulators (the chunk is not cut).  So the split loop gets the records
+ *     mz_train_run gets.  At world > 1 every rank logs its own shard and
+ *     steps; nothing is exchanged.  Off: none of the three is launched and
+ *     every pointer is the caller's as without the call.
+ *     Record e is kept in slot e % MZ_LOG_RECORDS of the ring.  Sums and
+ *     counts, never means: the host divides.
+ *       counts[16] = {training step t1 at the commit, learner steps folded
+ *                     since the previous record, num_played_games,
+ *                     num_played_steps, positions held (total_samples), games
+ *                     held, the count mz_replay_reanalysed_count reads, games
+ *                     folded since the previous record, their moves (Σ
+ *                     length), wins of player 1, wins of player 2, draws,
+ *                     actor refreshes (state_out[2]), games missed, 0, 0}
+ *       sums[16]   = {Σ over the folded steps of value, reward, policy,
+ *                     l2_repr, l2_pred, l2_dyn [0..5], the same six of the
+ *                     last folded step alone [6..11] (zeros when no step was
+ *                     folded), η = Cos(t1) [12], Σ rewards [13], Σ stored root
+ *                     values [14] and Σ over the positions of max_a
+ *                     child_visits[a] [15] of the folded games}
+ *     counts[2..6] are the shard's words at the commit's point of the stream.
+ *     Winner and draw: the engine's rule on each game's last record, as
+ *     mz_eval_results reads them (TicTacToe, Q14: a nonzero reward is a win of
+ *     3 - mover; every other env: of the mover; zero: a draw).  The numerics
+ *     are part of the contract: the loss sums add (double) of each f32 loss in
+ *     ascending step; a game's three sums start at +0 and add (double)x in
+ *     record order, the maximum taken in f32; the accumulator adds the games'
+ *     sums in ascending game number.  No float atomics.
+ *     learning.run_log_record is the exact host mirror.
+ *   mz_train_log_flush: one record now from whatever is accumulated (zero fold
+ *     counts when nothing is), stream-ordered.  Refused before mz_train_init
+ *     and with the log off.
+ *   mz_train_log_results: the latest min(max_records, held) records, oldest
+ *     first (held = min(total, MZ_LOG_RECORDS)); *total = records since create
+ *     / mz_train_log_clear; counts [n][16], sums [n][16]; any pointer may be
+ *     NULL.  Synchronises.  Refused: max_records < 0.
+ *   mz_train_log_clear: total back to 0 and the accumulators zeroed (the games
+ *     already folded stay folded).  Synchronises when the log was ever on.   */
+enum { MZ_LOG_RECORDS = 1024 };
+int mz_train_set_log(mz_handle* h, int64_t interval);
+int mz_train_log_flush(mz_handle* h, void* stream);
+int mz_train_log_results(mz_handle* h, int64_t* total, int64_t* counts, double* sums, int32_t max_records);
+int mz_train_log_clear(mz_handle* h);
+
 /* ---- Checkpoints -------------------------------------------
  * Replace serialize(joinpath(networks_path, "$(step)_<net>.bin"), net)
  * (Learning.jl:424-431) and play.jl's deserialize: one safetensors file with
@@ -867,7 +935,9 @@ int mz_checkpoint_load(mz_handle* h, const char* path, int64_t* training_step);
  * The test worker's settings (mz_test_config, mz_train_set_test,
  * mz_test_audit) and its record and audit rings are handle settings too, as
  * are mz_expert_table's switch and table: not written, and they survive the
- * load; the test slots are re-created by the next mz_test_play.
+ * load; the test slots are re-created by the next mz_test_play.  The run log
+ * (mz_train_set_log) likewise: its setting, ring and record count survive the
+ * load, its accumulators start over.
  * At world > 1 each rank saves
  * and loads its own file; the host orders the calls.                          */
 int mz_snapshot_save(mz_handle* h, const char* path, int64_t training_step);

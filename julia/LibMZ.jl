@@ -348,6 +348,24 @@ train_set_test!(e::Engine, interval; game_offset=0, temperature=0f0) =
     check(e, ccall((:mz_train_set_test, libmz), Cint, (Ptr{Cvoid}, Int64, UInt32, Float32),
                    e.h, interval, game_offset, temperature))
 
+# ---- the run log (DESIGN §21): per-interval loss and self-play records kept on the device.  train_run! /
+# train_learn! then commit one record after every move / call whose learner steps crossed a multiple of `interval`
+# (0, the default: the log is off)
+train_set_log!(e::Engine, interval) =
+    check(e, ccall((:mz_train_set_log, libmz), Cint, (Ptr{Cvoid}, Int64), e.h, interval))
+# one record now from whatever is accumulated (stream-ordered)
+train_log_flush!(e::Engine) = check(e, ccall((:mz_train_log_flush, libmz), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), e.h, C_NULL))
+# (records so far, counts (16, n), sums (16, n)), the latest n records, oldest first; the rows: include/mz.h.
+# Sums and counts, never means: the host divides
+function train_log_results(e::Engine; max_records=1024)
+    total = Ref{Int64}(0); counts = zeros(Int64, 16, max_records); sums = zeros(Float64, 16, max_records)
+    check(e, ccall((:mz_train_log_results, libmz), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Float64}, Int32),
+                   e.h, total, counts, sums, max_records))
+    n = min(max_records, total[], 1024)
+    total[], counts[:, 1:n], sums[:, 1:n]
+end
+train_log_clear!(e::Engine) = check(e, ccall((:mz_train_log_clear, libmz), Cint, (Ptr{Cvoid},), e.h))
+
 """The actor–learner loop of self_play! ‖ learning! (src/SelfPlay.jl:384-419,
 src/Learning.jl:306-438; quirk Q16) on one GPU: `moves` self-play moves with the
 actors' nets, one learner step per finished game, the actors one checkpoint behind.

@@ -29,6 +29,14 @@ TEST_COUNT_FIELDS = ("training_step", "games", "muzero_wins", "opponent_wins", "
 TEST_SUM_FIELDS = ("reward_muzero", "reward_opponent", "value_sum")
 # one audit row (mz_test_audit_results, mz_expert_judge); judged == -1: the evaluation ran with judging off
 TEST_AUDIT_FIELDS = ("judged", "best", "blunders", "deficit")
+# the run log (mz_train_log_results): counts[16] then sums[16]; sums and counts, never means
+LOG_RECORDS = 1024                               # MZ_LOG_RECORDS: the run log's record ring
+LOG_COUNT_FIELDS = ("training_step", "steps", "num_played_games", "num_played_steps", "positions_held", "games_held",
+                    "reanalysed", "games", "moves", "wins_p1", "wins_p2", "draws", "refreshes", "missed",
+                    "reserved14", "reserved15")
+LOG_SUM_FIELDS = ("value", "reward", "policy", "l2_repr", "l2_pred", "l2_dyn", "last_value", "last_reward",
+                  "last_policy", "last_l2_repr", "last_l2_pred", "last_l2_dyn", "eta", "reward_sum", "root_value_sum",
+                  "sharpness_sum")
 TTT_CODES = 19683                                # the solved TicTacToe table's entries (mz_expert_table)
 
 _lib = None
@@ -97,6 +105,10 @@ SIGNATURES = {
     "mz_test_audit_results": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int32]),
     "mz_test_get_game": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mz_train_set_test": (ctypes.c_int, [_VP, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float]),
+    "mz_train_set_log": (ctypes.c_int, [_VP, ctypes.c_int64]),
+    "mz_train_log_flush": (ctypes.c_int, [_VP, _VP]),
+    "mz_train_log_results": (ctypes.c_int, [_VP, _VP, _VP, _VP, ctypes.c_int32]),
+    "mz_train_log_clear": (ctypes.c_int, [_VP]),
     "mz_replay_counts": (ctypes.c_int, [_VP, _VP, _VP]),
     "mz_replay_save_game": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mz_replay_sample": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(MzBatch), _VP, _VP]),
@@ -583,6 +595,35 @@ class Engine:
         multiple of `interval` (test_play(t1, t1 * (max_moves + 1), game_offset, temperature)); 0 = off."""
         self._check(self.lib.mz_train_set_test(self.h, int(interval), game_offset & 0xffffffff, temperature),
                     "mz_train_set_test")
+
+    # ---- the run log (DESIGN §21): per-interval loss and self-play records kept on the device
+    def train_set_log(self, interval):
+        """One record after every move (train_run) or call (train_learn) whose learner steps crossed a
+        multiple of `interval`; 0 = off.  A handle setting."""
+        self._check(self.lib.mz_train_set_log(self.h, int(interval)), "mz_train_set_log")
+
+    def train_log_flush(self, stream=None):
+        """One record now from whatever is accumulated.  Stream-ordered, no host synchronisation."""
+        self._check(self.lib.mz_train_log_flush(self.h, stream), "mz_train_log_flush")
+
+    def train_log_results(self, max_records=LOG_RECORDS):
+        """(records since create / train_log_clear, the latest records oldest first): each record a dict of
+        LOG_COUNT_FIELDS (int) and LOG_SUM_FIELDS (np.float64).  Synchronises."""
+        total = ctypes.c_int64()
+        counts = np.zeros((max(max_records, 1), 16), np.int64)
+        sums = np.zeros((max(max_records, 1), 16), np.float64)
+        self._check(self.lib.mz_train_log_results(self.h, ctypes.byref(total), _p(counts), _p(sums), max_records),
+                    "mz_train_log_results")
+        n = min(max_records, total.value, LOG_RECORDS)
+        recs = []
+        for c, s in zip(counts[:n], sums[:n]):
+            r = {k: int(v) for k, v in zip(LOG_COUNT_FIELDS, c)}
+            r.update({k: np.float64(v) for k, v in zip(LOG_SUM_FIELDS, s)})
+            recs.append(r)
+        return int(total.value), recs
+
+    def train_log_clear(self):
+        self._check(self.lib.mz_train_log_clear(self.h), "mz_train_log_clear")
 
     def replay_counts(self):
         """({num_played_games, num_played_steps, total_samples}, games held)."""

@@ -228,6 +228,14 @@ struct mz_handle {
         int32_t* done = nullptr; int32_t* frozen = nullptr; float* temp = nullptr;
         float* cv2 = nullptr; float* rv2 = nullptr; int32_t* act2 = nullptr;   // MZ_OPP_NETWORK's second outputs
     } ts;
+    // the run log (mz_train_set_log).  The interval is a handle setting; the accumulators,
+    // the chunk's loss rows and the record ring are the handle's, allocated by the first interval > 0
+    int64_t log_interval = 0;
+    LogAcc* d_log_acc = nullptr;
+    float* d_log_rows = nullptr;                          // [MZ_MULTI_LMAX][8]
+    long long* d_log_counts = nullptr;                    // [MZ_LOG_RECORDS][16]
+    double* d_log_sums = nullptr;                         // [MZ_LOG_RECORDS][16]
+    int64_t log_total = 0;                                // records since create / mz_train_log_clear
     float* d_sp_dpow = nullptr;
     float *d_rs_obs = nullptr, *d_rs_act = nullptr, *d_rs_tv = nullptr, *d_rs_tr = nullptr, *d_rs_tp = nullptr,
           *d_rs_gs = nullptr;
@@ -3308,6 +3316,18 @@ static int sp_move_body(mz_handle* h, const SpParams& S, float* cv2, float* rv2,
     return 0;
 }
 
+// the run log starts over on a new shard (mz_selfplay_init, a passing mz_snapshot_load, the log
+// switched on): zero accumulators, and the shard's `played` games so far are not this log's.  The
+// record ring and log_total stay.  The caller has drained the device.
+static int log_rebase(mz_handle* h, long long played) {
+    if (!h->d_log_acc) return 0;
+    LogAcc a;
+    std::memset(&a, 0, sizeof(a));
+    a.logged_upto = played;
+    MZ_TRY(h, hipMemcpy(h->d_log_acc, &a, sizeof(a), hipMemcpyHostToDevice));
+    return 0;
+}
+
 extern "C" {
 
 int mz_selfplay_init(mz_handle* h, int env_kind, int G, int replay_games) {
@@ -3362,6 +3382,7 @@ int mz_selfplay_init(mz_handle* h, int env_kind, int G, int replay_games) {
     for (int n = 0; n < (int)dp.size(); ++n) dp[n] = (float)std::pow((double)c.discount, (double)n);
     MZ_TRY(h, spalloc(h, &h->d_sp_dpow, dp.size()));
     MZ_TRY(h, hipMemcpy(h->d_sp_dpow, dp.data(), dp.size() * 4, hipMemcpyHostToDevice));
+    if (log_rebase(h, 0)) return -1;                    // the run log: a new shard (its ring and setting stay)
     if (env_kind == MZ_ENV_ATARI) {
         // every slot: new game, its key and first frame drawn on the device at
         // the first mz_selfplay_move, keyed by the global game id game_offset +
@@ -4786,6 +4807,68 @@ int mz_train_set_test(mz_handle* h, int64_t interval, uint32_t game_offset, floa
     return 0;
 }
 
+// ---- the run log's host side (the launches: log_games / log_steps / log_commit below)
+int mz_train_set_log(mz_handle* h, int64_t interval) {
+    if (!h) return -2;
+    if (interval < 0) return fail(h, "mz_train_set_log: interval must be >= 0");
+    if (interval > 0 && h->log_interval == 0) {     // switched on: the shard's games so far are not this log's
+        MZ_TRY(h, hipSetDevice(h->device));
+        MZ_SYNC(h);
+        if (!h->d_log_acc) {
+            MZ_TRY(h, dalloc(h, &h->d_log_acc, 1));
+            MZ_TRY(h, dalloc(h, &h->d_log_rows, (size_t)MZ_MULTI_LMAX * 8));
+            MZ_TRY(h, dalloc(h, &h->d_log_counts, (size_t)MZ_LOG_RECORDS * 16));
+            MZ_TRY(h, dalloc(h, &h->d_log_sums, (size_t)MZ_LOG_RECORDS * 16));
+        }
+        long long played = 0;
+        if (h->sp_env >= 0) MZ_TRY(h, hipMemcpy(&played, h->d_sp_counters, sizeof(played), hipMemcpyDeviceToHost));
+        if (log_rebase(h, played)) return -1;
+    }
+    h->log_interval = interval;
+    return 0;
+}
+
+static int log_commit(mz_handle* h, hipStream_t st);
+
+int mz_train_log_flush(mz_handle* h, void* stream) {
+    if (!h) return -2;
+    if (!h->tr_B) return fail(h, "mz_train_init first");
+    if (h->log_interval <= 0) return fail(h, "mz_train_log_flush: the run log is off (mz_train_set_log first)");
+    MZ_TRY(h, hipSetDevice(h->device));
+    return log_commit(h, stream_of(h, stream));
+}
+
+int mz_train_log_results(mz_handle* h, int64_t* total, int64_t* counts, double* sums, int32_t max_records) {
+    if (!h) return -2;
+    if (max_records < 0) return fail(h, "mz_train_log_results: max_records must be >= 0");
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);
+    if (total) *total = h->log_total;
+    const int64_t held = std::min<int64_t>(h->log_total, MZ_LOG_RECORDS);
+    const int64_t n = std::min<int64_t>(max_records, held);
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t slot = (size_t)((h->log_total - n + i) % MZ_LOG_RECORDS);
+        long long c[16];
+        if (counts) {
+            MZ_TRY(h, hipMemcpy(c, h->d_log_counts + slot * 16, sizeof(c), hipMemcpyDeviceToHost));
+            for (int k = 0; k < 16; ++k) counts[i * 16 + k] = c[k];
+        }
+        if (sums) MZ_TRY(h, hipMemcpy(sums + i * 16, h->d_log_sums + slot * 16, 16 * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+int mz_train_log_clear(mz_handle* h) {
+    if (!h) return -2;
+    h->log_total = 0;
+    if (!h->d_log_acc) return 0;
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);
+    long long upto = 0;                             // the games folded so far stay folded
+    MZ_TRY(h, hipMemcpy(&upto, &h->d_log_acc->logged_upto, sizeof(upto), hipMemcpyDeviceToHost));
+    return log_rebase(h, upto);
+}
+
 int mz_selfplay_slots(mz_handle* h, int32_t* history_len, uint8_t* board, int32_t* player) {
     if (!h) return -2;
     if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
@@ -4919,6 +5002,41 @@ static int train_rean_rounds(mz_handle* h, uint32_t move, uint32_t game_offset, 
     return 0;
 }
 
+// ---- the run log: three tiny launches in stream order, nothing read back
+// behind a training move's mz_sp_store: the shard's new games
+static int log_games(mz_handle* h, hipStream_t st) {
+    hipLaunchKernelGGL(mz_log_games, dim3(1), dim3(1024), 0, st, sp_params(h), h->d_log_acc);
+    MZ_TRY(h, hipGetLastError());
+    return 0;
+}
+// behind a learner chunk: its n loss rows in d_log_rows
+static int log_steps(mz_handle* h, int n, hipStream_t st) {
+    LogArgs L;
+    std::memset(&L, 0, sizeof(L));
+    L.acc = h->d_log_acc; L.rows = h->d_log_rows; L.n = n;
+    hipLaunchKernelGGL(mz_log_steps, dim3(1), dim3(64), 0, st, L);
+    MZ_TRY(h, hipGetLastError());
+    return 0;
+}
+// record log_total from whatever is accumulated, with the learner at step tr_t
+static int log_commit(mz_handle* h, hipStream_t st) {
+    const size_t slot = (size_t)(h->log_total % MZ_LOG_RECORDS);
+    LogArgs L;
+    std::memset(&L, 0, sizeof(L));
+    L.acc = h->d_log_acc; L.counts = h->d_log_counts + slot * 16; L.sums = h->d_log_sums + slot * 16;
+    L.counters = h->d_sp_counters; L.cap = h->sp_cap;
+    L.t1 = h->tr_t; L.refreshes = h->tr_refresh; L.eta = cos_schedule(h->tr_t);
+    hipLaunchKernelGGL(mz_log_commit, dim3(1), dim3(64), 0, st, L);
+    MZ_TRY(h, hipGetLastError());
+    ++h->log_total;
+    return 0;
+}
+// the commit rule (the test worker's): the call's learner steps crossed a multiple of the interval
+static int log_crossed(mz_handle* h, int64_t t0, hipStream_t st) {
+    const int64_t iv = h->log_interval;
+    return iv > 0 && h->tr_t / iv > t0 / iv ? log_commit(h, st) : 0;
+}
+
 // 1. one self-play move with the actors' nets (SelfPlay.jl:343-380); temperature
 //    visit_softmax_temperature_fn(t) (:48-56, 396-397) for the games that start on
 //    this move (a game in progress keeps its own).  *nfin = the games save_game
@@ -4940,6 +5058,9 @@ static int train_move(mz_handle* h, uint32_t move, uint32_t game_offset, int64_t
     hipLaunchKernelGGL(mz_tr_publish, dim3(1), dim3(64), 0, st, (const long long*)h->d_sp_counters,
                        (const unsigned*)h->d_fault, h->h_tr_pub, seq);
     MZ_TRY(h, hipGetLastError());
+    // the run log folds the shard's new games (the move's saves, and any a host put in since the last
+    // move) behind the hand-back, so the host's wait overlaps it
+    if (h->log_interval > 0 && !h->sp_eval && log_games(h, st)) return -1;
     if (rean && train_rean_rounds(h, move, game_offset, st)) return -1;
     if (tr_wait_publish(h, seq, st)) return -1;
     h->h_tr_cnt[0] = h->h_tr_pub[0];
@@ -5011,16 +5132,25 @@ static int train_learn(mz_handle* h, int64_t nreq, float* losses_dev, hipStream_
             n = std::min<int64_t>(n, tb - t0 + 1);
         }
         const int64_t t = t0 + n - 1;
+        // the run log: every step's losses go to the handle's rows, mz_log_steps folds them behind the
+        // chunk, and the caller's losses_dev gets a copy of the last row.  Off: the pointers below are
+        // the caller's as ever and nothing more is issued.
+        float* rows = h->log_interval > 0 ? h->d_log_rows : nullptr;
         if (n == 1) {
-            if (mz_learner_train_dev(h, h->tr_B, (uint32_t)t, cos_schedule(t), losses_dev, st)) return -1;
+            if (mz_learner_train_dev(h, h->tr_B, (uint32_t)t, cos_schedule(t), rows ? rows : losses_dev, st)) return -1;
             for (int j = 0; j < 2; ++j)
                 if (cap.t[j] == t)
                     MZ_TRY(h, hipMemcpyAsync(cap.dst[j], h->d_flat, h->nflat * 4, hipMemcpyDeviceToDevice, st));
         } else {
             for (int64_t i = 0; i < n; ++i) eta[i] = cos_schedule(t0 + i);
-            if (learner_multi(h, h->tr_B, (uint32_t)t0, (int32_t)n, eta, nullptr, nullptr, st, losses_dev,
+            if (learner_multi(h, h->tr_B, (uint32_t)t0, (int32_t)n, eta, rows, nullptr, st, rows ? nullptr : losses_dev,
                               per_refresh ? nullptr : &cap))
                 return -1;
+        }
+        if (rows) {
+            if (losses_dev)
+                MZ_TRY(h, hipMemcpyAsync(losses_dev, rows + 8 * (n - 1), 6 * 4, hipMemcpyDeviceToDevice, st));
+            if (log_steps(h, (int)n, st)) return -1;
         }
         h->tr_t = t;
         *done += n;
@@ -5063,7 +5193,9 @@ int mz_train_learn(mz_handle* h, int64_t steps, float* losses_dev, int64_t* stat
     if (steps < 0) return fail(h, "steps must be >= 0");
     MZ_TRY(h, hipSetDevice(h->device));
     int64_t done = 0;
+    const int64_t t0 = h->tr_t;
     if (train_learn(h, steps, losses_dev, stream_of(h, stream), &done)) return -1;
+    if (log_crossed(h, t0, stream_of(h, stream))) return -1;       // the run log's commit rule, per call
     if (state_out) {
         state_out[0] = h->tr_t; state_out[1] = h->tr_games; state_out[2] = h->tr_refresh; state_out[3] = done;
     }
@@ -5087,6 +5219,7 @@ int mz_train_run(mz_handle* h, int32_t moves, uint32_t move0, uint32_t game_offs
         const int64_t t0 = h->tr_t;
         if (train_learn(h, nfin, losses_dev, st, &done)) return -1;
         steps += done;
+        if (log_crossed(h, t0, st)) return -1;      // the run log's commit rule, per move (mz_train_set_log)
         // the test worker (mz_train_set_test): the move's learner steps crossed a multiple of the
         // interval -> one evaluation with the learner's nets after the move's last step (the chunk is
         // not cut), where the next move's Reanalyse rounds search with them too
@@ -5268,5 +5401,5 @@ int mz_snap_restore_end(mz_handle* h, const long long* counters, int reset_pendi
     }
     ++h->pf_epoch;                           // no batch drawn ahead survives: the next step samples in place
     MZ_SYNC(h);
-    return 0;
+    return log_rebase(h, counters[0]);       // the run log: the file's games are not this log's
 }

@@ -9,7 +9,9 @@
 // get_batch + make_target on the ring, writing an mz_batch in HBM.  The test
 // worker plays its own slots with the same prepare / pick / commit
 // in their one-game mode (S.frozen), between mz_test_begin and, per move,
-// mz_test_tally in place of mz_sp_order / mz_sp_store.
+// mz_test_tally in place of mz_sp_order / mz_sp_store.  The run log (DESIGN
+// §21) folds the shard's new games, the learner's loss rows and the records
+// with mz_log_games / mz_log_steps / mz_log_commit.
 //
 // Env rules: TicTacToe exactly as games/tictactoe/game.jl with quirk Q14 (the
 // win test looks at the plane of the player TO MOVE; reward ±1 by the mover's
@@ -299,6 +301,124 @@ extern "C" __global__ __launch_bounds__(1024) void mz_test_tally(SpParams S, Tes
         R.counts[5] = moves; R.counts[6] = vmoves;
         R.sums[0] = s0; R.sums[1] = s1; R.sums[2] = s2;
     }
+}
+
+// ------------------------------------------------------------ run log
+// (mz_train_set_log).  mz_log_games, behind mz_sp_store of a
+// training move: the shard games numbered max(logged_upto, played - held) + 1
+// .. played go into the accumulators (game n lives in ring slot (n - 1) mod
+// cap); the games between logged_upto and that range were evicted unseen and
+// count as missed.  One workgroup, 1024 games per pass.  Every thread sums its
+// own game serially in f64 (+0, then + (double)x in record order); thread 0
+// then adds the pass's games in ascending game number.  No float atomics: the
+// host mirror (learning.run_log_record) is exact.
+extern "C" __global__ __launch_bounds__(1024) void mz_log_games(SpParams S, LogAcc* acc) {
+    __shared__ double gs[3][1024];
+    __shared__ int gi[2][1024];                    // 0 player 1 won | 1 player 2 | 2 draw; length
+    const int tid = threadIdx.x;
+    const long long played = S.counters[0];
+    const long long held = played < S.cap ? played : S.cap;
+    const long long upto = acc->logged_upto;
+    if (upto >= played) {                          // nothing new
+        if (tid == 0) acc->logged_upto = played;
+        return;
+    }
+    const long long oldest = played - held;        // the newest game number no longer held
+    const long long first = (upto > oldest ? upto : oldest) + 1;
+    const long long n = played - first + 1;        // 1..cap
+    long long games = 0, moves = 0, w0 = 0, w1 = 0, w2 = 0;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    if (tid == 0) {
+        games = acc->games; moves = acc->moves; w0 = acc->wins[0]; w1 = acc->wins[1]; w2 = acc->wins[2];
+        s0 = acc->gsum[0]; s1 = acc->gsum[1]; s2 = acc->gsum[2];
+    }
+    for (long long base = 0; base < n; base += 1024) {
+        const long long k = base + tid;
+        int cls = 2, len = 0;
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+        if (k < n) {
+            const int slot = (int)((first + k - 1) % S.cap);
+            len = S.ring.len[slot];
+            len = len < 0 ? 0 : len > S.T ? S.T : len;
+            const size_t r0 = (size_t)slot * S.T;
+            for (int j = 0; j < len; ++j) {
+                a0 = a0 + (double)S.ring.rew[r0 + j];
+                a1 = a1 + (double)S.ring.rv[r0 + j];
+                const float* cv = S.ring.cv + (r0 + j) * S.A;
+                float mx = cv[0];
+                for (int a = 1; a < S.A; ++a) mx = cv[a] > mx ? cv[a] : mx;
+                a2 = a2 + (double)mx;
+            }
+            const int w = len > 0 ? game_winner(S, S.ring.rew[r0 + len - 1], S.ring.tp[r0 + len - 1]) : 0;
+            cls = w == 1 ? 0 : w == 2 ? 1 : 2;
+        }
+        gs[0][tid] = a0; gs[1][tid] = a1; gs[2][tid] = a2;
+        gi[0][tid] = cls; gi[1][tid] = len;
+        __syncthreads();
+        if (tid == 0) {
+            const int m = (int)(n - base < 1024 ? n - base : 1024);
+            for (int j = 0; j < m; ++j) {
+                const int c = gi[0][j];
+                games += 1; moves += gi[1][j]; w0 += c == 0; w1 += c == 1; w2 += c == 2;
+                s0 = s0 + gs[0][j]; s1 = s1 + gs[1][j]; s2 = s2 + gs[2][j];
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        acc->games = games; acc->moves = moves; acc->wins[0] = w0; acc->wins[1] = w1; acc->wins[2] = w2;
+        acc->gsum[0] = s0; acc->gsum[1] = s1; acc->gsum[2] = s2;
+        acc->missed += first - 1 - upto;
+        acc->logged_upto = played;
+    }
+}
+
+// Behind a learner chunk: its n <= 256 loss rows, in ascending step, into the
+// six sums; the last row is kept.  One wave, lane j < 6 owns loss j.
+extern "C" __global__ __launch_bounds__(64) void mz_log_steps(LogArgs L) {
+    const int j = threadIdx.x;
+    if (L.n < 1) return;
+    if (j < 6) {
+        double s = L.acc->loss[j];
+        for (int i = 0; i < L.n; ++i) s = s + (double)L.rows[8 * i + j];
+        L.acc->loss[j] = s;
+        L.acc->last[j] = (double)L.rows[8 * (L.n - 1) + j];
+    }
+    if (j == 6) L.acc->steps += L.n;
+}
+
+// One record from the accumulators and the shard's counters as they stand at
+// this point of the stream (layout: mz.h); the accumulators start over,
+// logged_upto stays.  One thread per word of the record.
+extern "C" __global__ __launch_bounds__(64) void mz_log_commit(LogArgs L) {
+    const int i = threadIdx.x;
+    LogAcc* a = L.acc;
+    long long c = 0;
+    double s = 0.0;
+    if (i < 16) {
+        const long long played = L.counters[0];
+        switch (i) {
+            case 0: c = L.t1; break;
+            case 1: c = a->steps; break;
+            case 2: c = played; break;
+            case 3: c = L.counters[1]; break;
+            case 4: c = L.counters[2]; break;
+            case 5: c = played < L.cap ? played : L.cap; break;
+            case 6: c = L.counters[3]; break;
+            case 7: c = a->games; break;
+            case 8: c = a->moves; break;
+            case 9: case 10: case 11: c = a->wins[i - 9]; break;
+            case 12: c = L.refreshes; break;
+            case 13: c = a->missed; break;
+            default: break;
+        }
+        s = i < 6 ? a->loss[i] : i < 12 ? a->last[i - 6] : i == 12 ? L.eta : a->gsum[i - 13];
+    }
+    __syncthreads();                               // every word is read before the accumulators are zeroed
+    if (i < 16) { L.counts[i] = c; L.sums[i] = s; }
+    if (i < 6) { a->loss[i] = 0.0; a->last[i] = 0.0; }
+    if (i < 3) { a->wins[i] = 0; a->gsum[i] = 0.0; }
+    if (i == 0) { a->steps = 0; a->games = 0; a->moves = 0; a->missed = 0; }
 }
 
 // Ring slots of this move's finished games in slot order (the host driver

@@ -120,6 +120,32 @@ struct TestRec {
     int players;                // conf.players: with 1 every record is MuZero's
 };
 
+// The run log (mz_log_games / mz_log_steps / mz_log_commit in mz_selfplay.hip): the
+// device accumulators between two records.  Sums and counts, never means.
+struct LogAcc {
+    long long steps;            // learner steps folded
+    long long games, moves;     // shard games folded, Σ length
+    long long wins[3];          // player 1, player 2, draws (game_winner on the last record)
+    long long missed;           // games that entered the shard and left it before a fold reached them
+    long long logged_upto;      // the highest game number already folded (mz_log_commit keeps it)
+    double loss[6];             // Σ (double) of {value, reward, policy, l2_repr, l2_pred, l2_dyn}, ascending step
+    double last[6];             // the same six of the last folded step
+    double gsum[3];             // Σ rewards, Σ root values, Σ_positions max_a child_visits[a]
+};
+
+struct LogArgs {
+    LogAcc* acc;
+    // mz_log_steps: n loss rows of 8 floats (the first six are the losses), ascending step
+    const float* rows; int n;
+    // mz_log_commit: the record's ring slot, the shard's counters, and the host's words
+    long long* counts;          // [16]
+    double* sums;               // [16]
+    const long long* counters;  // [MZ_SP_COUNTERS]
+    int cap;
+    long long t1, refreshes;
+    double eta;
+};
+
 // mz_expert_move (mz_expert.hip): the rules-search expert opponent.  The rows are SpParams'
 // (G, env, A, osz, board, player; in self-play mode also muzero_player, seed, step, game_offset).
 struct ExpertArgs {
@@ -178,6 +204,9 @@ extern "C" __global__ void mz_expert_table_pack(const int32_t* scores, int8_t* t
 extern "C" __global__ void mz_sp_pick(SpParams S, PickArgs X);
 extern "C" __global__ void mz_test_begin(SpParams S, TestRec R);
 extern "C" __global__ void mz_test_tally(SpParams S, TestRec R);
+extern "C" __global__ void mz_log_games(SpParams S, LogAcc* acc);
+extern "C" __global__ void mz_log_steps(LogArgs L);
+extern "C" __global__ void mz_log_commit(LogArgs L);
 extern "C" __global__ void mz_rp_sample(RpSampleParams Q);
 extern "C" __global__ void mz_rp_per_init(SpHist ring, int slot, int len, int Tmax, int td, const float* disc_pow,
                                           int alpha);
