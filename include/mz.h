@@ -354,9 +354,18 @@ int mz_selfplay_move(mz_handle* h, uint32_t rng_step, uint32_t game_offset, floa
  * mz_debug_enable(h, 1) the dumped tree is the second (the opponent's)
  * search's.  Refused until the opponent set is complete, and on the
  * one-player frame-stack env.  No other mode launches or allocates anything
- * for it.                                                                    */
+ * for it.
+ * MZ_OPP_MCTS (board envs only): on the same turns the opponent
+ * is a vanilla MCTS over the true rules with uniform random rollouts, one
+ * extra launch per move and no network: S simulations of R rollouts each
+ * (mz_mcts_opponent), UCT with exploration constant 1, every draw from the
+ * Philox ROLLOUT stream keyed (game id, rng_step).  It plays the k-th
+ * (ascending) of the root actions with the most simulations, k =
+ * mz_rng_below(the OPPONENT stream's draw, their count).  Its strength grows
+ * with S at a cost linear in S.  The launch is issued in this mode only.    */
 enum { MZ_SP_TRAIN = 0, MZ_SP_EVAL = 1 };
 enum { MZ_OPP_SELF = 0, MZ_OPP_RANDOM = 1, MZ_OPP_EXPERT = 2, MZ_OPP_NETWORK = 3 };
+enum { MZ_OPP_MCTS = MZ_OPP_NETWORK + 1 };                /* 4: the next opponent id */
 int mz_selfplay_mode(mz_handle* h, int mode, int opponent, int muzero_player);
 
 /* The opponent's weight set of MZ_OPP_NETWORK: a second set of the three
@@ -443,6 +452,23 @@ int mz_expert_table_get(mz_handle* h, void* scores, int32_t* built, int32_t* in_
 int mz_expert_judge(mz_handle* h, int env_kind, int G, const uint8_t* boards, const int32_t* players,
                     const int32_t* actions, int depth, int64_t* out4);
 
+/* The rules-MCTS opponent's budget (MZ_OPP_MCTS): sims 1..1024 simulations
+ * a move, rollouts 1..64 random playouts per simulation; 0 = the default
+ * (64 simulations, 16 rollouts).  A handle setting like mz_expert_depth:
+ * mz_selfplay_init and mz_snapshot_load keep it, snapshots do not carry it.  */
+int mz_mcts_opponent(mz_handle* h, int sims, int rollouts);
+
+/* The rules-MCTS opponent's root statistics of G >= 1 given positions, by
+ * the kernel evaluation play runs (the parity entry point): boards, players
+ * as mz_expert_eval; sims 1..1024, rollouts 1..64; row g searches with the
+ * Philox id game_offset + g and the step rng_step -> n_out, w_out [G][A]:
+ * the simulations through each root action and the sum of their outcomes for
+ * the player to move, in rollouts (|w| <= n * rollouts); n = -1, w = 0 for an
+ * illegal action.  Host buffers; synchronises; needs no mz_selfplay_init.
+ * Buffers, validation and refusals are mz_expert_eval's.                     */
+int mz_mcts_eval(mz_handle* h, int env_kind, int G, const uint8_t* boards, const int32_t* players, int sims,
+                 int rollouts, uint32_t rng_step, uint32_t game_offset, int32_t* n_out, int32_t* w_out);
+
 /* Evaluation tally since mz_selfplay_init: {games finished, MuZero wins,
  * opponent wins, draws}; the winner is read from the last move's reward
  * (TicTacToe with quirk Q14: the player to move after it; Connect4: the
@@ -462,8 +488,8 @@ int mz_eval_results(mz_handle* h, int64_t* out4);
  *     off, which frees nothing until the next mz_selfplay_init), the opponent
  *     MZ_OPP_* and muzero_player 1|2.  Refused as mz_selfplay_mode refuses:
  *     before mz_selfplay_init, an unknown opponent, muzero_player outside
- *     1..2, EXPERT / NETWORK on the frame-stack env, NETWORK before the
- *     opponent set is complete.
+ *     1..2, EXPERT / NETWORK / MCTS on the frame-stack env, NETWORK before
+ *     the opponent set is complete.
  *   mz_test_play: one evaluation, stream-ordered, no host synchronisation.
  *     Every test slot g starts a new game as mz_selfplay_init plus the first
  *     mz_selfplay_move would start slot g (boards: empty, player 1; the

@@ -43,6 +43,7 @@ const ACT_IDENTITY, ACT_RELU, ACT_TANH = Int32(0), Int32(1), Int32(2)
 const ENV_TICTACTOE, ENV_CONNECT4, ENV_ATARI = Cint(0), Cint(1), Cint(2)   # ENV_ATARI: the synthetic frame-stacked env of configs[4]
 const SP_TRAIN, SP_EVAL, OPP_SELF, OPP_RANDOM, OPP_EXPERT = Cint(0), Cint(1), Cint(0), Cint(1), Cint(2)
 const OPP_NETWORK = Cint(3)
+const OPP_MCTS = OPP_NETWORK + Cint(1)          # 4 = MZ_OPP_MCTS: the next opponent id
 const LEARN_REF_SEMANTICS, LEARN_CORRECTED = Cint(0), Cint(1)
 const TRAIN_LEARNER, TRAIN_ACTOR, TRAIN_QUEUED = Cint(0), Cint(1), Cint(2)
 const REAN_OFF, REAN_BY_VALUE, REAN_BY_SEARCH = Cint(0), Cint(1), Cint(2)
@@ -212,6 +213,21 @@ function expert_judge(e::Engine, env::Cint, boards::Matrix{UInt8}, players::Vect
                    (Ptr{Cvoid}, Cint, Cint, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Cint, Ptr{Int64}),
                    e.h, env, size(boards, 2), boards, players, actions, depth, out))
     out
+end
+# OPP_MCTS (DESIGN §22): vanilla MCTS over the true rules with random rollouts on the device; sims 1..1024,
+# rollouts 1..64 per simulation, 0 = the default (64, 16); a handle setting like expert_depth!
+mcts_opponent!(e::Engine, sims=0, rollouts=0) =
+    check(e, ccall((:mz_mcts_opponent, libmz), Cint, (Ptr{Cvoid}, Cint, Cint), e.h, sims, rollouts))
+"""mcts_eval(e, env, boards (W*H*3, G), players (G), sims, rollouts, A; rng_step, game_offset) — the MCTS
+opponent's root statistics (n, w), each (A, G): the simulations through every root action and the sum of their
+outcomes for the player to move, in rollouts; n = -1 for an illegal action."""
+function mcts_eval(e::Engine, env::Cint, boards::Matrix{UInt8}, players::Vector{Int32}, sims::Integer,
+                   rollouts::Integer, A::Integer; rng_step=0, game_offset=0)
+    n = Matrix{Int32}(undef, A, size(boards, 2)); w = Matrix{Int32}(undef, A, size(boards, 2))
+    check(e, ccall((:mz_mcts_eval, libmz), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Ptr{UInt8}, Ptr{Int32}, Cint, Cint, UInt32, UInt32, Ptr{Int32}, Ptr{Int32}),
+                   e.h, env, size(boards, 2), boards, players, sims, rollouts, rng_step, game_offset, n, w))
+    (n, w)
 end
 # OPP_NETWORK: the opponent's weight set (a handle setting; complete after all three nets, one
 # opponent_from! or one opponent_load!), then selfplay_mode!(e, SP_EVAL; opponent=OPP_NETWORK, mzp=...)

@@ -20,7 +20,7 @@ ENV_TICTACTOE, ENV_CONNECT4, ENV_ATARI = 0, 1, 2
 SP_TRAIN, SP_EVAL = 0, 1
 TRAIN_LEARNER, TRAIN_ACTOR, TRAIN_QUEUED = 0, 1, 2
 LEARN_REF_SEMANTICS, LEARN_CORRECTED = 0, 1
-OPP_SELF, OPP_RANDOM, OPP_EXPERT, OPP_NETWORK = 0, 1, 2, 3
+OPP_SELF, OPP_RANDOM, OPP_EXPERT, OPP_NETWORK, OPP_MCTS = 0, 1, 2, 3, 4
 REAN_OFF, REAN_BY_VALUE, REAN_BY_SEARCH = 0, 1, 2
 TEST_RECORDS = 1024                              # MZ_TEST_RECORDS: the test worker's record ring
 # one record of the test worker (mz_test_results): counts[8] then sums[3]
@@ -92,6 +92,9 @@ SIGNATURES = {
     "mz_expert_table": (ctypes.c_int, [_VP, ctypes.c_int]),
     "mz_expert_table_get": (ctypes.c_int, [_VP, _VP, _VP, _VP]),
     "mz_expert_judge": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, ctypes.c_int, _VP]),
+    "mz_mcts_opponent": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int]),
+    "mz_mcts_eval": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_uint32, ctypes.c_uint32, _VP, _VP]),
     "mz_opponent_weights_set": (ctypes.c_int, [_VP, ctypes.c_int, _VP, ctypes.c_size_t]),
     "mz_opponent_weights_get": (ctypes.c_int, [_VP, ctypes.c_int, _VP, ctypes.c_size_t]),
     "mz_opponent_from": (ctypes.c_int, [_VP, ctypes.c_int, _VP]),
@@ -497,6 +500,28 @@ class Engine:
         self._check(self.lib.mz_expert_judge(self.h, env_kind, b.shape[0], _p(b), _p(p), _p(a), depth, _p(out)),
                     "mz_expert_judge")
         return tuple(int(x) for x in out)
+
+    def mcts_opponent(self, sims=0, rollouts=0):
+        """Budget of the OPP_MCTS rules MCTS: sims 1..1024 simulations a move, rollouts 1..64 random
+        playouts per simulation; 0: the default (64, 16).  A handle setting like expert_depth."""
+        self._check(self.lib.mz_mcts_opponent(self.h, sims, rollouts), "mz_mcts_opponent")
+
+    def mcts_eval(self, env_kind, boards, players, sims, rollouts, rng_step=0, game_offset=0):
+        """The rules MCTS's root statistics of the positions boards (G, W*H*3) ([p1, p2, empty] planes) with
+        players (G,) to move, row g keyed (game_offset + g, rng_step): (n, w) int32 (G, A) each, the simulations
+        through every root action and the sum of their outcomes for the mover in rollouts; n = -1 for an illegal
+        action."""
+        b = np.ascontiguousarray(boards, np.uint8)
+        b = b.reshape(1, -1) if b.ndim == 1 else b
+        p = np.ascontiguousarray(players, np.int32).reshape(-1)
+        want = {ENV_TICTACTOE: 27, ENV_CONNECT4: 126}.get(env_kind)     # any other env: the library refuses it
+        if want is not None and (b.shape[1] != want or p.size != b.shape[0]):
+            raise MzError(f"mz_mcts_eval: boards must be (G, {want}) with G players")
+        n = np.zeros((b.shape[0], self.A), np.int32)
+        w = np.zeros((b.shape[0], self.A), np.int32)
+        self._check(self.lib.mz_mcts_eval(self.h, env_kind, b.shape[0], _p(b), _p(p), sims, rollouts, rng_step,
+                                          game_offset, _p(n), _p(w)), "mz_mcts_eval")
+        return n, w
 
     # ---- the opponent's weight set of OPP_NETWORK (DESIGN §19): a handle setting
     def opponent_set_weights(self, net, flat):

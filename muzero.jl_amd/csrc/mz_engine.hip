@@ -28,6 +28,7 @@ static const size_t kLdsMax = 160 * 1024;   // LDS per workgroup on gfx950
 #include "mz_backprop_params.h"
 #include "mz_selfplay_params.h"
 #include "mz_expert_rules.h"
+#include "mz_mcts_rules.h"
 #include "mz_ckpt_iface.h"
 #include "mz_snap_iface.h"
 
@@ -203,6 +204,8 @@ struct mz_handle {
     std::string tr_ckpt_path;               // mz_train_set_networks_path: periodic checkpoints
     int sp_eval = 0, sp_opp = MZ_OPP_SELF, sp_mzp = 1;    // mz_selfplay_mode
     int sp_expert_depth = 0;                              // mz_expert_depth (0: the env's default)
+    int sp_mcts_sims = 0, sp_mcts_rollouts = 0;           // mz_mcts_opponent (0: the defaults)
+    double* d_mcts_sqrt = nullptr;                        // [MZM_MAX_SIMS + 1] sqrt(k) (the first MZ_OPP_MCTS use)
     // the solved TicTacToe table (mz_expert_table): the handle's, built by the first on = 1
     bool xtable_on = false;
     int8_t* d_xtable = nullptr;                           // [MZX_TTT_CODES][MZX_TTT_ENTRY]
@@ -3266,6 +3269,35 @@ static bool expert_table_in_use(const mz_handle* h) {
     return h->xtable_on && h->d_xtable && h->sp_env == MZ_ENV_TICTACTOE && expert_depth_of(h, h->sp_env) == 9;
 }
 
+// ---- the rules-MCTS opponent
+// rows per workgroup: what fits the LDS with (S + 1)·A edge records a row, at most mz_expert_move's 4
+static int mcts_games_per_block(int sims, int A) {
+    const size_t row = (size_t)(sims + 1) * A * sizeof(MctsEdge);
+    return (int)std::min<size_t>(4, std::max<size_t>(1, kLdsMax / row));
+}
+
+// what the first use needs, outside any launch path: the sqrt table and the kernel's LDS ceiling
+static int mcts_prepare(mz_handle* h) {
+    if (h->d_mcts_sqrt) return 0;
+    static_assert((size_t)(MZM_MAX_SIMS + 1) * 9 * sizeof(MctsEdge) <= kLdsMax, "the largest tree fits one workgroup");
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_TRY(h, hipFuncSetAttribute((const void*)mz_mcts_move, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+    std::vector<double> sq(MZM_MAX_SIMS + 1);
+    for (size_t k = 0; k < sq.size(); ++k) sq[k] = std::sqrt((double)k);
+    double* d = nullptr;
+    MZ_TRY(h, dalloc(h, &d, sq.size()));
+    MZ_TRY(h, hipMemcpy(d, sq.data(), sq.size() * 8, hipMemcpyHostToDevice));
+    h->d_mcts_sqrt = d;
+    return 0;
+}
+
+static void mcts_launch(const SpParams& S, int sims, int rollouts, const double* sqrt_tab, int32_t* act, int32_t* n,
+                        int32_t* w, hipStream_t st) {
+    MctsArgs X{sims, rollouts, mcts_games_per_block(sims, S.A), sqrt_tab, act, n, w};
+    const size_t lds = (size_t)X.games * (sims + 1) * S.A * sizeof(MctsEdge);
+    hipLaunchKernelGGL(mz_mcts_move, dim3((S.G + X.games - 1) / X.games), dim3(64 * X.games), lds, st, S, X);
+}
+
 static void wset_swap(mz_handle* h, mz_handle::WSet& w);
 
 // MZ_OPP_NETWORK: the opponent search's outputs, part of the self-play state (a snapshot load
@@ -3302,6 +3334,12 @@ static int sp_move_body(mz_handle* h, const SpParams& S, float* cv2, float* rv2,
         } else {
             hipLaunchKernelGGL(mz_expert_move, waves, dim3(256), 0, st, S, X);
         }
+    }
+    if (S.eval && S.opponent == MZ_OPP_MCTS) {       // the rules MCTS's turns: its move replaces the search's action
+        if (!h->d_mcts_sqrt) return fail(h, "mcts opponent: not prepared (mz_selfplay_mode / mz_test_config first)");
+        mcts_launch(S, h->sp_mcts_sims ? h->sp_mcts_sims : MZM_DEF_SIMS,
+                    h->sp_mcts_rollouts ? h->sp_mcts_rollouts : MZM_DEF_ROLLOUTS, h->d_mcts_sqrt, h->d_act, nullptr,
+                    nullptr, st);
     }
     if (S.eval && S.opponent == MZ_OPP_NETWORK) {    // the same search with the opponent's nets; its turns take
         wset_swap(h, h->opp);                        // that search's whole result
@@ -3437,10 +3475,14 @@ int mz_selfplay_mode(mz_handle* h, int mode, int opponent, int muzero_player) {
     if (!h) return -2;
     if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
     if (mode != MZ_SP_TRAIN && mode != MZ_SP_EVAL) return fail(h, "mode must be MZ_SP_TRAIN or MZ_SP_EVAL");
-    if (opponent != MZ_OPP_SELF && opponent != MZ_OPP_RANDOM && opponent != MZ_OPP_EXPERT && opponent != MZ_OPP_NETWORK)
-        return fail(h, "opponent must be MZ_OPP_SELF, MZ_OPP_RANDOM, MZ_OPP_EXPERT or MZ_OPP_NETWORK");
+    if (opponent != MZ_OPP_SELF && opponent != MZ_OPP_RANDOM && opponent != MZ_OPP_EXPERT && opponent != MZ_OPP_NETWORK &&
+        opponent != MZ_OPP_MCTS)
+        return fail(h, "opponent must be MZ_OPP_SELF, MZ_OPP_RANDOM, MZ_OPP_EXPERT, MZ_OPP_NETWORK or MZ_OPP_MCTS");
     if (opponent == MZ_OPP_EXPERT && h->sp_env == MZ_ENV_ATARI) return fail(h, "expert: needs a two-player board env");
+    if (opponent == MZ_OPP_MCTS && h->sp_env == MZ_ENV_ATARI)
+        return fail(h, "mcts opponent: needs a two-player board env");
     if (muzero_player != 1 && muzero_player != 2) return fail(h, "muzero_player must be 1 or 2");
+    if (opponent == MZ_OPP_MCTS && mcts_prepare(h)) return -1;
     if (opponent == MZ_OPP_NETWORK) {
         if (h->sp_env == MZ_ENV_ATARI) return fail(h, "opponent network: needs a two-player board env");
         if (h->opp_have != 7u)
@@ -3457,6 +3499,54 @@ int mz_expert_depth(mz_handle* h, int depth) {
     if (!h) return -2;
     if (depth < 0 || depth > MZX_MAX_DEPTH) return fail(h, "expert: depth must be in 0..9 (0 = the env's default)");
     h->sp_expert_depth = depth;
+    return 0;
+}
+
+int mz_mcts_opponent(mz_handle* h, int sims, int rollouts) {
+    if (!h) return -2;
+    if (sims < 0 || sims > MZM_MAX_SIMS) return fail(h, "mcts opponent: sims must be in 0..1024 (0 = the default, 64)");
+    if (rollouts < 0 || rollouts > MZM_MAX_ROLLOUTS)
+        return fail(h, "mcts opponent: rollouts must be in 0..64 (0 = the default, 16)");
+    h->sp_mcts_sims = sims; h->sp_mcts_rollouts = rollouts;
+    return 0;
+}
+
+int mz_mcts_eval(mz_handle* h, int env_kind, int G, const uint8_t* boards, const int32_t* players, int sims,
+                 int rollouts, uint32_t rng_step, uint32_t game_offset, int32_t* n_out, int32_t* w_out) {
+    if (!h || !boards || !players || !n_out || !w_out) return -2;
+    if (int rc = sp_env_check(h, env_kind)) return rc;
+    if (env_kind == MZ_ENV_ATARI) return fail(h, "mcts opponent: needs a two-player board env");
+    if (G < 1) return fail(h, "mcts opponent: G must be >= 1");
+    if (sims < 1 || sims > MZM_MAX_SIMS) return fail(h, "mcts opponent: sims must be in 1..1024");
+    if (rollouts < 1 || rollouts > MZM_MAX_ROLLOUTS) return fail(h, "mcts opponent: rollouts must be in 1..64");
+    const int A = h->A, osz = 3 * mzx_cells(env_kind);
+    for (int g = 0; g < G; ++g) {
+        ExpertPos pos;
+        if (players[g] != 1 && players[g] != 2) return fail(h, "mcts opponent: player must be 1 or 2");
+        if (!mzx_pos_from_planes(env_kind, boards + (size_t)g * osz, players[g], &pos))
+            return fail(h, "mcts opponent: every cell must be set in exactly one plane");
+    }
+    if (mcts_prepare(h)) return -1;
+    uint8_t* d_b = nullptr; int32_t* d_p = nullptr; int32_t* d_n = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_b), (size_t)G * osz);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_p), (size_t)G * 4);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_n), (size_t)G * A * 8);   // n then w
+    if (e == hipSuccess) e = hipMemcpy(d_b, boards, (size_t)G * osz, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_p, players, (size_t)G * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        SpParams S;
+        std::memset(&S, 0, sizeof(S));
+        S.G = G; S.env = env_kind; S.W = h->conf.observation_shape[0]; S.H = h->conf.observation_shape[1];
+        S.osz = osz; S.A = A; S.board = d_b; S.player = d_p;
+        S.seed = h->seed; S.step = rng_step; S.game_offset = game_offset;
+        mcts_launch(S, sims, rollouts, h->d_mcts_sqrt, nullptr, d_n, d_n + (size_t)G * A, h->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = hipMemcpy(n_out, d_n, (size_t)G * A * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(w_out, d_n + (size_t)G * A, (size_t)G * A * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(d_b); (void)hipFree(d_p); (void)hipFree(d_n);
+    MZ_TRY(h, e);
     return 0;
 }
 
@@ -3617,10 +3707,14 @@ int mz_eval_results(mz_handle* h, int64_t* out4) {
 static int test_check(mz_handle* h, int games, int opponent, int muzero_player) {
     if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
     if (games < 0 || games > h->max_games) return fail(h, "mz_test_config: games must be in 0..max_games");
-    if (opponent != MZ_OPP_SELF && opponent != MZ_OPP_RANDOM && opponent != MZ_OPP_EXPERT && opponent != MZ_OPP_NETWORK)
-        return fail(h, "opponent must be MZ_OPP_SELF, MZ_OPP_RANDOM, MZ_OPP_EXPERT or MZ_OPP_NETWORK");
+    if (opponent != MZ_OPP_SELF && opponent != MZ_OPP_RANDOM && opponent != MZ_OPP_EXPERT && opponent != MZ_OPP_NETWORK &&
+        opponent != MZ_OPP_MCTS)
+        return fail(h, "opponent must be MZ_OPP_SELF, MZ_OPP_RANDOM, MZ_OPP_EXPERT, MZ_OPP_NETWORK or MZ_OPP_MCTS");
     if (opponent == MZ_OPP_EXPERT && h->sp_env == MZ_ENV_ATARI) return fail(h, "expert: needs a two-player board env");
+    if (opponent == MZ_OPP_MCTS && h->sp_env == MZ_ENV_ATARI)
+        return fail(h, "mcts opponent: needs a two-player board env");
     if (muzero_player != 1 && muzero_player != 2) return fail(h, "muzero_player must be 1 or 2");
+    if (opponent == MZ_OPP_MCTS && mcts_prepare(h)) return -1;
     if (opponent == MZ_OPP_NETWORK) {
         if (h->sp_env == MZ_ENV_ATARI) return fail(h, "opponent network: needs a two-player board env");
         if (h->opp_have != 7u)

@@ -163,6 +163,18 @@ struct ExpertArgs {
     long long* judge;
 };
 
+// mz_mcts_move (mz_mcts_opp.hip): the rules-MCTS opponent.  The rows are SpParams' (G, env,
+// A, osz, board, player, seed, step, game_offset; in self-play mode also muzero_player, frozen).
+struct MctsArgs {
+    int sims, rollouts;         // S 1..1024, R 1..64
+    int games;                  // rows (waves) per workgroup: the grid is ceil(G / games) blocks of 64 * games lanes,
+                                // each wave with (S + 1) * A edge records of dynamic LDS
+    const double* sqrt_tab;     // [S + 1] IEEE sqrt(k), built on the host
+    int32_t* act;               // self-play mode (n == null): [G] the search's actions; the rows whose mover is
+                                // not muzero_player get the opponent's
+    int32_t* n; int32_t* w;     // eval mode: [G][A] the root's statistics, n = -1 (w = 0) for an illegal action
+};
+
 // mz_sp_pick (mz_selfplay.hip): MZ_OPP_NETWORK's choice between the two searches of one move.
 // The rows are SpParams' (G, A, player, muzero_player).
 struct PickArgs {
@@ -201,6 +213,7 @@ extern "C" __global__ void mz_expert_move(SpParams S, ExpertArgs X);
 extern "C" __global__ void mz_expert_table_move(SpParams S, ExpertArgs X);
 extern "C" __global__ void mz_expert_table_rows(uint8_t* boards, int32_t* players, int c0, int n);
 extern "C" __global__ void mz_expert_table_pack(const int32_t* scores, int8_t* table, int c0, int n);
+extern "C" __global__ void mz_mcts_move(SpParams S, MctsArgs X);
 extern "C" __global__ void mz_sp_pick(SpParams S, PickArgs X);
 extern "C" __global__ void mz_test_begin(SpParams S, TestRec R);
 extern "C" __global__ void mz_test_tally(SpParams S, TestRec R);

@@ -3,6 +3,7 @@ host mirrors (replay_buffer.py, selfplay.py) draw from the same streams as the
 kernels, keyed (seed, purpose, id, step, index) — Julia's global RNG (quirk Q6)
 made reproducible."""
 _M = 0xFFFFFFFF
+MZ_RNG_ROLLOUT = 10                                   # include/mz_detmath.h: the rules-MCTS opponent's rollout moves
 
 
 def _philox(c0, c1, c2, c3, k0, k1):

@@ -15,6 +15,7 @@ import numpy as np
 
 from .config import stacked_features
 from .games.expert import DEFAULT_DEPTH, expert_pick, expert_scores, judge_move, solved_table, ttt_code
+from .games.mcts_rules import DEFAULT_ROLLOUTS, DEFAULT_SIMS, mcts_pick, mcts_root_stats
 from .rng import rng_below, rng_u32
 
 MZ_RNG_OPPONENT = 7                                               # include/mz_detmath.h
@@ -90,7 +91,7 @@ class BatchedSelfPlay:
     """G TicTacToe games played in lockstep on one engine (one GPU)."""
 
     def __init__(self, engine, env_cls, G, game_offset=0, step0=0, opponent="self", muzero_player=1,
-                 expert_depth=None, opponent_engine=None):
+                 expert_depth=None, opponent_engine=None, mcts_sims=None, mcts_rollouts=None):
         """opponent "self" (self_play!, SelfPlay.jl:384-419) or "random": the
         player != muzero_player plays a uniform legal action
         (select_opponent_action, :311-325) — competitive_play! (:421-435);
@@ -98,12 +99,15 @@ class BatchedSelfPlay:
         expert_depth plies (None: the env's default); "network": that player's
         moves are the same search on opponent_engine (another set of weights
         under the same config and rng_seed), and the history holds the mover's
-        own search statistics."""
-        assert opponent in ("self", "random", "expert", "network") and muzero_player in (1, 2)
+        own search statistics; "mcts": that player plays the rules MCTS of
+        games/mcts_rules.py with mcts_sims simulations of mcts_rollouts
+        rollouts (None: the defaults)."""
+        assert opponent in ("self", "random", "expert", "network", "mcts") and muzero_player in (1, 2)
         assert (opponent == "network") == (opponent_engine is not None), "network: needs opponent_engine (only)"
         self.opponent = opponent
         self.opponent_engine = opponent_engine
         self.expert_depth = expert_depth
+        self.mcts_sims, self.mcts_rollouts = mcts_sims or DEFAULT_SIMS, mcts_rollouts or DEFAULT_ROLLOUTS
         self.muzero_player = muzero_player
         self.eng = engine
         self.conf = engine.conf
@@ -114,6 +118,7 @@ class BatchedSelfPlay:
         self.frame_stack = getattr(env_cls, "FRAME_STACK", 0)
         assert not (opponent == "expert" and self.frame_stack), "expert: needs a two-player board env"
         assert not (opponent == "network" and self.frame_stack), "opponent network: needs a two-player board env"
+        assert not (opponent == "mcts" and self.frame_stack), "mcts opponent: needs a two-player board env"
         self.game_offset = game_offset
         self.step = step0
         self.plane = self.conf.observation_shape[0] * self.conf.observation_shape[1]
@@ -177,6 +182,14 @@ class BatchedSelfPlay:
                 if legal[g].any():
                     r = rng_u32(self.eng.rng_seed, MZ_RNG_OPPONENT, self.game_offset + int(g), self.step, 0)
                     act[g] = expert_pick(expert_scores(name, self.env.board[g], int(tp[g]), depth), r)
+        if self.opponent == "mcts":                                           # the same turns, its own ROLLOUT stream
+            name = "tictactoe" if self.env.board.shape[1] == 27 else "connect4"
+            for g in np.flatnonzero(tp != self.muzero_player):
+                if legal[g].any():
+                    gid = self.game_offset + int(g)
+                    n, _ = mcts_root_stats(name, self.env.board[g], int(tp[g]), self.mcts_sims, self.mcts_rollouts,
+                                           self.eng.rng_seed, gid, self.step)
+                    act[g] = mcts_pick(n, rng_u32(self.eng.rng_seed, MZ_RNG_OPPONENT, gid, self.step, 0))
         reward, done = self.env.step(act)                                     # :366-368
         for g, h in enumerate(self.histories):                                # :375-379
             h.child_visits.append(cv[g])
@@ -270,12 +283,14 @@ def env_name_of(env_cls):
 
 
 def evaluate(engine, env_cls, E, opponent="self", muzero_player=1, rng_step0=0, game_offset=0, temperature=0.0,
-             training_step=0, expert_depth=None, opponent_engine=None, audit=False):
+             training_step=0, expert_depth=None, opponent_engine=None, audit=False, mcts_sims=None,
+             mcts_rollouts=None):
     """One evaluation of the test worker on the host: E slots play one game each (move m keyed
     rng_step0 + m, game_offset); returns (the histories in slot order, their evaluation_record), and
     with audit=True their evaluation_audit at expert_depth as a third item."""
     sp = BatchedSelfPlay(engine, env_cls, E, game_offset=game_offset, step0=rng_step0, opponent=opponent,
-                         muzero_player=muzero_player, expert_depth=expert_depth, opponent_engine=opponent_engine)
+                         muzero_player=muzero_player, expert_depth=expert_depth, opponent_engine=opponent_engine,
+                         mcts_sims=mcts_sims, mcts_rollouts=mcts_rollouts)
     histories = sp.play_games(temperature)
     players = engine.conf.players                      # Config.players lists the player ids
     name = env_name_of(env_cls)
