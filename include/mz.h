@@ -586,6 +586,41 @@ int mz_replay_save_game(mz_handle* h, int32_t T, const uint8_t* obs, const int32
 int mz_replay_sample(mz_handle* h, int32_t B, uint32_t step, mz_batch* batch, int32_t* index_batch,
                      void* stream);
 
+/* Board-symmetry augmentation of get_batch.  The board envs have
+ * exact symmetries: TicTacToe the eight of the square (id s: transpose
+ * (i, j) -> (j, i) if s >= 4, then s & 3 quarter turns (a, b) -> (b, 2 - a);
+ * cell i + 3j, action a <-> cell a - 1), Connect4 the left-right mirror (id 1:
+ * cell (w, h) -> (w, H-1 - h), action a -> H + 1 - a).  id 0 is the identity.
+ *
+ *   mz_replay_set_symmetry: a handle setting like mz_expert_depth (default 0 =
+ *     off; mz_selfplay_init of the same env and mz_snapshot_load keep it,
+ *     snapshots do not carry it).  on = 1: sample b of every device get_batch
+ *     at learner step `step` (mz_replay_sample, mz_learner_grad_sampled_dev /
+ *     _train_dev / _train_multi_dev / _train_dp, mz_train_run / _learn) is
+ *     the stored position replayed under element
+ *       s_b = rng_below(rng_u32(seed, MZ_RNG_SYMMETRY, b, step, 0), n)
+ *     of the env's group: every board plane of the stacked observation is
+ *     permuted, the action planes, `actions` (absorbing-state actions
+ *     included, drawn as ever and then permuted) hold the permuted id,
+ *     target_policies moves with the actions; target_values / _rewards,
+ *     gradient_scale, the index batch, the PER weights and the priority
+ *     update are those of the plain sample.  Needs mz_selfplay_init; the
+ *     Atari-like env has no group and is refused; on must be 0 or 1.  A toggle
+ *     drops a batch drawn ahead.
+ *   mz_replay_symmetry_get: the group order n, the tables as the device holds
+ *     them (cell_perm [n][W*H]: cell c moves to cell_perm[s][c]; action_perm
+ *     [n][A], 0-based) and the setting; any output may be NULL.  n <= 8.
+ *   mz_batch_symmetry: the same transform of a device batch of in->batch_size
+ *     rows assembled by the caller, row b under element sym_dev[b] (device
+ *     int32 [B]; an id outside 0..n-1 copies the row) into the arrays of *out
+ *     (device, the caller's, writable, the same sizes; weights are copied
+ *     when both batches have them).  No array of *out may overlap one of *in.
+ *     Works with the setting on or off.                                      */
+int mz_replay_set_symmetry(mz_handle* h, int on);
+int mz_replay_symmetry_get(mz_handle* h, int32_t* n, int32_t* cell_perm, int32_t* action_perm, int32_t* on);
+int mz_batch_symmetry(mz_handle* h, const mz_batch* in_dev, const int32_t* sym_dev, mz_batch* out_dev,
+                      void* stream);
+
 /* One learner iteration on a batch drawn from this GPU's replay shard:
  * get_batch (as mz_replay_sample(step)) + learning! (Learning.jl:327-404).
  * The sampling runs inside the FC unroll kernel (its own launch otherwise).

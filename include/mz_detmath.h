@@ -217,7 +217,8 @@ enum {
     MZ_RNG_OPPONENT = 7,   /* random opponent, select_opponent_action :321    */
     MZ_RNG_ENV = 8,        /* synthetic Atari-like env: reset key, step      */
     MZ_RNG_FRAME = 9,      /* synthetic Atari-like env: frame bytes of a key */
-    MZ_RNG_ROLLOUT = 10    /* rules-MCTS opponent: rollout moves (mz_mcts_rules.h) */
+    MZ_RNG_ROLLOUT = 10,   /* rules-MCTS opponent: rollout moves (mz_mcts_rules.h) */
+    MZ_RNG_SYMMETRY = 11   /* replay sampler: the sample's board-symmetry id */
 };
 
 MZ_HD uint32_t mz_rng_u32(uint64_t seed, uint32_t purpose, uint32_t id, uint32_t step, uint32_t idx) {

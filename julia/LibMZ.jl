@@ -229,6 +229,27 @@ function mcts_eval(e::Engine, env::Cint, boards::Matrix{UInt8}, players::Vector{
                    e.h, env, size(boards, 2), boards, players, sims, rollouts, rng_step, game_offset, n, w))
     (n, w)
 end
+# Board-symmetry augmentation of the device get_batch (DESIGN §23): a handle setting like expert_depth!;
+# on: every sample of every device get_batch is drawn under a random element of the env's symmetry group
+# (TicTacToe 8, Connect4 2), keyed by the Philox SYMMETRY stream
+replay_set_symmetry!(e::Engine, on::Bool=true) =
+    check(e, ccall((:mz_replay_set_symmetry, libmz), Cint, (Ptr{Cvoid}, Cint), e.h, on ? 1 : 0))
+"""replay_symmetry_get(e, P, A) — (cell_perm (P, n), action_perm (A, n) 0-based, on): column s + 1 = where
+each cell / action goes under element s."""
+function replay_symmetry_get(e::Engine, P::Integer, A::Integer)
+    n = Ref{Int32}(0); on = Ref{Int32}(0)
+    check(e, ccall((:mz_replay_symmetry_get, libmz), Cint,
+                   (Ptr{Cvoid}, Ref{Int32}, Ptr{Int32}, Ptr{Int32}, Ref{Int32}), e.h, n, C_NULL, C_NULL, on))
+    cell = Matrix{Int32}(undef, P, n[]); act = Matrix{Int32}(undef, A, n[])
+    check(e, ccall((:mz_replay_symmetry_get, libmz), Cint,
+                   (Ptr{Cvoid}, Ref{Int32}, Ptr{Int32}, Ptr{Int32}, Ref{Int32}), e.h, n, cell, act, on))
+    (cell, act, on[] != 0)
+end
+# the same transform of a device batch the caller assembled: row b under element ids[b] (a device Int32
+# vector) into the distinct device arrays of `dst`
+batch_symmetry!(e::Engine, src::MzBatch, ids::Ptr{Int32}, dst::MzBatch) =
+    check(e, ccall((:mz_batch_symmetry, libmz), Cint, (Ptr{Cvoid}, Ref{MzBatch}, Ptr{Int32}, Ref{MzBatch}, Ptr{Cvoid}),
+                   e.h, src, ids, dst, C_NULL))
 # OPP_NETWORK: the opponent's weight set (a handle setting; complete after all three nets, one
 # opponent_from! or one opponent_load!), then selfplay_mode!(e, SP_EVAL; opponent=OPP_NETWORK, mzp=...)
 function opponent_set_weights!(e::Engine, net::Cint, chain)

@@ -115,6 +115,9 @@ SIGNATURES = {
     "mz_replay_counts": (ctypes.c_int, [_VP, _VP, _VP]),
     "mz_replay_save_game": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mz_replay_sample": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(MzBatch), _VP, _VP]),
+    "mz_replay_set_symmetry": (ctypes.c_int, [_VP, ctypes.c_int]),
+    "mz_replay_symmetry_get": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "mz_batch_symmetry": (ctypes.c_int, [_VP, ctypes.POINTER(MzBatch), _VP, ctypes.POINTER(MzBatch), _VP]),
     "mz_learner_grad_sampled_dev": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_uint32, _VP, _VP, _VP]),
     "mz_learner_train_dev": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_uint32, ctypes.c_double, _VP, _VP]),
     "mz_learner_train_multi_dev": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int32,
@@ -693,6 +696,56 @@ class Engine:
         self._check(self.lib.mz_replay_sample(self.h, B, step, ctypes.byref(b), _p(idx) if index else None, stream),
                     "mz_replay_sample")
         return b, idx
+
+    def replay_set_symmetry(self, on=True):
+        """Board-symmetry augmentation of every device get_batch: sample b at learner step
+        `step` is drawn under element rng_below(rng_u32(seed, MZ_RNG_SYMMETRY, b, step, 0), n) of the
+        env's group.  A handle setting like expert_depth; off by default."""
+        self._check(self.lib.mz_replay_set_symmetry(self.h, int(on)), "mz_replay_set_symmetry")
+
+    def replay_symmetry_get(self):
+        """(games.symmetry.SymmetryTables as the device holds them, the setting)."""
+        from .games.symmetry import SymmetryTables
+        n, on = ctypes.c_int32(), ctypes.c_int32()
+        self._check(self.lib.mz_replay_symmetry_get(self.h, ctypes.byref(n), None, None, ctypes.byref(on)),
+                    "mz_replay_symmetry_get")
+        P = self.conf.observation_shape[0] * self.conf.observation_shape[1]
+        cell, act = np.zeros((n.value, P), np.int32), np.zeros((n.value, self.A), np.int32)
+        self._check(self.lib.mz_replay_symmetry_get(self.h, None, _p(cell), _p(act), None), "mz_replay_symmetry_get")
+        return SymmetryTables(cell, act, self.conf.observation_shape[2]), bool(on.value)
+
+    def batch_symmetry(self, batch, ids, stream=None):
+        """mz_batch_symmetry: row b of `batch` under element ids[b] of the env's group.  batch: a device
+        MzBatch (replay_sample's) or a host dict in get_batch's layout; ids: (B,) int32.  Returns a
+        device MzBatch in torch tensors the result keeps alive (out._keep)."""
+        import torch
+        K1 = self.conf.num_unroll_steps + 1
+        keep = []
+
+        def dev(a, dtype):
+            t = torch.as_tensor(np.ascontiguousarray(a, dtype)).cuda()
+            keep.append(t)
+            return t.data_ptr()
+        if isinstance(batch, dict):
+            B = batch["observation"].shape[0]
+            src = MzBatch(B, *(dev(batch[k], np.float32) for k in (
+                "observation", "actions", "target_values", "target_rewards", "target_policies", "gradient_scale")),
+                dev(batch["weights"], np.float32) if "weights" in batch else None)
+        else:
+            src, B = batch, batch.batch_size
+        out = MzBatch(B)
+        for name, size in (("observation", B * self.obs_feat), ("actions", B * K1), ("target_values", B * K1),
+                           ("target_rewards", B * K1), ("target_policies", B * K1 * self.A), ("gradient_scale", B),
+                           ("weights", B if src.weights else 0)):
+            if size:
+                t = torch.empty(size, dtype=torch.float32, device="cuda")
+                keep.append(t)
+                setattr(out, name, t.data_ptr())
+        self._check(self.lib.mz_batch_symmetry(self.h, ctypes.byref(src), dev(ids, np.int32), ctypes.byref(out), stream),
+                    "mz_batch_symmetry")
+        self.sync()
+        out._keep = keep
+        return out
 
     def learner_grad_sampled_dev(self, B, step, grad_ptr, losses_ptr=None, stream=None):
         """replay_sample(B, step) + learner_grad_dev, the sampling fused into the unroll kernel."""

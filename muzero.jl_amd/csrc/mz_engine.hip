@@ -205,6 +205,12 @@ struct mz_handle {
     int sp_eval = 0, sp_opp = MZ_OPP_SELF, sp_mzp = 1;    // mz_selfplay_mode
     int sp_expert_depth = 0;                              // mz_expert_depth (0: the env's default)
     int sp_mcts_sims = 0, sp_mcts_rollouts = 0;           // mz_mcts_opponent (0: the defaults)
+    // board symmetry (mz_replay_set_symmetry): the setting is the handle's; the tables of
+    // the env's group are self-play state (built by mz_selfplay_init for a board env, behind the
+    // discount powers in d_sp_dpow's buffer): [sym_n][plane] cells, then [sym_n][A] actions
+    bool sym_on = false;
+    int sym_n = 0;
+    int32_t* d_sym = nullptr;
     double* d_mcts_sqrt = nullptr;                        // [MZM_MAX_SIMS + 1] sqrt(k) (the first MZ_OPP_MCTS use)
     // the solved TicTacToe table (mz_expert_table): the handle's, built by the first on = 1
     bool xtable_on = false;
@@ -3258,6 +3264,53 @@ static int sp_env_check(mz_handle* h, int env_kind) {
     return 0;
 }
 
+// The symmetry group of the handle's board env from its board shape: cell (i, j) is
+// i + W·j.  TicTacToe (a square board, one action per cell): the dihedral group, id s = transpose if
+// s >= 4, then s & 3 quarter turns (a, b) -> (b, W - 1 - a); the action table is the cell table.
+// Connect4 (H columns of W rows, one action per column): the mirror (w, h) -> (w, H - 1 - h).
+// cell [n][W·H], act [n][A]; returns n (0: the env has no group).
+static int sym_tables(const mz_handle* h, std::vector<int32_t>& cell, std::vector<int32_t>& act) {
+    const int W = h->conf.observation_shape[0], H = h->conf.observation_shape[1], P = W * H, A = h->A;
+    int n = 0;
+    if (h->sp_env == MZ_ENV_TICTACTOE && W == H && A == P) n = 8;
+    else if (h->sp_env == MZ_ENV_CONNECT4 && A == H) n = 2;
+    cell.assign((size_t)n * P, 0); act.assign((size_t)n * A, 0);
+    for (int s = 0; s < n; ++s)
+        for (int j = 0; j < H; ++j)
+            for (int i = 0; i < W; ++i) {
+                int a = i, b = j;
+                if (n == 8) {
+                    if (s >= 4) { a = j; b = i; }
+                    for (int q = 0; q < (s & 3); ++q) { const int t = a; a = b; b = W - 1 - t; }
+                    act[(size_t)s * A + i + W * j] = a + W * b;
+                } else {
+                    if (s == 1) b = H - 1 - j;
+                    act[(size_t)s * A + j] = b;
+                }
+                cell[(size_t)s * P + i + W * j] = a + W * b;
+            }
+    return n;
+}
+
+// The sampler's small constants in one device buffer (mz_selfplay_init: it lives and dies with the
+// shard's allocations): f32(discount^n) as Julia's Float32^Int (≈ f32(pow(f64))), n = 0..td+1, then
+// the env's symmetry tables (RpSampleParams names them by their offset from disc_pow)
+static int sp_constants(mz_handle* h) {
+    const mz_config& c = h->conf;
+    std::vector<float> dp(c.td_steps + 2);
+    for (int n = 0; n < (int)dp.size(); ++n) dp[n] = (float)std::pow((double)c.discount, (double)n);
+    std::vector<int32_t> cell, act;
+    h->sym_n = sym_tables(h, cell, act);
+    MZ_TRY(h, spalloc(h, &h->d_sp_dpow, dp.size() + cell.size() + act.size()));
+    MZ_TRY(h, hipMemcpy(h->d_sp_dpow, dp.data(), dp.size() * 4, hipMemcpyHostToDevice));
+    h->d_sym = nullptr;
+    if (!h->sym_n) return 0;
+    h->d_sym = reinterpret_cast<int32_t*>(h->d_sp_dpow + dp.size());
+    MZ_TRY(h, hipMemcpy(h->d_sym, cell.data(), cell.size() * 4, hipMemcpyHostToDevice));
+    MZ_TRY(h, hipMemcpy(h->d_sym + cell.size(), act.data(), act.size() * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
 // D of the expert opponent: the handle's mz_expert_depth, 0 = the env's default
 static int expert_depth_of(const mz_handle* h, int env_kind) {
     return h->sp_expert_depth ? h->sp_expert_depth : env_kind == MZ_ENV_TICTACTOE ? 9 : 4;
@@ -3385,6 +3438,7 @@ int mz_selfplay_init(mz_handle* h, int env_kind, int G, int replay_games) {
     h->sp_has_games = false;
     h->sp_reset_pending = false;
     h->tr_B = 0;                                // a new shard: mz_train_init again
+    if (env_kind != h->sp_env) h->sym_on = false;       // mz_replay_set_symmetry is kept for the same env only
     h->sp_env = env_kind; h->sp_G = G; h->sp_cap = replay_games;
     h->sp_T = c.max_moves + 1; h->sp_osz = W * H * C;
     h->sp_frames = 0;
@@ -3415,11 +3469,7 @@ int mz_selfplay_init(mz_handle* h, int env_kind, int G, int replay_games) {
     MZ_TRY(h, spalloc(h, &h->d_per_p, (size_t)h->sp_cap));
     MZ_TRY(h, spalloc(h, &h->d_per_total, 1));
     h->sp_eval = 0; h->sp_opp = MZ_OPP_SELF; h->sp_mzp = 1;
-    // f32(discount^n) as Julia's Float32^Int (≈ f32(pow(f64))), n = 0..td+1
-    std::vector<float> dp(c.td_steps + 2);
-    for (int n = 0; n < (int)dp.size(); ++n) dp[n] = (float)std::pow((double)c.discount, (double)n);
-    MZ_TRY(h, spalloc(h, &h->d_sp_dpow, dp.size()));
-    MZ_TRY(h, hipMemcpy(h->d_sp_dpow, dp.data(), dp.size() * 4, hipMemcpyHostToDevice));
+    if (sp_constants(h)) return -1;                     // discount powers, the env's symmetry tables
     if (log_rebase(h, 0)) return -1;                    // the run log: a new shard (its ring and setting stay)
     if (env_kind == MZ_ENV_ATARI) {
         // every slot: new game, its key and first frame drawn on the device at
@@ -3968,6 +4018,11 @@ static int rs_params(mz_handle* h, int32_t B, uint32_t step, hipStream_t st, RpS
                            h->sp_cap, h->d_per_cum, h->d_per_p, h->d_per_total);
         MZ_TRY(h, hipGetLastError());
     }
+    if (h->sym_on && h->d_sym) {                  // mz_replay_set_symmetry: every path draws under the env's group
+        Q.sym_n = h->sym_n;                       // (the tables follow disc_pow in its buffer)
+        Q.sym_cell = (int)(h->d_sym - reinterpret_cast<int32_t*>(h->d_sp_dpow));
+        Q.sym_act = Q.sym_cell + h->sym_n * h->plane;
+    }
     *Qo = Q;
     batch->batch_size = B;
     batch->observation = h->d_rs_obs; batch->actions = h->d_rs_act; batch->target_values = h->d_rs_tv;
@@ -4008,6 +4063,74 @@ int mz_replay_sample(mz_handle* h, int32_t B, uint32_t step, mz_batch* batch, in
         MZ_TRY(h, hipMemcpyAsync(index_batch, h->d_rs_index, (size_t)B * 8, hipMemcpyDeviceToHost, st));
         MZ_TRY(h, hipStreamSynchronize(st));
     }
+    return 0;
+}
+
+// the board env's group for the symmetry calls: refusals that name the env
+static int sym_env_check(mz_handle* h) {
+    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
+    if (h->sp_env == MZ_ENV_ATARI) return fail(h, "symmetry: the Atari-like env has no symmetry group");
+    if (!h->sym_n || !h->d_sym) return fail(h, "symmetry: the env has no symmetry group");
+    return 0;
+}
+
+int mz_replay_set_symmetry(mz_handle* h, int on) {
+    if (!h) return -2;
+    if (int rc = sym_env_check(h)) return rc;
+    if (on != 0 && on != 1) return fail(h, "symmetry: on must be 0 (off) or 1 (the env's full group)");
+    if (h->sym_on != (on != 0)) ++h->pf_epoch;      // a batch drawn ahead was drawn under the other setting
+    h->sym_on = on != 0;
+    return 0;
+}
+
+int mz_replay_symmetry_get(mz_handle* h, int32_t* n, int32_t* cell_perm, int32_t* action_perm, int32_t* on) {
+    if (!h) return -2;
+    if (int rc = sym_env_check(h)) return rc;
+    MZ_TRY(h, hipSetDevice(h->device));
+    const size_t nc = (size_t)h->sym_n * h->plane, na = (size_t)h->sym_n * h->A;
+    if (n) *n = h->sym_n;
+    if (cell_perm) MZ_TRY(h, hipMemcpy(cell_perm, h->d_sym, nc * 4, hipMemcpyDeviceToHost));
+    if (action_perm) MZ_TRY(h, hipMemcpy(action_perm, h->d_sym + nc, na * 4, hipMemcpyDeviceToHost));
+    if (on) *on = h->sym_on ? 1 : 0;
+    return 0;
+}
+
+int mz_batch_symmetry(mz_handle* h, const mz_batch* in_dev, const int32_t* sym_dev, mz_batch* out_dev, void* stream) {
+    if (!h || !in_dev || !out_dev || !sym_dev) return -2;
+    if (int rc = sym_env_check(h)) return rc;
+    const int B = in_dev->batch_size, K1 = h->conf.num_unroll_steps + 1, A = h->A;
+    if (B < 1) return fail(h, "batch_size must be >= 1");
+    if (out_dev->batch_size != B) return fail(h, "symmetry: the two batches must have the same batch_size");
+    const size_t sz[7] = {(size_t)B * h->obs_feat, (size_t)B * K1, (size_t)B * K1, (size_t)B * K1, (size_t)B * K1 * A,
+                          (size_t)B, (size_t)B};
+    const float* in[7] = {in_dev->observation, in_dev->actions, in_dev->target_values, in_dev->target_rewards,
+                          in_dev->target_policies, in_dev->gradient_scale, in_dev->weights};
+    const float* out[7] = {out_dev->observation, out_dev->actions, out_dev->target_values, out_dev->target_rewards,
+                           out_dev->target_policies, out_dev->gradient_scale, out_dev->weights};
+    for (int i = 0; i < 6; ++i)
+        if (!in[i] || !out[i]) return fail(h, "symmetry: a batch array is NULL");
+    for (int i = 0; i < 7; ++i)                     // the transform scatters: an output may overlap no input
+        for (int j = 0; j < 7; ++j)
+            if (in[i] && out[j] && in[i] < out[j] + sz[j] && out[j] < in[i] + sz[i])
+                return fail(h, "symmetry: the output arrays must not overlap the input arrays (in == out is refused)");
+    for (int i = 0; i < 7; ++i)
+        for (int j = i + 1; j < 7; ++j)
+            if (out[i] && out[j] && out[i] < out[j] + sz[j] && out[j] < out[i] + sz[i])
+                return fail(h, "symmetry: the output arrays overlap each other");
+    MZ_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream_of(h, stream);
+    RpSymParams Y;
+    std::memset(&Y, 0, sizeof(Y));
+    Y.B = B; Y.K = K1 - 1; Y.A = A; Y.P = h->plane; Y.C = h->sp_osz / h->plane; Y.F = h->obs_feat;
+    Y.n = h->sym_n; Y.cell = h->d_sym; Y.act = h->d_sym + (size_t)h->sym_n * h->plane;
+    Y.sym = sym_dev;
+    Y.obs = in[0]; Y.actions = in[1]; Y.tv = in[2]; Y.tr = in[3]; Y.tpol = in[4]; Y.gscale = in[5];
+    Y.o_obs = const_cast<float*>(out[0]); Y.o_actions = const_cast<float*>(out[1]);
+    Y.o_tv = const_cast<float*>(out[2]); Y.o_tr = const_cast<float*>(out[3]);
+    Y.o_tpol = const_cast<float*>(out[4]); Y.o_gscale = const_cast<float*>(out[5]);
+    if (in[6] && out[6]) { Y.weights = in[6]; Y.o_weights = const_cast<float*>(out[6]); }
+    hipLaunchKernelGGL(mz_rp_symmetry, dim3((B + 3) / 4), dim3(256), 0, st, Y);
+    MZ_TRY(h, hipGetLastError());
     return 0;
 }
 
@@ -4534,7 +4657,8 @@ static int learner_multi(mz_handle* h, int32_t B, uint32_t step0, int32_t L, con
         M.counter = h->d_ml_cnt + (size_t)ir * MZ_MULTI_CNT_STRIDE;
         M.out = losses_dev ? losses_dev + 8 * i0 : h->d_ml_out + 8 * ir;
         M.out_last = i0 + n == L ? out_last : nullptr;
-        M.sample = 1;                               // (each step's get_batch in its unroll workgroups)
+        M.sample = Q.sym_n == 0;                    // (each step's get_batch in its unroll workgroups; with the
+                                                    // board symmetry on, in the chain launch: DESIGN §23)
         M.q = Qk;
         const int grid = M.xcd ? 8 * ((n + 7) / 8) * nU : n * nU;
         void* args[] = {&U, &M};
@@ -4548,7 +4672,7 @@ static int learner_multi(mz_handle* h, int32_t B, uint32_t step0, int32_t L, con
         if (e1) MZ_TRY(h, hipEventRecord(e1, st));
         return 0;
     };
-    if (multi_drive(h, step0, L, Ls, eta, theta_dev, st, cap, Q, S, false, body)) return -1;
+    if (multi_drive(h, step0, L, Ls, eta, theta_dev, st, cap, Q, S, Q.sym_n != 0, body)) return -1;
     h->last_lvariant = ti == 0 ? "mz_learn_chain+mz_learn_multi1"
                      : ti == 1 ? "mz_learn_chain+mz_learn_multi2" : "mz_learn_chain+mz_learn_multi4";
     return 0;

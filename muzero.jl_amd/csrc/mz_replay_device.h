@@ -115,9 +115,117 @@ __device__ __forceinline__ void per_game_max(SpHist& ring, int slot, int len, in
     ring.gprio[slot] = m;
 }
 
+// ---- board symmetry: the row transform shared by the sampler's symmetric path
+// (rp_sample_row<true>) and mz_rp_symmetry.  cp / ap: the rows of the cell / action tables of the
+// row's group element.
+
+// the permuted id of the raw (1-based) action id a, as the batch arrays hold it; a value that is no
+// action id (the 0 of the all-zero block before the first move) stays and indexes nothing
+__device__ __forceinline__ float sym_action(const int32_t* ap, int A, float a) {
+    const int i = (int)a - 1;
+    return (unsigned)i < (unsigned)A ? (float)(ap[i] + 1) : a;
+}
+
+// C board planes of P cells each, `in` (the shard's bytes, or a batch's floats) -> out: cell c of
+// every plane goes to cell cp[c]
+template <class T>
+__device__ __forceinline__ void sym_put_board(float* out, const T* in, int C, int P, const int32_t* cp, int lane) {
+    for (int c = lane; c < P; c += 64) {
+        const int t = cp[c];
+        for (int pl = 0; pl < C; ++pl) out[pl * P + t] = (float)in[pl * P + c];
+    }
+}
+
+// entry e = k·A + a (value v) of a target_policies row
+__device__ __forceinline__ void sym_put_pol(float* out, int e, float v, int A, const int32_t* ap) {
+    const int k = e / A;
+    out[k * A + ap[e - k * A]] = v;
+}
+
+// stacked_obs (Q15) under a group element: each observation's board planes through sym_put_board,
+// each constant action plane holding the permuted id, the all-zero block as it is
+__device__ __forceinline__ void stacked_obs_sym(float* out, const uint8_t* cur, const uint8_t* obs, const int32_t* act,
+                                                int index, int osz, int P, int stacked, int lane, int A,
+                                                const int32_t* cp, const int32_t* ap) {
+    const int C = osz / P;
+    sym_put_board(out, cur, C, P, cp, lane);
+    int o = osz;
+    for (int past = index - 1; past >= index - stacked; --past) {
+        if (past >= 1) {
+            const float av = sym_action(ap, A, (float)act[past - 1]);
+            for (int k = lane; k < P; k += 64) out[o + k] = av;
+            sym_put_board(out + o + P, obs + (size_t)(past - 1) * osz, C, P, cp, lane);
+        } else {
+            for (int k = lane; k < P + osz; k += 64) out[o + k] = 0.0f;
+        }
+        o += P + osz;
+    }
+}
+
+// row b of the batch arrays of Q from position pos (1-based) of the game `num` in ring slot `slot`
+// (make_target :25-50, the stacked observation, gradient_scale :212).  SYM: under the group element
+// whose table rows are cp / ap, every permuted array written straight to its place.
+template <bool SYM>
+__device__ __forceinline__ void rp_sample_row(const RpSampleParams& Q, int b, int lane, long long num, int slot, int T,
+                                              int pos, const int32_t* cp, const int32_t* ap) {
+    const size_t base = (size_t)slot * Q.T;
+    const int K1 = Q.K + 1, A = Q.A;
+    // the bootstrap values: reanalysed_predicted_root_values unless `nothing` (ReplayBuffer.jl:8);
+    // the policy targets: the reanalyse search's child_visits if the game has them
+    const int rean = Q.ring.rean[slot];
+    const float* rv = (rean & MZ_REAN_VALUES ? Q.ring.rrv : Q.ring.rv) + base;
+    const int32_t* tp = Q.ring.tp + base;
+    const float* rew = Q.ring.rew + base;
+    const int32_t* act = Q.ring.act + base;
+    const float* cv = (rean & MZ_REAN_POLICIES ? Q.ring.rcv : Q.ring.cv) + base * A;
+    const float uni = 1.0f / (float)A;
+    for (int k = lane; k < K1; k += 64) {                          // make_target (:25-50)
+        const int ci = pos + k;
+        float v = 0.0f, r = 0.0f, a;
+        if (ci < T) {
+            v = rp_target_value(Q.td, Q.disc_pow, rv, tp, rew, T, ci);
+            r = rew[ci - 1];
+            a = (float)act[ci - 1];
+        } else if (ci == T) {
+            r = rew[ci - 1];
+            a = (float)act[ci - 1];
+        } else {                                                   // absorbing states
+            a = (float)(mz_rng_below(mz_rng_u32(Q.seed, MZ_RNG_ABSORB, (uint32_t)b, Q.step, (uint32_t)k), (uint32_t)A) + 1);
+        }
+        Q.tv[(size_t)b * K1 + k] = v;
+        Q.tr[(size_t)b * K1 + k] = r;
+        if constexpr (SYM) a = sym_action(ap, A, a);
+        Q.actions[(size_t)b * K1 + k] = a;
+    }
+    for (int e = lane; e < K1 * A; e += 64) {
+        const int k = e / A, a = e - k * A, ci = pos + k;
+        const float p = ci < T ? cv[(size_t)(ci - 1) * A + a] : uni;
+        if constexpr (SYM) sym_put_pol(Q.tpol + (size_t)b * K1 * A, e, p, A, ap);
+        else Q.tpol[(size_t)b * K1 * A + e] = p;
+    }
+    if constexpr (SYM)                                             // (the Atari-like env has no group)
+        stacked_obs_sym(Q.obs + (size_t)b * Q.F, Q.ring.obs + (base + pos - 1) * Q.osz, Q.ring.obs + base * Q.osz, act,
+                        pos, Q.osz, Q.P, Q.stacked, lane, A, cp, ap);
+    else if (Q.frames)
+        frame_stack_obs(Q.obs + (size_t)b * Q.F, Q.ring.obs + base * Q.osz, pos, Q.osz, Q.frames, lane);
+    else
+        stacked_obs(Q.obs + (size_t)b * Q.F, Q.ring.obs + (base + pos - 1) * Q.osz, Q.ring.obs + base * Q.osz, act,
+                    pos, Q.osz, Q.P, Q.stacked, lane);
+    if (lane == 0) {
+        const int gs = T + 1 - pos;                                // :212 min(K, len(action_history)+1-pos)
+        // write-through (agent scope): the fold of a learner launch that draws its
+        // batch in place reads every sample's gradient_scale from another workgroup
+        __hip_atomic_store(Q.gscale + b, (float)(Q.K < gs ? Q.K : gs), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        Q.index[2 * b] = (int)num;
+        Q.index[2 * b + 1] = pos;
+    }
+}
+
 // get_batch's sample b (sample_n_games :102, sample_position :80,
 // make_target :25-50, gradient_scale :212) on one wave (lane 0..63): writes
 // row b of the batch arrays of Q.
+// SYM_OK = false compiles the symmetric path out (a kernel whose host never hands it a group).
+template <bool SYM_OK = true>
 __device__ __forceinline__ void rp_sample_one(const RpSampleParams& Q, int b, int lane) {
     const long long played = Q.counters[0];
     const int n = (int)(played < Q.cap ? played : Q.cap);
@@ -151,48 +259,13 @@ __device__ __forceinline__ void rp_sample_one(const RpSampleParams& Q, int b, in
     } else {
         pos = (int)mz_rng_below(rp, (uint32_t)T) + 1;              // :80
     }
-    const int K1 = Q.K + 1, A = Q.A;
-    // the bootstrap values: reanalysed_predicted_root_values unless `nothing` (ReplayBuffer.jl:8);
-    // the policy targets: the reanalyse search's child_visits if the game has them
-    const int rean = Q.ring.rean[slot];
-    const float* rv = (rean & MZ_REAN_VALUES ? Q.ring.rrv : Q.ring.rv) + base;
-    const int32_t* tp = Q.ring.tp + base;
-    const float* rew = Q.ring.rew + base;
-    const int32_t* act = Q.ring.act + base;
-    const float* cv = (rean & MZ_REAN_POLICIES ? Q.ring.rcv : Q.ring.cv) + base * A;
-    const float uni = 1.0f / (float)A;
-    for (int k = lane; k < K1; k += 64) {                          // make_target (:25-50)
-        const int ci = pos + k;
-        float v = 0.0f, r = 0.0f, a;
-        if (ci < T) {
-            v = rp_target_value(Q.td, Q.disc_pow, rv, tp, rew, T, ci);
-            r = rew[ci - 1];
-            a = (float)act[ci - 1];
-        } else if (ci == T) {
-            r = rew[ci - 1];
-            a = (float)act[ci - 1];
-        } else {                                                   // absorbing states
-            a = (float)(mz_rng_below(mz_rng_u32(Q.seed, MZ_RNG_ABSORB, (uint32_t)b, Q.step, (uint32_t)k), (uint32_t)A) + 1);
-        }
-        Q.tv[(size_t)b * K1 + k] = v;
-        Q.tr[(size_t)b * K1 + k] = r;
-        Q.actions[(size_t)b * K1 + k] = a;
-    }
-    for (int e = lane; e < K1 * A; e += 64) {
-        const int k = e / A, a = e - k * A, ci = pos + k;
-        Q.tpol[(size_t)b * K1 * A + e] = ci < T ? cv[(size_t)(ci - 1) * A + a] : uni;
-    }
-    if (Q.frames)
-        frame_stack_obs(Q.obs + (size_t)b * Q.F, Q.ring.obs + base * Q.osz, pos, Q.osz, Q.frames, lane);
-    else
-        stacked_obs(Q.obs + (size_t)b * Q.F, Q.ring.obs + (base + pos - 1) * Q.osz, Q.ring.obs + base * Q.osz, act,
-                    pos, Q.osz, Q.P, Q.stacked, lane);
-    if (lane == 0) {
-        const int gs = T + 1 - pos;                                // :212 min(K, len(action_history)+1-pos)
-        // write-through (agent scope): the fold of a learner launch that draws its
-        // batch in place reads every sample's gradient_scale from another workgroup
-        __hip_atomic_store(Q.gscale + b, (float)(Q.K < gs ? Q.K : gs), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        Q.index[2 * b] = (int)num;
-        Q.index[2 * b + 1] = pos;
+    if (SYM_OK && Q.sym_n) {                                       // wave-uniform: the sample's group element
+        // (s and the two table rows stay in vector registers: the learner kernels that inline this are
+        // short of scalar registers, not of vector ones, while they sample)
+        const int s = (int)mz_rng_below(mz_rng_u32(Q.seed, MZ_RNG_SYMMETRY, (uint32_t)b, Q.step, 0), (uint32_t)Q.sym_n);
+        const int32_t* tab = reinterpret_cast<const int32_t*>(Q.disc_pow);
+        rp_sample_row<true>(Q, b, lane, num, slot, T, pos, tab + Q.sym_cell + s * Q.P, tab + Q.sym_act + s * Q.A);
+    } else {
+        rp_sample_row<false>(Q, b, lane, num, slot, T, pos, nullptr, nullptr);
     }
 }

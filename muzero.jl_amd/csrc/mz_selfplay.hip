@@ -596,3 +596,44 @@ extern "C" __global__ __launch_bounds__(256) void mz_rp_sample(RpSampleParams Q)
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b < Q.B) rp_sample_one(Q, b, lane);
 }
+
+// mz_batch_symmetry: row b of a batch under element sym[b] of the env's group, one wave per row, through
+// the sampler's row transform (sym_put_board / sym_action / sym_put_pol of mz_replay_device.h); an id
+// outside 0..n-1 copies the row and reads no table
+extern "C" __global__ __launch_bounds__(256) void mz_rp_symmetry(RpSymParams Y) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b >= Y.B) return;
+    const int K1 = Y.K + 1, A = Y.A;
+    const int s = __builtin_amdgcn_readfirstlane(Y.sym[b]);
+    const bool on = (unsigned)s < (unsigned)Y.n;
+    const int32_t* cp = Y.cell + (size_t)(on ? s : 0) * Y.P;
+    const int32_t* ap = Y.act + (size_t)(on ? s : 0) * A;
+    const float* x = Y.obs + (size_t)b * Y.F;
+    float* y = Y.o_obs + (size_t)b * Y.F;
+    const float* pi = Y.tpol + (size_t)b * K1 * A;
+    float* po = Y.o_tpol + (size_t)b * K1 * A;
+    if (on) {
+        // the row is a run of planes of P cells (Q15): C board planes per observation, one action plane
+        // (the raw id in every cell, 0 in the all-zero block before the first move) before each past one
+        const int blk = (Y.C + 1) * Y.P;
+        sym_put_board(y, x, Y.C, Y.P, cp, lane);
+        for (int o = Y.C * Y.P; o + blk <= Y.F; o += blk) {
+            for (int c = lane; c < Y.P; c += 64) y[o + cp[c]] = sym_action(ap, A, x[o + c]);
+            sym_put_board(y + o + Y.P, x + o + Y.P, Y.C, Y.P, cp, lane);
+        }
+        for (int e = lane; e < K1 * A; e += 64) sym_put_pol(po, e, pi[e], A, ap);
+    } else {
+        for (int f = lane; f < Y.F; f += 64) y[f] = x[f];
+        for (int e = lane; e < K1 * A; e += 64) po[e] = pi[e];
+    }
+    for (int k = lane; k < K1; k += 64) {
+        const float a = Y.actions[(size_t)b * K1 + k];
+        Y.o_actions[(size_t)b * K1 + k] = on ? sym_action(ap, A, a) : a;
+        Y.o_tv[(size_t)b * K1 + k] = Y.tv[(size_t)b * K1 + k];
+        Y.o_tr[(size_t)b * K1 + k] = Y.tr[(size_t)b * K1 + k];
+    }
+    if (lane == 0) {
+        Y.o_gscale[b] = Y.gscale[b];
+        if (Y.weights) Y.o_weights[b] = Y.weights[b];
+    }
+}

@@ -187,7 +187,13 @@ struct PickArgs {
 struct RpSampleParams {
     int B, K, A, osz, P, F, stacked, T, td, cap;
     int frames;                 // the env's frame stack (0: stacked observations, Q15)
+    // board symmetry (mz_replay_set_symmetry): sample b is written under element
+    // s_b = rng_below(SYMMETRY stream (b, step), sym_n) of the env's group.  The three fields sit in
+    // the struct's alignment holes, so every kernel argument keeps its offset (§23's resource table);
+    // the tables follow disc_pow in its buffer, named by their offsets from it in 4-byte words
+    int sym_n;                  // the group's order, 0: off
     uint64_t seed; uint32_t step;
+    int sym_cell;               // [sym_n][P] at (int32_t*)disc_pow + sym_cell: cell c moves to [s][c]
     SpHist ring;
     const long long* counters;
     const float* disc_pow;      // [td + 2]: f32(discount^n) as Julia's Float32^Int
@@ -197,10 +203,24 @@ struct RpSampleParams {
     // from the cumulative game probabilities of mz_rp_per_prep; raw IS weights
     // 1/(total_samples·p_game·p_pos), normalised by mz_rp_per_norm (:211-215)
     int per;
+    int sym_act;                // [sym_n][A] at (int32_t*)disc_pow + sym_act: 0-based action a becomes [s][a]
     const float* per_cum;       // [n held] cumulative f32 game probabilities (oldest first)
     const float* per_p;         // [n held] game probabilities
     const long long* per_total; // total_samples of the held games
     float* weights;             // [B]
+};
+static_assert(sizeof(RpSampleParams) == 272, "RpSampleParams: the symmetry fields belong in the alignment holes");
+
+// mz_rp_symmetry (mz_selfplay.hip): mz_batch_symmetry's transform of a device batch, row b under
+// element sym[b] of the group (an id outside 0..n-1: the row is copied)
+struct RpSymParams {
+    int B, K, A, P, C, F;       // C = board planes of one observation (osz / P)
+    int n;
+    const int32_t* cell; const int32_t* act;                    // the tables: [n][P], [n][A]
+    const int32_t* sym;         // [B]
+    const float* obs; const float* actions; const float* tv; const float* tr; const float* tpol;
+    const float* gscale; const float* weights;                  // weights: null without PER
+    float* o_obs; float* o_actions; float* o_tv; float* o_tr; float* o_tpol; float* o_gscale; float* o_weights;
 };
 
 // ---- kernel prototypes (mz_selfplay.hip, mz_reanalyse.hip)
@@ -221,6 +241,7 @@ extern "C" __global__ void mz_log_games(SpParams S, LogAcc* acc);
 extern "C" __global__ void mz_log_steps(LogArgs L);
 extern "C" __global__ void mz_log_commit(LogArgs L);
 extern "C" __global__ void mz_rp_sample(RpSampleParams Q);
+extern "C" __global__ void mz_rp_symmetry(RpSymParams Y);
 extern "C" __global__ void mz_rp_per_init(SpHist ring, int slot, int len, int Tmax, int td, const float* disc_pow,
                                           int alpha);
 extern "C" __global__ void mz_rp_per_prep(SpHist ring, const long long* counters, int cap, float* cum, float* prob,

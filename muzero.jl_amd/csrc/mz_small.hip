@@ -1288,7 +1288,9 @@ __device__ __forceinline__ void learn_multi_body(const SmallUnrollParams& P, con
             Q.step += (uint32_t)i;
             Q.obs += i * M.s_obs; Q.actions += i * M.s_k1; Q.tv += i * M.s_k1; Q.tr += i * M.s_k1;
             Q.tpol += i * M.s_tp; Q.gscale += (size_t)i * P.B; Q.index += (size_t)i * 2 * P.B;
-            rp_sample_one(Q, b, tid & 63);
+            // (a symmetric job's batches are the chain launch's, M.sample = 0: with the symmetric path
+            // in, these kernels, at the limit of their scalar registers, reserved scratch)
+            rp_sample_one<false>(Q, b, tid & 63);
         }
         __threadfence_block();
         __syncthreads();

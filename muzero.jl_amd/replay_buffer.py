@@ -15,7 +15,7 @@ import numpy as np
 from .selfplay import GameHistory, frame_stack_obs, get_stacked_observations
 
 MZ_RNG_GAME, MZ_RNG_POS, MZ_RNG_ABSORB = 4, 5, 6
-from .rng import _M, _philox, rng_below, rng_u32  # noqa: F401  (re-exported)
+from .rng import MZ_RNG_SYMMETRY, _M, _philox, rng_below, rng_u32  # noqa: F401  (re-exported)
 
 
 def disc_pow(g, n):
@@ -43,8 +43,10 @@ def compute_target_value(conf, h, index):
     return value
 
 
-def make_target(conf, h, state_index, seed=0, sample=0, step=0):
-    """ReplayBuffer.jl:25-50 -> (values (K+1,), rewards (K+1,), policies (K+1, A), actions (K+1,))."""
+def make_target(conf, h, state_index, seed=0, sample=0, step=0, action_perm=None):
+    """ReplayBuffer.jl:25-50 -> (values (K+1,), rewards (K+1,), policies (K+1, A), actions (K+1,)).
+    action_perm (symmetric get_batch, h already permuted): the 0-based action table row that the
+    absorbing-state actions, drawn as ever, go through."""
     K, A = conf.num_unroll_steps, len(conf.action_space)
     T = len(h.root_values)
     tv = np.zeros(K + 1, np.float32)
@@ -68,7 +70,62 @@ def make_target(conf, h, state_index, seed=0, sample=0, step=0):
         else:                                              # absorbing states
             tp[k] = uni
             ta[k] = rng_below(rng_u32(seed, MZ_RNG_ABSORB, sample, step, k), A) + 1
+            if action_perm is not None:
+                ta[k] = action_perm[int(ta[k]) - 1] + 1
     return tv, tr, tp, ta
+
+
+def symmetry_ids(seed, step, B, n):
+    """s_b of samples 0..B-1 of learner step `step` in a group of order n: keyed like the
+    sample's GAME and POS draws."""
+    return np.array([rng_below(rng_u32(seed, MZ_RNG_SYMMETRY, b, step, 0), n) for b in range(B)], np.int32)
+
+
+def apply_symmetry(batch, ids, tables):
+    """The batch dict (get_batch's layout) with row b under element ids[b] of `tables`
+    (games/symmetry.SymmetryTables); a new dict.  Board planes are permuted by the cell table, the
+    constant action planes and `actions` hold the permuted id, target_policies moves with the action
+    table; everything else is copied.  An id outside 0..n-1 leaves its row as it is."""
+    cp, ap, C = tables.cell, tables.action, tables.planes
+    P = cp.shape[1]
+    out = {k: np.array(v, copy=True) for k, v in batch.items()}
+    obs, acts, tpol = batch["observation"], batch["actions"], batch["target_policies"]
+    for b, s in enumerate(np.asarray(ids).reshape(-1)):
+        if not 0 <= s < tables.n:
+            continue
+        x = obs[b].reshape(-1, P)
+        y = np.empty_like(x)
+        y[:, cp[s]] = x
+        for pl in range(C, x.shape[0], C + 1):                 # the stacked action planes (Q15)
+            if x[pl, 0] != 0:                                  # (the zero block before move 1 stays)
+                y[pl, :] = ap[s][int(x[pl, 0]) - 1] + 1
+        out["observation"][b] = y.reshape(-1)
+        out["actions"][b] = ap[s][acts[b].astype(np.int64) - 1] + 1
+        out["target_policies"][b][:, ap[s]] = tpol[b]
+    return out
+
+
+def _permuted_history(h, cp, ap, C):
+    """GameHistory h played in another orientation: boards through the cell table row cp, actions and
+    child visits through the action table row ap."""
+    def board(o):
+        x = np.asarray(o, np.float32).reshape(C, -1)
+        y = np.empty_like(x)
+        y[:, cp] = x
+        return y.reshape(-1)
+
+    def visits(cv):
+        out = np.empty(len(ap), np.float32)
+        out[ap] = np.asarray(cv, np.float32)
+        return out
+    return GameHistory(observation_history=[board(o) for o in h.observation_history],
+                       action_history=[int(ap[a - 1]) + 1 for a in h.action_history],
+                       reward_history=h.reward_history, to_play_history=h.to_play_history,
+                       child_visits=[visits(c) for c in h.child_visits], root_values=h.root_values,
+                       reanalysed_predicted_root_values=h.reanalysed_predicted_root_values,
+                       priorities=h.priorities, game_priority=h.game_priority,
+                       reanalysed_child_visits=None if h.reanalysed_child_visits is None else
+                       [visits(c) for c in h.reanalysed_child_visits])
 
 
 _TTT_LINES = np.array([[0, 3, 6], [1, 4, 7], [2, 5, 8], [0, 1, 2], [3, 4, 5], [6, 7, 8], [0, 4, 8], [6, 4, 2]])
@@ -191,10 +248,19 @@ class ReplayBuffer:
             removed = self.buffer.pop(del_id)
             self.total_samples -= len(removed.root_values)
 
-    def get_batch(self, step):
+    def get_batch(self, step, symmetry=False):
         """:188-217 with uniform sampling keyed by the learner step.
-        Returns (index_batch, batch dict in the engine's layout)."""
+        Returns (index_batch, batch dict in the engine's layout).  symmetry (mz_replay_set_symmetry,
+        DESIGN §23): sample b is the stored game replayed under element s_b of the env's symmetry
+        group, s_b from the SYMMETRY stream; the ids drawn are kept in self.last_symmetry_ids."""
         c = self.conf
+        sym = None
+        if symmetry:
+            if self.frame_stack:
+                raise ValueError("symmetry: the Atari-like env has no symmetry group")
+            from .games import symmetry as _symmetry
+            sym = _symmetry.for_conf(c)
+            self.last_symmetry_ids = symmetry_ids(self.seed, step, c.batch_size, sym.n)
         B, K, A = c.batch_size, c.num_unroll_steps, len(c.action_space)
         ids = list(self.buffer.keys())
         n = len(ids)
@@ -229,7 +295,12 @@ class ReplayBuffer:
                 wts[b] = np.float32(1.0) / np.float32(np.float32(np.float32(total) * gprob) * pprob)   # :213
             else:
                 pos = rng_below(rp, T) + 1                                         # sample_position :80
-            tv[b], tr[b], tp[b], acts[b] = make_target(c, h, pos, self.seed, b, step)
+            ap = None
+            if sym is not None:
+                s = self.last_symmetry_ids[b]
+                ap = sym.action[s]
+                h = _permuted_history(h, sym.cell[s], ap, sym.planes)
+            tv[b], tr[b], tp[b], acts[b] = make_target(c, h, pos, self.seed, b, step, ap)
             if self.frame_stack:
                 obs[b] = frame_stack_obs(h.observation_history, pos, self.frame_stack)
             else:

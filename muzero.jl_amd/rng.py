@@ -4,6 +4,7 @@ kernels, keyed (seed, purpose, id, step, index) — Julia's global RNG (quirk Q6
 made reproducible."""
 _M = 0xFFFFFFFF
 MZ_RNG_ROLLOUT = 10                                   # include/mz_detmath.h: the rules-MCTS opponent's rollout moves
+MZ_RNG_SYMMETRY = 11                                  # the replay sampler's board-symmetry id (DESIGN §23)
 
 
 def _philox(c0, c1, c2, c3, k0, k1):
