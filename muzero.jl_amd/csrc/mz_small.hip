@@ -125,6 +125,11 @@ struct SmFusedIn {
 __device__ __forceinline__ int sm_lds_addr(const void* p) {
     return (int)(unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
 }
+// (and back: a pointer to the LDS byte `addr`, for code that takes pointers)
+template <typename V>
+__device__ __forceinline__ V* sm_lds_ptr(int addr) {
+    return (V*)(__attribute__((address_space(3))) V*)(unsigned)addr;
+}
 // A host record (mz_small_params.h: .x, .z relative to the activation buffer)
 // as the kernel holds it in LDS, act_b = sm_lds_addr(act)
 __device__ __forceinline__ int4 sm_rec_abs(int rx, int ry, int rz, float bias, int act_b) {
@@ -636,6 +641,24 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
     const int rtp_w = __builtin_amdgcn_readfirstlane(sg_root_tp[wv < T ? wv : 0]);
     // wave w < T, lane n: the statics of node n of its game (the ballot select's; the root's to start with)
     NodeStat nst = node_stat_root(lane);
+    // wave w < T: the LDS addresses its select reads game w through (tree, path, cache entries,
+    // header), formed once.  Pinned: left to itself the compiler forms the tree's again in every
+    // simulation, from a load of P.tree_game_bytes in front of the ballot pass's LDS reads
+    const int wsel = wv < T ? wv : 0;
+    int sel_tree_b = sm_lds_addr(lds_tree + (size_t)wsel * P.tree_game_bytes);
+    int sel_path_b = sm_lds_addr(sg_path + wsel * PS);
+    int sel_cache_b = sm_lds_addr(c_cache + wsel * NN);
+    int sel_hdr_b = sm_lds_addr(c_hdr + wsel);
+    asm volatile("" : "+s"(sel_tree_b), "+s"(sel_path_b), "+s"(sel_cache_b), "+s"(sel_hdr_b));
+    // wave 0, lane 16 g + a: its read-out (even a: the value, odd: the reward) as the activation's
+    // kind and the LDS address of game g's raw output, selected here between values.  Selected
+    // where they are used, between two fields of P, the compiler selects the fields' addresses
+    // and loads both from the argument segment per lane, in front of every simulation's read-outs
+    int ro_va = P.v_act, ro_ra = P.r_act, ro_vo = P.v_out, ro_ro = P.r_out;
+    asm volatile("" : "+s"(ro_va), "+s"(ro_ra), "+s"(ro_vo), "+s"(ro_ro));
+    int ro_kind = (a & 1) != 0 ? ro_ra : ro_va;
+    int ro_addr = act_b + (((a & 1) != 0 ? ro_ro : ro_vo) + g) * 4;
+    asm volatile("" : "+v"(ro_kind), "+v"(ro_addr));
     // Per simulation, three workgroup barriers besides the 8 network stages:
     // wave 0 owns the trees' updates (T <= 4 games x 16 lanes); wave w < T
     // selects for game w, behind the recompute's barrier (the last simulation's
@@ -647,19 +670,20 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
             // tied or stale entry, lanes 0..15 of the same wave walk on from there.
             const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
             if (tile0 + w < P.G) {
-                const TreeView tw = tree_view(lds_tree + (size_t)w * P.tree_game_bytes, E, NN);
-                int* pw = sg_path + w * PS;
-                const uint2* cw = c_cache + w * NN;
+                const TreeView tw = tree_view(sm_lds_ptr<char>(sel_tree_b), E, NN);
+                int* pw = sm_lds_ptr<int>(sel_path_b);
+                const uint2* cw = sm_lds_ptr<const uint2>(sel_cache_b);
+                int4* hw = sm_lds_ptr<int4>(sel_hdr_b);
                 uint32_t verw;                 // the game's tag (the ballot pass reads it with the entries)
                 SelectOut so{0, 0, 1, 0};
                 int D, e0;
                 uint32_t npc0;
                 bool found = false;
                 if (sel_ballot) {
-                    found = select_path_ballot(tw, cw, nst, &c_hdr[w].z, verw, pw, s + 1, s + 1, rtp_w,
+                    found = select_path_ballot(tw, cw, nst, &hw->z, verw, pw, s + 1, s + 1, rtp_w,
                                                lane, A, P.players, so, D, e0, npc0);
                 } else {                       // the tree outgrows one wave: the walk, from the skip-ahead level
-                    verw = (uint32_t)c_hdr[w].z;
+                    verw = (uint32_t)hw->z;
                     D = c_skip[w];
                     e0 = D > 0 ? pw[2 * D + 1] : 0;
                     npc0 = D > 0 ? tw.nc(pw[2 * D]) : 0u;
@@ -715,8 +739,7 @@ __device__ __forceinline__ void small_body(const SmallParams& P) {
                 // one activation per lane (even lanes the value, odd the reward, both
                 // f64 tanh chains run at once), then each quad's lanes 0 / 1 to all
                 // four by DPP quad_perm [0,0,0,0] / [1,1,1,1]
-                const bool odd = (a & 1) != 0;
-                const float ro = mz_post_act(odd ? P.r_act : P.v_act, act[(odd ? P.r_out : P.v_out) + g]);
+                const float ro = mz_post_act(ro_kind, SM_LDS(const float, ro_addr));
                 const float val = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
                     0, __builtin_bit_cast(int, ro), 0x00, 0xF, 0xF, false));
                 const float rew = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
