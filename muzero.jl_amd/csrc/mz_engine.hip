@@ -21,8 +21,6 @@
 #include "mz_internal.h"
 #include "mz_tree_device.h"   // tree_bytes (tree layout shared with the kernels)
 
-static const size_t kLdsMax = 160 * 1024;   // LDS per workgroup on gfx950
-
 #include "mz_small_params.h"
 #include "mz_resnet_params.h"
 #include "mz_backprop_params.h"
@@ -31,385 +29,13 @@ static const size_t kLdsMax = 160 * 1024;   // LDS per workgroup on gfx950
 #include "mz_mcts_rules.h"
 #include "mz_ckpt_iface.h"
 #include "mz_snap_iface.h"
+#include "mz_handle.h"
 
-namespace {
-
-enum { CH_TRUNK = 0, CH_HEAD1 = 1, CH_HEAD2 = 2 };
-
-struct LayerSpec {
-    int net, chain, in, out, act;
-    size_t flux_w, flux_b;     // offsets in the global flat parameter vector
-    int bn = 0;                // make_dense with use_batch_norm: BatchNorm β at flux_be, γ at flux_be + out
-    size_t flux_be = 0;
-    int nq, n_ob;
-    int packed_w, packed_b;    // offsets in the packed images
-};
-
-struct PlanBuild {
-    std::vector<std::vector<std::pair<int, int>>> stages;
-    std::vector<LayerDesc> layers;
-    void ensure(int n) { if ((int)stages.size() < n) stages.resize(n); }
-    std::vector<int> image() const {
-        std::vector<int> v;
-        int nt = 0;
-        for (auto& s : stages) nt += (int)s.size();
-        v.push_back((int)stages.size()); v.push_back((int)layers.size()); v.push_back(nt);
-        int acc = 0;
-        for (auto& s : stages) { v.push_back(acc); acc += (int)s.size(); }
-        v.push_back(acc);
-        for (auto& s : stages) for (auto& t : s) { v.push_back(t.first); v.push_back(t.second); }
-        for (auto& L : layers) {
-            const int* p = reinterpret_cast<const int*>(&L);
-            for (size_t i = 0; i < sizeof(LayerDesc) / sizeof(int); ++i) v.push_back(p[i]);
-        }
-        return v;
-    }
-};
+using namespace mz;
 
 thread_local std::string g_create_error;
 
-}  // namespace
-
-struct mz_handle {
-    mz_config conf;
-    mz_ffhp hp;
-    int kind = 0;                           // 0 FeedForwardHP, 1 ResNetHP
-    mz_resnet_hp rhp{};
-    // ResNet config of the networks after the downsampler (= conf without
-    // one): observation_shape = the representation tail's input board and
-    // channels, stacked_observations = 0 (ResNetHP.downsample, configs[4])
-    mz_config rconf{};
-    int ds = 0;                             // downsampler (mz_downsample.hip) on
-    DsPlan dsplan{};
-    DsPlan* d_dsplan = nullptr;
-    size_t ds_lds = 0, ds_n = 0;            // its LDS bytes, its parameter count (first in the repr net)
-    int rin_feat = 0;                       // representation tail input features (obs_feat without downsampler)
-    float* d_dsout = nullptr;               // [max_games][rin_feat] search roots' downsampled observations
-    float* d_dsb = nullptr; int dsb_cap = 0;   // [cap][rin_feat] scratch: learner batches, net_forward
-    // ResNet networks (mz_resnet.hip): host plans, device copies, tile width
-    std::vector<RPlan> rplan;               // [3]
-    RPlan* d_rplan = nullptr;               // [3]
-    int rn_ng = 0;
-    // the learner unroll's chain (mz_runroll_chain1 / _chain_r): the same nets on narrow (one-sample) tiles
-    std::vector<RPlan> rplan_l;
-    RPlan* d_rplan_l = nullptr;
-    size_t rn_lds_l = 0;
-    size_t rn_lds[3] = {0, 0, 0};
-    float bn_s = 1.0f;
-    int* d_rpath = nullptr; int* d_rgst = nullptr;          // ResNet search: [G][2(S+2)], [G][RG_INTS]
-    uint2* d_rcache = nullptr; int* d_rnN = nullptr;        // [G][S+1]: the LDS tree step's cached select
-    int* d_rhk = nullptr; float* d_rov = nullptr; float* d_rologit = nullptr; float* d_ror = nullptr;
-    float* d_rhs = nullptr;                 // [bcap][K][H] learner unroll scratch (h between the nets)
-    float* d_rts = nullptr;                 // [bcap][K][H] dynamics trunk outputs (the reward heads' input)
-    int rn_dyn_split = 0;                   // first reward-head layer of the dynamics plan
-    bool rd_chain = false;                  // the chain runs as mz_runroll_chain_r (rd_chain_ok)
-    bool rp_pred = false;                   // one-item predictions run as mz_runroll_pred_r (rp_pred_ok)
-    unsigned long long* d_prog = nullptr;   // [bcap] mz_runroll_fused_r progress words
-    float* d_rtrunk = nullptr;              // [max_games][H] dynamics trunk outputs (mz_rsearch_nets)
-    unsigned long long* d_tprog = nullptr;  // [tiles] their publish words
-    unsigned long long tprog_epoch = 0;     // mz_rsearch_nets launches
-    float* d_chx = nullptr;                 // [MZ_MULTI_MAX][hx_n] mz_learn_chain helpers' θ (ChainParams::hx)
-    unsigned long long* d_chcnt = nullptr;  // [3·MZ_L2_BLOCKS] their slots' arrival counters
-    unsigned long long prog_epoch = 0;      // launches of mz_runroll_fused_r (prog_base = epoch · 64)
-    std::vector<int> rtab;                  // offset tables of the narrow (chain) plans
-    int* d_rtab = nullptr;
-    int device = 0, max_games = 0;
-    uint64_t seed = 0;
-    std::string err;
-    hipStream_t stream = nullptr;
-    hipStream_t sync_stream = nullptr; bool sync_narrow = false;   // mz_set_sync_stream
-
-    std::vector<LayerSpec> layers;
-    std::vector<int> chains[3][3];          // [net][chain] -> layer indices
-    size_t nparams[3] = {0, 0, 0}, flat_off[3] = {0, 0, 0}, nflat = 0;
-    size_t packed_w_n = 0, packed_b_n = 0;
-    int obs_feat = 0, plane = 0, H = 0, A = 0, S = 0;
-    ActLayout lay{};
-    int chain_buf[3][3][2];                 // LDS ping-pong buffers per chain
-
-    float* d_flat = nullptr; float* d_Wp = nullptr; float* d_Bp = nullptr;
-    int* d_srcW = nullptr; int* d_srcB = nullptr;
-    int* d_plan[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // repr, pred, dyn, root, sim
-    int* d_plan_sim_res = nullptr;          // register-resident image of the sim plan (or null)
-    double* d_pbc = nullptr; double* d_sqrt = nullptr; float* d_aval = nullptr;
-    double* d_pbterm = nullptr;             // pbc(Np) * (sqrt(Np) / (Nc + 1)), triangle
-    size_t rtree_lds = 0;                                    // LDS of the LDS-cached ResNet tree step (0 = HBM kernel)
-    float* d_bw = nullptr;                                   // host batch PER weights (mz_learner_step)
-    float* d_rs_w = nullptr; float* d_per_cum = nullptr; float* d_per_p = nullptr;   // PER sampling
-    long long* d_per_total = nullptr;
-    int rs_last_B = 0;                                       // batch size of the last get_batch
-    void* dp_comm = nullptr; int dp_world = 0, dp_rank = 0;  // mz_dp_init: RCCL communicator
-    float* d_dp_cnt = nullptr;              // mz_train_run at world > 1: the finished-game count exchange
-    char* d_tree = nullptr; size_t tree_game_bytes = 0; bool lds_tree = false; int dump_tree = 0;
-    int time_nets = 0;                      // mz_debug_enable flag 2: events around each ResNet nets launch
-    int time_unroll = 0;                    // flag 4: events around each ResNet learner unroll launch
-                                            // (and each mz_learn_multi* launch)
-    std::vector<hipEvent_t> tev; size_t tev_used = 0;
-    bool use_res = false;                   // register-resident sim-plan kernel
-    // small-batch kernel (mz_small.hip): schedule images + LDS layout
-    bool small_ok = false;
-    int n_cu = 256;
-    int sm_n_sim = 0, sm_n_root = 0;
-    float* d_sm_w = nullptr;                // [n_sim + n_root][2][256][16] weight image (sim then root)
-    float* d_sm_bias = nullptr;             // [n_sim + n_root][2][64]
-    // FC engines: a second image set (tile16 W/B, small W/bias) that the one-launch
-    // learner step (mz_learn_small*) writes while its unroll reads the current set;
-    // the host swaps the sets after the launch
-    float* d_Wp2 = nullptr; float* d_Bp2 = nullptr; float* d_sm_w2 = nullptr; float* d_sm_bias2 = nullptr;
-    int* d_sm_srcw = nullptr; int* d_sm_srcb = nullptr;
-    size_t sm_w_n = 0, sm_b_n = 0;
-    int* d_sm_rec[3] = {nullptr, nullptr, nullptr};   // per T in {1,2,4}
-    int sm_lay[3][8];                       // per T: act_total, x_rep, x_pred, x_dyn, h_out, v_out, p_out, r_out
-    size_t sm_lds[3] = {0, 0, 0};
-    std::vector<uint32_t> sm_nzm;           // nonzero-chunk masks of the register images (SM_NZM_N)
-    bool sm_bn = false;                     // BatchNorm FC layers: the bias image carries γ, β sections
-    float* d_zero16 = nullptr;              // 64 zero bytes (sm_load's skipped chunks)
-    unsigned* d_fault = nullptr;            // device fault word (MZ_FAULT_*), checked at host synchronisation
-    int dbg_skip = -1;                      // debug: the hand-off producer that skips its publish
-    unsigned long long poll_ticks = MZ_POLL_TICKS;
-    int force_kernel = 0;                   // 0 auto, 1 tile16, 2 small
-    // inverse image maps, one code per flat parameter: >= 0 position in the
-    // weight image, <= -2 position -code-2 in the bias image, -1 none.  ADAM
-    // scatters every update into the images through them (no repack).
-    std::vector<int> inv_tile, inv_small;
-    int* d_inv_tile = nullptr; int* d_inv_small = nullptr;
-    std::string last_variant = "none";
-    std::string last_lvariant = "none";     // the learner unroll's kernels (mz_learner_variant)
-    int force_T = 0;                        // MZ_SMALL_T=1|2|4 (tests)
-    float* d_hid = nullptr;
-    float* d_obs = nullptr; uint8_t* d_legal = nullptr; int32_t* d_tp = nullptr;
-    float* d_cv = nullptr; float* d_rv = nullptr; int32_t* d_act = nullptr;
-    // learner
-    float* d_m = nullptr; float* d_v = nullptr; float* d_grad = nullptr;
-    double bp1 = 0.9, bp2 = 0.999;
-    int bcap = 0;
-    float *d_bobs = nullptr, *d_bact = nullptr, *d_btv = nullptr, *d_btr = nullptr, *d_btp = nullptr,
-          *d_bgs = nullptr, *d_pv = nullptr, *d_pp = nullptr, *d_pr = nullptr, *d_loss = nullptr;
-    double* d_sq = nullptr;                 // [3][MZ_L2_BLOCKS] partial Σθ²
-    size_t* d_netoff = nullptr;             // [3] flat offset, [3] count per net
-    unsigned* d_counter = nullptr;          // last-block counter of mz_learner_grad_kernel
-    float* d_lterm = nullptr;               // [2][B(K+1)] loss terms
-    unsigned long long* d_stamps = nullptr;
-    int32_t* d_sel_stats = nullptr;         // mz_debug_enable flag 1: [max_games][2] select counters of the small kernel
-    // device self-play + replay shard (mz_selfplay.hip); own allocation list (re-init frees it)
-    int sp_env = -1, sp_G = 0, sp_T = 0, sp_osz = 0, sp_cap = 0;
-    uint8_t* d_sp_board = nullptr; int32_t* d_sp_player = nullptr; uint8_t* d_sp_over = nullptr;
-    uint32_t* d_sp_ekey = nullptr; int sp_frames = 0;
-    SpHist sp_hist{}, sp_ring{};
-    long long* d_sp_counters = nullptr;
-    int32_t* d_sp_done = nullptr; int32_t* d_sp_rpos = nullptr;
-    float* d_sp_temp = nullptr;             // [G] per-slot temperatures (temperature_threshold)
-    float* d_sp_tgame = nullptr;            // [G] each game's own temperature (mz_train_run)
-    bool sp_latch = false;                  // mz_selfplay_move latches temperatures per game
-    std::string tr_ckpt_path;               // mz_train_set_networks_path: periodic checkpoints
-    int sp_eval = 0, sp_opp = MZ_OPP_SELF, sp_mzp = 1;    // mz_selfplay_mode
-    int sp_expert_depth = 0;                              // mz_expert_depth (0: the env's default)
-    int sp_mcts_sims = 0, sp_mcts_rollouts = 0;           // mz_mcts_opponent (0: the defaults)
-    // board symmetry (mz_replay_set_symmetry): the setting is the handle's; the tables of
-    // the env's group are self-play state (built by mz_selfplay_init for a board env, behind the
-    // discount powers in d_sp_dpow's buffer): [sym_n][plane] cells, then [sym_n][A] actions
-    bool sym_on = false;
-    int sym_n = 0;
-    int32_t* d_sym = nullptr;
-    double* d_mcts_sqrt = nullptr;                        // [MZM_MAX_SIMS + 1] sqrt(k) (the first MZ_OPP_MCTS use)
-    // the solved TicTacToe table (mz_expert_table): the handle's, built by the first on = 1
-    bool xtable_on = false;
-    int8_t* d_xtable = nullptr;                           // [MZX_TTT_CODES][MZX_TTT_ENTRY]
-    long long* d_eval = nullptr;                          // [4] evaluation tally
-    // the test worker (mz_test_*).  Handle settings: mz_test_config, mz_train_set_test.
-    // The record ring stays with the handle (allocated by the first mz_test_play); the test slots
-    // are self-play state (in sp_allocs, allocated by the first mz_test_play after a re-init).
-    int test_E = 0, test_opp = MZ_OPP_SELF, test_mzp = 1;
-    int64_t test_interval = 0; uint32_t test_goff = 0; float test_temp = 0.0f;
-    long long* d_test_counts = nullptr;                   // [MZ_TEST_RECORDS][8]
-    double* d_test_sums = nullptr;                        // [MZ_TEST_RECORDS][3]
-    int64_t test_total = 0;                               // evaluations since create / mz_test_clear
-    // judging (mz_test_audit): the audit ring beside the records, allocated by the first
-    // evaluation that judges; which rows hold an audit is host bookkeeping
-    bool test_audit = false;
-    long long* d_test_audit = nullptr;                    // [MZ_TEST_RECORDS][4]
-    std::vector<uint8_t> test_audited = std::vector<uint8_t>(MZ_TEST_RECORDS, 0);
-    struct TestSlots {
-        int E = 0;                                        // 0: not allocated
-        bool played = false;                              // an evaluation's games are in `hist`
-        uint8_t* board = nullptr; int32_t* player = nullptr; uint8_t* over = nullptr; uint32_t* ekey = nullptr;
-        SpHist hist{};
-        int32_t* done = nullptr; int32_t* frozen = nullptr; float* temp = nullptr;
-        float* cv2 = nullptr; float* rv2 = nullptr; int32_t* act2 = nullptr;   // MZ_OPP_NETWORK's second outputs
-    } ts;
-    // the run log (mz_train_set_log).  The interval is a handle setting; the accumulators,
-    // the chunk's loss rows and the record ring are the handle's, allocated by the first interval > 0
-    int64_t log_interval = 0;
-    LogAcc* d_log_acc = nullptr;
-    float* d_log_rows = nullptr;                          // [MZ_MULTI_LMAX][8]
-    long long* d_log_counts = nullptr;                    // [MZ_LOG_RECORDS][16]
-    double* d_log_sums = nullptr;                         // [MZ_LOG_RECORDS][16]
-    int64_t log_total = 0;                                // records since create / mz_train_log_clear
-    float* d_sp_dpow = nullptr;
-    float *d_rs_obs = nullptr, *d_rs_act = nullptr, *d_rs_tv = nullptr, *d_rs_tr = nullptr, *d_rs_tp = nullptr,
-          *d_rs_gs = nullptr;
-    int32_t* d_rs_index = nullptr;
-    int rs_cap = 0;
-    bool sp_has_games = false;              // the FIFO never empties once a game is in
-    bool sp_reset_pending = false;          // Atari-like env: the initial games start at the first move
-    // get_batch one step ahead (the one-launch FC learner, PER off): the launch
-    // for step t also samples step t+1's batch into the other batch set and
-    // stamps that set's header {epoch, games played, step, B}; the next launch
-    // uses a set only if its header still matches (the same shard state — a
-    // stored game bumps `played` — step and B), else it samples in place.
-    // Anything else that fills set 0 or re-creates the shard bumps the epoch.
-    float *d_rs2_obs = nullptr, *d_rs2_act = nullptr, *d_rs2_tv = nullptr, *d_rs2_tr = nullptr,
-          *d_rs2_tp = nullptr, *d_rs2_gs = nullptr;
-    int32_t* d_rs2_index = nullptr;
-    int pf_cap = 0, pf_cur = 0;
-    long long* d_pf_hdr = nullptr;          // [2][4]
-    long long pf_epoch = 1;
-    // mz_replay_reanalyse on ResNet engines: staging of one chunk (in sp_allocs)
-    float *d_rn_x = nullptr, *d_rn_h = nullptr, *d_rn_v = nullptr, *d_rn_p = nullptr;
-    int rn_cap = 0;
-    size_t rean_lds = 0;                    // mz_reanalyse_fc's dynamic-LDS attribute
-    // mz_replay_reanalyse_search: the io of one batched search of max_games rows (in sp_allocs,
-    // allocated with sp_ring.rcv at the first call that has work)
-    float *d_rq_obs = nullptr, *d_rq_cv = nullptr, *d_rq_rv = nullptr;
-    uint8_t* d_rq_legal = nullptr;
-    int32_t *d_rq_tp = nullptr, *d_rq_act = nullptr, *d_rq_state = nullptr;
-    // mz_replay_reanalyse_next: the round's packed (slot, pos) rows (in sp_allocs), and
-    // mz_train_set_reanalyse's rounds inside mz_train_run
-    int32_t* d_rean_rows = nullptr;
-    int rean_rows_cap = 0;
-    int tr_rean_mode = 0, tr_rean_rounds = 0, tr_rean_expl = 0;
-    // L learner steps per launch pair (mz_learner_train_multi_dev, ChainParams): the bank of
-    // MZ_MULTI_MAX small-kernel images (θ_t .. θ_{t+L-1}), per-step batches, read-outs,
-    // loss terms, Σθ² partials, fold counters and losses, for batches up to ml_cap
-    float* d_bank_w = nullptr; float* d_bank_b = nullptr;
-    // ResNet nets: the MFMA image bank (W, B), the flat-parameter bank, per-step unroll scratch (h, trunk
-    // outputs), progress words and downsampled batches
-    float* d_tbank_w = nullptr; float* d_tbank_b = nullptr; float* d_fbank = nullptr;
-    float* d_ml_hs = nullptr; float* d_ml_ts = nullptr; float* d_ml_dsb = nullptr;
-    unsigned long long* d_ml_prog = nullptr;
-    unsigned long long ml_prog_epoch = 0;   // multi-step fused launches (d_ml_prog's prog_base = epoch · 64)
-    int ml_cap = 0, ml_cap_L = 0, ml_last_B = 0, ml_last_L = 0, ml_last_R = 0;   // (ring: ensure_multi)
-    float *d_ml_obs = nullptr, *d_ml_act = nullptr, *d_ml_tv = nullptr, *d_ml_tr = nullptr, *d_ml_tp = nullptr,
-          *d_ml_gs = nullptr, *d_ml_pv = nullptr, *d_ml_pp = nullptr, *d_ml_pr = nullptr, *d_ml_terms = nullptr,
-          *d_ml_out = nullptr;
-    int32_t* d_ml_index = nullptr;
-    double* d_ml_part = nullptr;
-    unsigned* d_ml_cnt = nullptr;
-    // actor–learner loop (mz_train_*): the actors' weight set (flat + the
-    // search images), the queued nets (remote_NNs, flat), the learner step t
-    struct WSet { float* flat = nullptr; float* Wp = nullptr; float* Bp = nullptr; float* smw = nullptr;
-                  float* smb = nullptr; };
-    WSet tr_actor;
-    // MZ_OPP_NETWORK: the opponent's weight set, a handle setting allocated by the
-    // first mz_opponent_* call that fills it; opp_have = the nets given so far (bit per net, 7 =
-    // complete); the opponent search's outputs (in sp_allocs, allocated when the mode is first used)
-    WSet opp;
-    unsigned opp_have = 0;
-    float* d_cv2 = nullptr; float* d_rv2 = nullptr; int32_t* d_act2 = nullptr;
-    float* d_tr_queued = nullptr;
-    int tr_B = 0;
-    int64_t tr_t = 0, tr_games = 0, tr_refresh = 0;
-    long long* h_tr_cnt = nullptr;          // pinned: num_played_games read back once per move
-    long long* h_tr_pub = nullptr;          // coherent pinned: mz_tr_publish's {count, fault, sequence}
-    long long tr_pub_seq = 0;
-    // corrected-gradient learner (mz_backprop.hip): the unrolled graph and its arenas
-    int learn_mode = MZ_LEARN_REF_SEMANTICS;
-    bool bp_built = false;
-    // the corrected learner for the ResNet nets (mz_rbp_sample / mz_rbp_dw)
-    bool rbp_built = false;
-    int rbp_n_app = 0, rbp_n_head = 0, rbp_arena = 0, rbp_obs_t = 0, rbp_dt = 0, rbp_xs = 0, rbp_n_job = 0, rbp_cap = 0;
-    int rbp_ring = 0;                      // forward / backward LDS ring slots of mz_rbp_sample
-    int2* d_rbp_gzero = nullptr; int rbp_n_gzero = 0;
-    int rbp_threads = 256;
-    int rbp_job0[4] = {0, 0, 0, 0};
-    RbpApp* d_rbp_apps = nullptr; BpHead* d_rbp_heads = nullptr;
-    RbpLayer* d_rbp_layers = nullptr; RbpUse* d_rbp_uses = nullptr; RbpJob* d_rbp_jobs = nullptr;
-    float* d_rbp_act = nullptr; float* d_rbp_grad = nullptr;
-    float* d_rbp_terms = nullptr; double* d_rbp_sq = nullptr;
-    // ... through the downsampler (mz_dsbp_*): per-sample arenas, one dW job per conv output channel
-    int dsbp_arena = 0, dsbp_dt = 0, dsbp_n_job = 0, dsbp_cap = 0;
-    DsBpLayer* d_dsbp_lay = nullptr; DsDwJob* d_dsbp_jobs = nullptr;
-    float* d_dsbp_act = nullptr; float* d_dsbp_grad = nullptr;
-    int bp_n_app = 0, bp_n_head = 0, bp_n_job = 0, bp_tile_floats = 0, bp_obs_t = 0, bp_tiles_cap = 0;
-    BpApp* d_bp_apps = nullptr; BpHead* d_bp_heads = nullptr; BpLayer* d_bp_layers = nullptr;
-    BpUse* d_bp_uses = nullptr; BpJob* d_bp_jobs = nullptr;
-    int2* d_bp_funits = nullptr; int* d_bp_flev = nullptr; int2* d_bp_bunits = nullptr; int* d_bp_blev = nullptr;
-    int bp_n_flev = 0, bp_n_blev = 0, bp_n_funit = 0, bp_n_bunit = 0;
-    int* d_bp_fsync = nullptr; int* d_bp_bsync = nullptr; int bp_cache_floats = 0, bp_obs_s = -1;
-    double* d_bp_sq = nullptr; int bp_job0[4] = {0, 0, 0, 0};
-    float* d_bp_act = nullptr; float* d_bp_grad = nullptr; float* d_bp_terms = nullptr;
-    std::vector<void*> sp_allocs;
-    std::vector<void*> allocs;
-};
-
-#define MZ_TRY(h, expr)                                                                  \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess) {                                                          \
-            (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                \
-            return -1;                                                                   \
-        }                                                                                \
-    } while (0)
-
-static int fail(mz_handle* h, const std::string& m) { h->err = m; return -2; }
-// the stream of a `_dev` call: the caller's, or the handle's own
-static hipStream_t stream_of(const mz_handle* h, void* stream) { return stream ? (hipStream_t)stream : h->stream; }
 static int timing_events(mz_handle* h, hipEvent_t* e0, hipEvent_t* e1);
-
-// Host-synchronous entry points (weights, state, replay read-outs, debug
-// copies) wait for ALL of this process's work on the device, not only the
-// handle's stream: `_dev` calls may have queued work on a caller stream
-// (torch's, created non-blocking like the handle's), which a blocking
-// hipMemcpy would not wait for.  A caller that orders its own
-// work narrows the wait to one named stream plus the handle's own with
-// mz_set_sync_stream, so unrelated device work is not waited for.
-static hipError_t sync_device(mz_handle* h) {
-    if (!h->sync_narrow) return hipDeviceSynchronize();
-    hipError_t e = hipStreamSynchronize(h->sync_stream);
-    return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
-}
-
-// After a synchronisation: a kernel that gave up on a cross-workgroup publish
-// (mz_poll_ge) left bits in d_fault; report them once (the word is cleared)
-// as this call's error.  The outputs of the launches since the last check
-// are then not to be trusted.
-static int check_fault(mz_handle* h) {
-    if (!h->d_fault) return 0;
-    unsigned v = 0;
-    MZ_TRY(h, hipMemcpy(&v, h->d_fault, 4, hipMemcpyDeviceToHost));
-    if (!v) return 0;
-    MZ_TRY(h, hipMemset(h->d_fault, 0, 4));
-    char wait[32];
-    std::snprintf(wait, sizeof(wait), "%.3g s", (double)h->poll_ticks / 1e8);   // the 100 MHz constant clock
-    std::string m = std::string("device fault: a workgroup waited ") + wait + " for a publish that never came (";
-    if (v & MZ_FAULT_RS_TRUNK) m += "mz_rsearch_nets trunk hand-off ";
-    if (v & MZ_FAULT_RD_PROGRESS) m += "mz_runroll_fused_r chain progress ";
-    h->err = m + "); the results of the launches since the last synchronisation are invalid (search results, "
-                 "games self-play stored from them, losses, read-outs; the ref_semantics weights and ADAM state "
-                 "do not read them and stay valid)";
-    return -1;
-}
-
-// every host-synchronous call: wait (sync_device), then report a device fault
-#define MZ_SYNC(h)                                    \
-    do {                                              \
-        MZ_TRY(h, sync_device(h));                    \
-        if (check_fault(h)) return -1;                \
-    } while (0)
-
-template <typename T>
-static hipError_t dalloc(mz_handle* h, T** p, size_t n) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T) + 16);
-    if (e == hipSuccess) h->allocs.push_back(*p);
-    return e;
-}
-// free one dalloc'd buffer before the handle is destroyed (the caller has drained the work using it)
-static hipError_t dfree(mz_handle* h, void* p) {
-    auto it = std::find(h->allocs.begin(), h->allocs.end(), p);
-    if (it == h->allocs.end()) return hipErrorInvalidValue;
-    h->allocs.erase(it);
-    return hipFree(p);
-}
 
 // ------------------------------------------------------------ specs & plans
 static void add_layer(mz_handle* h, int net, int chain, int in, int out, int act, bool bn = false) {
@@ -831,7 +457,7 @@ static int build_pack_index(mz_handle* h) {
     return 0;
 }
 
-static int repack(mz_handle* h, hipStream_t st = nullptr) {
+int mz::repack(mz_handle* h, hipStream_t st) {
     const int T = 256;
     if (!st) st = h->stream;
     hipLaunchKernelGGL(mz_repack_kernel, dim3((unsigned)((h->packed_w_n + T - 1) / T)), dim3(T), 0, st,
@@ -867,7 +493,7 @@ static size_t unroll_small_lds(const mz_handle* h, int ti) {
            (h->sm_bn ? nri * 8 : 0);                                   // BatchNorm (γ, β) per record row
 }
 
-static size_t tree_game_bytes(int S, int A) {
+size_t mz::tree_game_bytes(int S, int A) {
     return tree_bytes((S + 1) * A, S + 1);
 }
 static size_t search_lds_base(const mz_handle* h) {
@@ -884,670 +510,8 @@ static search_fn search_kernel(const mz_handle* h) {
 }
 
 // ------------------------------------------------------------------- ABI
-extern "C" {
-
 const char* mz_create_error(void) { return g_create_error.c_str(); }
 const char* mz_last_error(const mz_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
-
-// ------------------------------------------------------------- ResNet nets
-// Row a14: the intended architecture of Learning.jl:148-255,
-// op for op as oracle/mz_oracle.c onet_build_resnet, in Flux.params order:
-// Conv weight (kw,kh,cin,cout) col-major, bias, BatchNorm β, γ; Dense W
-// (out,in) col-major, b.
-struct RSpec {
-    int chain, conv, cin, cout, kw, kh, act, bn, res_save, res_add;
-    size_t woff, boff, bnoff;               // local to the net
-};
-
-static std::vector<RSpec> rn_specs(const mz_config& c, const mz_resnet_hp& hp, int net, size_t* nparams) {
-    const int W = c.observation_shape[0], H = c.observation_shape[1], C = c.observation_shape[2];
-    const int nf = hp.num_filters, nb = hp.num_blocks, hs = hp.width_hidden, A = c.action_space_size;
-    const int P = W * H, nvf = hp.num_first_head_filters, npf = hp.num_second_head_filters;
-    std::vector<RSpec> v;
-    size_t n = 0;
-    auto conv = [&](int ch, int cin, int cout, int kw, int kh) {
-        RSpec r{ch, 1, cin, cout, kw, kh, MZ_ACT_RELU, 1, 0, 0, 0, 0, 0};
-        r.woff = n; n += (size_t)kw * kh * cin * cout;
-        r.boff = n; n += (size_t)cout;
-        r.bnoff = n; n += (size_t)2 * cout;
-        v.push_back(r);
-    };
-    auto block = [&](int ch, int f, int kw, int kh) { conv(ch, f, f, kw, kh); v.back().res_save = 1;
-                                                      conv(ch, f, f, kw, kh); v.back().res_add = 1; };
-    auto dense = [&](int ch, int in, int out, int act) {
-        RSpec r{ch, 0, in, out, 1, 1, act, 0, 0, 0, 0, 0, 0};
-        r.woff = n; n += (size_t)in * out;
-        r.boff = n; n += (size_t)out;
-        v.push_back(r);
-    };
-    if (net == MZ_NET_REPR) {
-        const int kw = hp.conv_kernel_size[0], kh = hp.conv_kernel_size[1];
-        conv(0, C * (c.stacked_observations + 1) + c.stacked_observations, nf, kw, kh);
-        for (int i = 0; i < nb; ++i) block(0, nf, kw, kh);
-    } else if (net == MZ_NET_PRED) {
-        conv(0, nf, nf, 1, 1);
-        for (int i = 0; i < nb; ++i) block(0, nf, 1, 1);
-        conv(1, nf, nvf, 1, 1);
-        dense(1, P * nvf, hs, MZ_ACT_RELU);
-        for (int i = 0; i < hp.depth_value; ++i) dense(1, hs, hs, MZ_ACT_RELU);
-        dense(1, hs, 1, MZ_ACT_TANH);
-        conv(2, nf, npf, 1, 1);
-        dense(2, P * npf, hs, MZ_ACT_IDENTITY);
-        for (int i = 0; i < hp.depth_value; ++i) dense(2, hs, hs, MZ_ACT_RELU);    // :222 depth_value
-        dense(2, hs, A, MZ_ACT_IDENTITY);
-    } else {
-        conv(0, nf + 1, nf, 1, 1);
-        for (int i = 0; i < nb; ++i) block(0, nf, 1, 1);
-        conv(1, nf, nf, 1, 1);
-        for (int i = 0; i < nb; ++i) block(1, nf, 1, 1);
-        conv(2, nf, nvf, 1, 1);
-        dense(2, P * nvf, hs, MZ_ACT_RELU);
-        for (int i = 0; i < hp.depth_value; ++i) dense(2, hs, hs, MZ_ACT_RELU);
-        dense(2, hs, 1, hp.reward_activation);
-    }
-    *nparams = n;
-    return v;
-}
-
-// LDS plan of one net for a tile of NG games (floats).  Trunk: X -> B0, each
-// block B0 -> B1 -> B0 (residual in place); head 1 reads B0 (the dynamics
-// state head runs its tower in B2 / B1, B2 aliasing the dead input X); head 2
-// reads B0 through the small buffers S0..S2; outputs O0 / O1.
-// Offset table of a narrow plan's layer L with a kernel > 1x1 (MODE 4 of
-// rn_layer_t): for quarter q, chunk c, column n < ncols_t and bank slot
-// sl = ((n >> 2) & 3) ^ σ(kl), the byte addresses of B(k, n), k = (q·nq + 4c +
-// jj)·4 + kl, jj = 0..3 — the same operand MODE 2 gathers through the k table —
-// or of the zero float for taps off the board, padded steps and columns past
-// the tile.  One 16-byte read gives a lane a chunk's four addresses.
-static void rn_otab_fill(std::vector<int>& t, const RLayer& L, int NG, int W, int P, int ncols_t, int zero_off) {
-    static const int sinv[4] = {0, 2, 3, 1};                      // σ^-1, σ = (0, 3, 1, 2)
-    const int nch = ((L.nq + 3) & ~3) / 4;
-    for (int q = 0; q < 4; ++q)
-        for (int c = 0; c < nch; ++c)
-            for (int n = 0; n < ncols_t; ++n)
-                for (int sl = 0; sl < 4; ++sl)
-                    for (int jj = 0; jj < 4; ++jj) {
-                        const int kl = sinv[sl ^ ((n >> 2) & 3)], j = 4 * c + jj, k = (q * L.nq + j) * 4 + kl;
-                        int a = zero_off;
-                        if (j < L.nq && k < L.K && n < P * NG) {
-                            const int ci = k / L.kk, r = k - ci * L.kk, jy = r / L.kw, ix = r - jy * L.kw;
-                            const int dx = (L.kw - 1 - ix) - L.pw, dy = (L.kh - 1 - jy) - L.ph;
-                            const int p = n / NG, g = n - p * NG, px = p % W + dx, py = p / W + dy;
-                            if (px >= 0 && px < W && py >= 0 && py < P / W)
-                                a = L.in_off + ci * P * NG + (px + W * py) * NG + g;
-                        }
-                        t.push_back(a * 4);
-                    }
-}
-
-// mz_runroll_chain_r applies when the plane is one column block (the narrow
-// tiles are one sample wide) and the dynamics chain ([0, dyn_split)) is RD_NL
-// 1x1 conv layers of 64 channels with BatchNorm + relu: layer 0 on the plain
-// input with 4 < nq <= 8 (nf + 1 channels: two A chunks), the others K = 64 on
-// k-blocked inputs.  (A three-block variant for 4-block towers, 18 layers, kept
-// 304 VGPRs resident and spilled: 1.27k vs 1.53k learner steps/s on Connect4
-// ResNet-8; it was removed.)
-static size_t rd_chain_lds(const mz_handle* h) { return h->rn_lds_l + (size_t)h->rn_dyn_split * 64 * 16; }
-static bool rd_chain_ok(const mz_handle* h) {
-    const RPlan& R = h->rplan_l[MZ_NET_DYN];
-    if ((h->plane + 15) / 16 != 1 || h->rn_dyn_split != RD_NL) return false;
-    for (int i = 0; i < h->rn_dyn_split; ++i) {
-        const RLayer& L = R.L[i];
-        if (L.kk != 1 || L.cout != 64 || L.n_ob != 4 || !L.spatial || !L.bn || L.act != MZ_ACT_RELU) return false;
-        if (i == 0 ? (L.in_kb || L.nq <= 4 || L.nq > 8) : (!L.in_kb || L.K != 64 || L.nq != 4)) return false;
-    }
-    return rd_chain_lds(h) <= kLdsMax;
-}
-// mz_runroll_pred_r applies when the prediction trunk ([0, RP_NL), the
-// first head layer next) is RP_NL such layers, all on k-blocked inputs
-static size_t rp_pred_lds(const mz_handle* h) { return h->rn_lds_l + (size_t)RP_NL * 64 * 16; }
-static bool rp_pred_ok(const mz_handle* h) {
-    const RPlan& R = h->rplan_l[MZ_NET_PRED];
-    if ((h->plane + 15) / 16 != 1 || R.n <= RP_NL || R.L[RP_NL].cout == 64) return false;
-    if (2 * h->rhp.num_blocks + 1 != RP_NL) return false;
-    for (int i = 0; i < RP_NL; ++i) {
-        const RLayer& L = R.L[i];
-        if (L.kk != 1 || L.cout != 64 || L.n_ob != 4 || !L.spatial || !L.bn || L.act != MZ_ACT_RELU ||
-            !L.in_kb || L.K != 64 || L.nq != 4)
-            return false;
-    }
-    // the heads in rn_specs order: value [RP_NL, RP_NL + nv), policy after (the fused
-    // launch runs them in separate blocks)
-    const int nv = 3 + h->rhp.depth_value;
-    if (R.n != RP_NL + 2 * nv || R.L[RP_NL].cout != h->rhp.num_first_head_filters ||
-        R.L[RP_NL + nv].cout != h->rhp.num_second_head_filters || R.L[RP_NL + nv - 1].cout != 1)
-        return false;
-    return rp_pred_lds(h) <= kLdsMax;
-}
-
-static RPlan rn_plan(const mz_handle* h, const std::vector<RSpec>& sp, int net, int NG, size_t flat_off,
-                     int& w_img, std::vector<int>* srcw, bool sep_b2 = false, std::vector<int>* otab = nullptr) {
-    const mz_config& c = h->rconf;
-    const int W = c.observation_shape[0], Hh = c.observation_shape[1], P = W * Hh;
-    const int nf = h->rhp.num_filters, hs = h->rhp.width_hidden;
-    const int in_feat = net == MZ_NET_REPR ? h->rin_feat : net == MZ_NET_PRED ? h->H : h->H + h->plane;
-    const int big = nf * P * NG;
-    int off = 0;
-    auto region = [&](int n) { int o = off; off += (n + 3) / 4 * 4; return o; };
-    RPlan R;
-    std::memset(&R, 0, sizeof(R));
-    // the dynamics state head's B2 aliases the dead input X, or (sep_b2, when the
-    // LDS allows) has its own region, so that its layout can be k-blocked
-    const int X = region(std::max(in_feat * NG, net == MZ_NET_DYN && !sep_b2 ? big : 0));
-    const int B0 = region(big), B1 = region(big);
-    // (aliased, B2 sits at the END of X's region, at a different offset from X:
-    // a region's layout follows the readers of its offset, so B2 can be
-    // k-blocked for the state head's 1x1 convs while X stays plain for the
-    // K = nf + 1 first layer; X is dead once that layer has run)
-    const int xsz = (std::max(in_feat * NG, net == MZ_NET_DYN && !sep_b2 ? big : 0) + 3) / 4 * 4;
-    const int B2 = net == MZ_NET_DYN && sep_b2 ? region(big) : X + (xsz - big) / 4 * 4;
-    // the head convs write S0 (every conv off the trunk but the dynamics state head's tower, which
-    // runs in B2 / B1); their width is a hyperparameter of its own and may equal num_filters
-    int headc = 0;
-    for (const RSpec& r : sp)
-        if (r.chain && r.conv && !(net == MZ_NET_DYN && r.chain == 1)) headc = std::max(headc, r.cout * P * NG);
-    const int S0 = region(std::max(headc, hs * NG)), S1 = region(hs * NG), S2 = region(hs * NG);
-    const int O0 = net == MZ_NET_PRED ? region(NG) : B0;             // REPR / DYN out0 = h (B0 / B2)
-    const int O1 = net == MZ_NET_REPR ? 0 : region((net == MZ_NET_PRED ? h->A : 1) * NG);
-    R.in_off = X; R.in_feat = in_feat;
-    int cur[3] = {X, B0, B0};                                        // current input of each chain
-    int ping[3] = {0, S1, S1};
-    for (size_t i = 0; i < sp.size(); ++i) {
-        const RSpec& r = sp[i];
-        RLayer& L = R.L[R.n++];
-        L.kk = r.kw * r.kh; L.kw = r.kw; L.kh = r.kh; L.pw = r.kw / 2; L.ph = r.kh / 2;
-        L.K = r.conv ? r.kw * r.kh * r.cin : r.cin;
-        L.cout = r.cout; L.nq = (L.K + 15) / 16; L.n_ob = (r.cout + 15) / 16;
-        L.spatial = r.conv; L.act = r.act; L.bn = r.bn; L.res_add = r.res_add;
-        L.boff = (int)(flat_off + r.boff); L.bnoff = (int)(flat_off + r.bnoff);
-        L.ktab = -1;
-        L.in_off = cur[r.chain];
-        const bool last_in_chain = i + 1 == sp.size() || sp[i + 1].chain != r.chain;
-        if (r.chain == 0) {
-            if (r.res_add) { L.out_off = B0; L.res_off = B0; L.in_off = B1; }
-            else if (r.res_save) L.out_off = B1;
-            else L.out_off = B0;
-            cur[0] = r.res_save ? B1 : B0;
-            if (r.res_add) cur[0] = B0;
-            if (last_in_chain) { cur[1] = cur[2] = B0; }
-        } else if (r.chain == 1 && net == MZ_NET_DYN) {            // state head tower in B2 / B1
-            if (r.res_add) { L.in_off = B1; L.out_off = B2; L.res_off = B2; }
-            else if (r.res_save) { L.out_off = B1; }
-            else L.out_off = B2;
-            cur[1] = r.res_save ? B1 : B2;
-        } else {                                                    // conv head -> Dense chain
-            if (last_in_chain) L.out_off = r.chain == 1 ? O0 : O1;
-            else if (r.conv) L.out_off = S0;
-            else { L.out_off = ping[r.chain]; ping[r.chain] = ping[r.chain] == S1 ? S2 : S1; }
-            cur[r.chain] = L.out_off;
-        }
-        // A fragments [ob][q][j/4][lane][j%4] (NQ padded to NQ4 = 4⌈NQ/4⌉ with
-        // zeros): one 16-byte load gives a lane four k-steps of a quarter chain
-        L.w_img = w_img;
-        const int nq4 = (L.nq + 3) & ~3;
-        for (int ob = 0; ob < L.n_ob; ++ob)
-            for (int q = 0; q < 4; ++q)
-                for (int jc = 0; jc < nq4 / 4; ++jc)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int jj = 0; jj < 4; ++jj) {
-                            const int j = 4 * jc + jj;
-                            const int o = ob * 16 + (lane & 15), k = (q * L.nq + j) * 4 + (lane >> 4);
-                            int src = -1;
-                            if (j < L.nq && o < r.cout && k < L.K)
-                                src = (int)(flat_off + r.woff + (r.conv ? (size_t)k + (size_t)L.K * o
-                                                                        : (size_t)o + (size_t)r.cout * k));
-                            if (srcw) srcw->push_back(src);
-                        }
-        w_img += L.n_ob * 4 * nq4 * 64;
-        // epilogue image: per output row o, {bias, γ, β, 0} (a lane's four rows
-        // are four 16-byte loads; ADAM scatters into it through the same inverse map)
-        L.ep_img = w_img;
-        for (int o = 0; o < L.n_ob * 16; ++o) {
-            const bool in = o < r.cout;
-            const int e[4] = {in ? (int)(flat_off + r.boff + o) : -1,
-                              in && r.bn ? (int)(flat_off + r.bnoff + r.cout + o) : -1,
-                              in && r.bn ? (int)(flat_off + r.bnoff + o) : -1, -1};
-            if (srcw) for (int x = 0; x < 4; ++x) srcw->push_back(e[x]);
-        }
-        w_img += L.n_ob * 16 * 4;
-        if (L.kk > 1 && !otab) L.ktab = region(L.K);
-    }
-    // layouts, per LDS region: k-blocked when every layer that reads the region
-    // as its B operand is a 1x1 conv / Dense with K % 64 == 0 (a region's
-    // layout never changes, so in-place residual blocks and aliased regions
-    // stay consistent); the final outputs are checked plain below
-    auto capable = [&](const RLayer& L) { return L.kk == 1 && L.K % 64 == 0; };
-    // (the k-blocked position of an element depends on the column count, so a region a conv
-    // writes, P·NG columns, and a Dense layer reads as its flattened features, NG columns,
-    // stays plain, where the two agree: a head conv whose P·cout is a multiple of 64)
-    auto kb = [&](int off) {
-        bool any = false, all = true, dense_in = false, conv_out = false;
-        for (int j = 0; j < R.n; ++j) {
-            if (R.L[j].in_off == off) { any = true; all &= capable(R.L[j]); dense_in |= !R.L[j].spatial; }
-            if (R.L[j].out_off == off) conv_out |= R.L[j].spatial != 0;
-        }
-        return (int)(any && all && !(dense_in && conv_out));
-    };
-    R.in_kb = kb(X);
-    for (int j = 0; j < R.n; ++j) {
-        R.L[j].in_kb = kb(R.L[j].in_off);
-        R.L[j].out_kb = kb(R.L[j].out_off);
-        R.L[j].res_kb = R.L[j].res_add ? kb(R.L[j].res_off) : 0;
-    }
-    if (net == MZ_NET_REPR) { R.out0_off = B0; R.out0_n = h->H; R.out1_n = 0; }
-    else if (net == MZ_NET_PRED) { R.out0_off = O0; R.out0_n = 1; R.out1_off = O1; R.out1_n = h->A; }
-    else { R.out0_off = B2; R.out0_n = h->H; R.out1_off = O1; R.out1_n = 1; }
-    R.out0_act = R.out1_act = MZ_ACT_IDENTITY;
-    for (int j = 0; j < R.n; ++j) {
-        if (R.L[j].out_off == R.out0_off) R.out0_act = R.L[j].act;
-        if (R.out1_n && R.L[j].out_off == R.out1_off) R.out1_act = R.L[j].act;
-    }
-    if (otab) {   // narrow plans: offset tables for the kernels > 1x1 (shared by layers of the same input / shape)
-        const int n_nb = (P * NG + 15) >> 4, nbw = n_nb == 1 ? 1 : n_nb == 2 ? 2 : 3;
-        const int ncols_t = (n_nb + nbw - 1) / nbw * nbw * 16;
-        const int zero = region(4);
-        std::vector<int> t;
-        std::vector<std::pair<std::vector<int>, int>> seen;      // (in_off, K, kw, kh) -> table offset in t
-        for (int i = 0; i < R.n; ++i) {
-            RLayer& L = R.L[i];
-            if (L.kk == 1) continue;
-            const std::vector<int> key = {L.in_off, L.K, L.kw, L.kh};
-            int at = -1;
-            for (auto& e : seen) if (e.first == key) at = e.second;
-            if (at < 0) { at = (int)t.size(); seen.push_back({key, at}); rn_otab_fill(t, L, NG, W, P, ncols_t, zero); }
-            L.ktab = at;                                           // relative until the region is placed
-            L.otab = 1;
-        }
-        if (!t.empty() && (size_t)(off + t.size() + 16 * 16 * 4) * 4 <= kLdsMax) {
-            R.tab_lds = region((int)t.size());
-            R.tab_n = (int)t.size();
-            R.tab_src = (int)otab->size();
-            R.zero_off = zero;
-            otab->insert(otab->end(), t.begin(), t.end());
-            for (int i = 0; i < R.n; ++i) if (R.L[i].otab) R.L[i].ktab += R.tab_lds;
-        } else {                                                   // does not fit: the k-table gather (MODE 2)
-            for (int i = 0; i < R.n; ++i) if (R.L[i].otab) { R.L[i].otab = 0; R.L[i].ktab = -1; }
-        }
-        for (int i = 0; i < R.n; ++i)                              // k tables for the layers that still need one
-            if (R.L[i].kk > 1 && !R.L[i].otab && R.L[i].ktab < 0) R.L[i].ktab = region(R.L[i].K);
-    }
-    region(16 * 16 * 4);           // slack: past-the-tile lanes of k-blocked reads (MODE 3) read up to 15 columns on
-    R.n_ktab = 0;
-    for (int j = 0; j < R.n; ++j) R.n_ktab += R.L[j].kk > 1 && !R.L[j].otab;
-    R.lds_floats = off;
-    R.out0_kb = kb(R.out0_off);
-    for (int j = 0; j < R.n; ++j) R.k[j] = rn_rk_pack(R.L[j]);
-    if ((R.out0_kb && net == MZ_NET_PRED) || (R.out1_n && kb(R.out1_off))) R.n = -1;   // (never: read as plain)
-    return R;
-}
-
-// The packed layer entry (rn_rk_pack) carries a layer's k table / offset table LDS offset in
-// 16 signed bits: a plan whose table lies past 32767 does not run (a narrower tile may)
-static bool rn_ktab_ok(const RPlan& R) {
-    for (int j = 0; j < R.n; ++j)
-        if (R.L[j].kk > 1 && R.L[j].ktab > 32767) return false;
-    return true;
-}
-
-// pUCT tables (libm log2/sqrt on the host: the values the oracle computes
-// inline), the action-plane values a/|A|, and the pb_term triangle
-static int alloc_search_tables(mz_handle* h) {
-    const mz_config& c = h->conf;
-    const int S = h->S, A = h->A;
-    std::vector<double> pbc(S + 2), sq(S + 2);
-    for (int n = 0; n < S + 2; ++n) {
-        pbc[n] = std::log2((double)(n + c.pb_c_base + 1) / (double)c.pb_c_base) + (double)c.pb_c_init;
-        sq[n] = std::sqrt((double)n);
-    }
-    std::vector<float> av(A);
-    for (int a = 0; a < A; ++a) av[a] = (float)((double)(a + 1) / (double)A);
-    std::vector<double> pbt(pbterm_count(S), 0.0);
-    for (int np = 0; np <= S + 1; ++np)
-        for (int nc = 0; nc <= np; ++nc) pbt[pbterm_index(np, nc)] = pbc[np] * (sq[np] / (double)(nc + 1));
-    MZ_TRY(h, dalloc(h, &h->d_pbc, pbc.size()));
-    MZ_TRY(h, dalloc(h, &h->d_sqrt, sq.size()));
-    MZ_TRY(h, dalloc(h, &h->d_aval, av.size()));
-    MZ_TRY(h, dalloc(h, &h->d_pbterm, pbt.size()));
-    MZ_TRY(h, hipMemcpy(h->d_pbc, pbc.data(), pbc.size() * 8, hipMemcpyHostToDevice));
-    MZ_TRY(h, hipMemcpy(h->d_sqrt, sq.data(), sq.size() * 8, hipMemcpyHostToDevice));
-    MZ_TRY(h, hipMemcpy(h->d_aval, av.data(), av.size() * 4, hipMemcpyHostToDevice));
-    MZ_TRY(h, hipMemcpy(h->d_pbterm, pbt.data(), pbt.size() * 8, hipMemcpyHostToDevice));
-    return 0;
-}
-
-// loss / Σθ² scratch, per-net offsets and the last-block counter of
-// mz_learner_grad_kernel
-static int alloc_learner(mz_handle* h) {
-    MZ_TRY(h, dalloc(h, &h->d_loss, 8));
-    MZ_TRY(h, dalloc(h, &h->d_sq, 3 * MZ_L2_BLOCKS));
-    size_t oc[6] = {h->flat_off[0], h->flat_off[1], h->flat_off[2], h->nparams[0], h->nparams[1], h->nparams[2]};
-    MZ_TRY(h, dalloc(h, &h->d_netoff, 6));
-    MZ_TRY(h, dalloc(h, &h->d_counter, 1));
-    MZ_TRY(h, hipMemset(h->d_counter, 0, 4));
-    MZ_TRY(h, dalloc(h, &h->d_fault, 1));
-    MZ_TRY(h, hipMemset(h->d_fault, 0, 4));
-    // debug (tests/test_fault_gpu.py): MZ_DEBUG_SKIP_PUBLISH=1 at create makes
-    // tile / sample 0 of the cross-workgroup hand-offs skip its publish, with a
-    // 10 ms poll bound, so the reported fault can be tested
-    if (std::getenv("MZ_DEBUG_SKIP_PUBLISH")) { h->dbg_skip = 0; h->poll_ticks = 1000000ull; }
-    MZ_TRY(h, hipMemcpy(h->d_netoff, oc, sizeof(oc), hipMemcpyHostToDevice));
-    return 0;
-}
-
-static size_t rsearch_root_lds(const mz_handle* h) {
-    const int gw = h->A > 16 ? 32 : 16;     // softmax / noise staging [16][gw] x 2
-    return (size_t)std::max(h->rplan[0].lds_floats, h->rplan[1].lds_floats) * 4 + (size_t)2 * 16 * gw * 4;
-}
-
-// The downsampler of Learning.jl:175-187 (op for op as oracle/mz_oracle.c
-// onet_build_resnet with downsample, `size` read as conv_kernel_size):
-// Conv(k, C => C, stride 2), 2 blocks, Conv(k, C => 2C, stride 2), 3 blocks,
-// MeanPool((3,3), stride 2, pad 1), 3 blocks, MeanPool — then the tail
-// Conv(k, 2C => nf) + BatchNorm + blocks is the RPlan of rconf.  Parameters
-// (Flux.params order, first in the representation's flat vector): strided
-// conv W, b; block conv W, b, β, γ.  Returns the parameter count.
-static size_t ds_build(mz_handle* h, DsPlan& D) {
-    const mz_config& c = h->conf;
-    const int kw = h->rhp.conv_kernel_size[0], kh = h->rhp.conv_kernel_size[1];
-    int C = c.observation_shape[2] * (c.stacked_observations + 1) + c.stacked_observations;
-    int w = c.observation_shape[0], hh = c.observation_shape[1];
-    std::memset(&D, 0, sizeof(D));
-    D.in_feat = w * hh * C;
-    size_t n = 0;
-    int cur = -1;
-    auto s2 = [](int x, int k) { return (x + 2 * (k / 2) - k) / 2 + 1; };
-    auto conv = [&](int cin, int cout, int stride, int bn, int act) -> DsLayer& {
-        DsLayer& L = D.L[D.n++];
-        L.kind = DS_CONV; L.cin = cin; L.cout = cout; L.kw = kw; L.kh = kh; L.pw = kw / 2; L.ph = kh / 2;
-        L.stride = stride; L.Wi = w; L.Hi = hh;
-        L.Wo = stride == 2 ? s2(w, kw) : w; L.Ho = stride == 2 ? s2(hh, kh) : hh;
-        L.act = act; L.bn = bn;
-        L.woff = (int)n; n += (size_t)kw * kh * cin * cout;
-        L.boff = (int)n; n += (size_t)cout;
-        if (bn) { L.bnoff = (int)n; n += (size_t)2 * cout; }
-        L.pn = (int)(n - (size_t)L.woff);
-        D.w_floats = std::max(D.w_floats, kw * kh * cin * cout);
-        w = L.Wo; hh = L.Ho;
-        return L;
-    };
-    auto strided = [&](int cin, int cout) {
-        DsLayer& L = conv(cin, cout, 2, 0, MZ_ACT_IDENTITY);
-        L.in_buf = cur; L.out_buf = cur == 0 ? 1 : 0; cur = L.out_buf;
-    };
-    auto block = [&](int f) {
-        DsLayer& a = conv(f, f, 1, 1, MZ_ACT_RELU);
-        a.in_buf = cur; a.out_buf = 1 - cur;
-        DsLayer& b = conv(f, f, 1, 1, MZ_ACT_RELU);
-        b.in_buf = 1 - cur; b.out_buf = cur; b.res_add = 1; b.res_buf = cur;
-    };
-    auto pool = [&](int f) {
-        DsLayer& L = D.L[D.n++];
-        L.kind = DS_POOL; L.cin = f; L.cout = f; L.kw = 3; L.kh = 3; L.pw = 1; L.ph = 1; L.stride = 2;
-        L.Wi = w; L.Hi = hh; L.Wo = s2(w, 3); L.Ho = s2(hh, 3); L.act = MZ_ACT_IDENTITY;
-        L.in_buf = cur; L.out_buf = 1 - cur; cur = L.out_buf;
-        w = L.Wo; hh = L.Ho;
-    };
-    strided(C, C);
-    for (int i = 0; i < 2; ++i) block(C);
-    strided(C, 2 * C);
-    for (int i = 0; i < 3; ++i) block(2 * C);
-    pool(2 * C);
-    for (int i = 0; i < 3; ++i) block(2 * C);
-    pool(2 * C);
-    D.L[D.n - 1].out_buf = -1;                       // the last layer writes the output to HBM
-    D.out_feat = w * hh * 2 * C;
-    for (int i = 0; i < D.n; ++i) {
-        const DsLayer& L = D.L[i];
-        if (i > 0) D.buf_floats = std::max(D.buf_floats, L.cin * L.Wi * L.Hi);
-        D.buf_floats = std::max(D.buf_floats, L.cout * L.Wo * L.Ho);
-    }
-    D.buf_floats = (D.buf_floats + 3) & ~3;
-    D.w_floats = (D.w_floats + 3) & ~3;
-    h->rconf = c;
-    h->rconf.observation_shape[0] = w; h->rconf.observation_shape[1] = hh; h->rconf.observation_shape[2] = 2 * C;
-    h->rconf.stacked_observations = 0;
-    // LDS: buffer 0 | buffer 1 (from buf_floats; the staged observation for layer 0 when it fits, layer 0
-    // writing buffer 0) | one conv's packed parameters | the generic conv's weights and tap tables
-    for (int i = 0; i < D.n; ++i) D.pn_max = std::max(D.pn_max, D.L[i].pn);
-    D.pn_max = (D.pn_max + 3) & ~3;
-    const size_t gen = (size_t)D.pn_max + D.w_floats + 512;
-    const size_t in4 = ((size_t)D.in_feat + 3) & ~(size_t)3;
-    D.ptot = (int)(n - (size_t)D.L[0].woff);
-    D.stage_in = D.L[0].kind == DS_CONV && D.L[0].in_buf < 0 && D.L[0].out_buf == 0 && D.in_feat % 4 == 0 &&
-                 D.L[0].woff % 4 == 0 && (size_t)2 * D.buf_floats + D.ptot <= in4 &&
-                 ((size_t)D.buf_floats + std::max<size_t>(D.buf_floats, in4) + gen) * 4 <= kLdsMax;
-    D.lds_floats = (int)((size_t)D.buf_floats + (D.stage_in ? std::max<size_t>(D.buf_floats, in4) : D.buf_floats));
-    h->ds_lds = ((size_t)D.lds_floats + gen) * 4;
-    return n;
-}
-
-// run the downsampler over n items: x (in_feat, n) -> y (rin_feat, n); with
-// per_step > 0 item i uses the parameters flat + (i / per_step)·nflat (the
-// multi-step learner's per-step bank), else the engine's
-// the flat bank's per-step stride (rlearner_multi): nflat rounded up to 4 floats, so the downsampler's
-// float4 parameter staging (DsParams.per_step) reads 16-byte aligned rows
-static size_t fbank_stride(const mz_handle* h) { return (h->nflat + 3) / 4 * 4; }
-static int ds_launch(mz_handle* h, const float* x, float* y, int n, hipStream_t st, const float* flat = nullptr,
-                     int per_step = 0) {
-    DsParams Q;
-    Q.n_items = n; Q.bn_s = h->bn_s; Q.plan = h->d_dsplan; Q.flat = h->d_flat; Q.x = x; Q.y = y;
-    Q.stamps = nullptr;
-    Q.per_step = per_step; Q.flat_stride = fbank_stride(h);
-    if (flat) Q.flat = flat;
-#ifdef MZ_STAMPS
-    if (!h->d_stamps) MZ_TRY(h, dalloc(h, &h->d_stamps, (size_t)8 * std::max(h->max_games, 128)));
-    Q.stamps = h->d_stamps;
-#endif
-    void* args[] = {&Q};
-    MZ_TRY(h, hipLaunchKernel((const void*)mz_downsample_kernel, dim3(n), dim3(DS_THREADS), args, h->ds_lds, st));
-    return 0;
-}
-static int ensure_dsb(mz_handle* h, int n) {
-    if (n <= h->dsb_cap) return 0;
-    if (h->d_dsb) { (void)hipFree(h->d_dsb); h->d_dsb = nullptr; }
-    MZ_TRY(h, hipMalloc(&h->d_dsb, (size_t)n * h->rin_feat * 4));
-    h->dsb_cap = n;
-    return 0;
-}
-static size_t rsearch_nets_lds(const mz_handle* h) {
-    return (size_t)std::max(h->rplan[1].lds_floats, h->rplan[2].lds_floats) * 4;
-}
-
-int mz_engine_create_resnet(const mz_config* conf, const mz_resnet_hp* hyper, int device, int max_games,
-                            uint64_t rng_seed, mz_handle** out) {
-    g_create_error.clear();
-    if (!conf || !hyper || !out) { g_create_error = "null argument"; return -2; }
-    *out = nullptr;
-    mz_handle* h = new mz_handle();
-    h->kind = 1; h->conf = *conf; h->rhp = *hyper; h->device = device; h->max_games = max_games;
-    h->seed = rng_seed;
-    auto bad = [&](const std::string& m) { g_create_error = m; delete h; return -2; };
-    const mz_config& c = *conf;
-    if (c.action_space_size < 1 || c.action_space_size > 32)
-        return bad("action_space_size must be in 1..32 (16- or 32-lane select groups)");
-    if (c.players < 1 || c.players > 2) return bad("players must be 1 or 2");
-    if (c.num_iters < 1 || c.num_iters > 65000) return bad("num_iters out of range");
-    if (hyper->conv_kernel_size[0] % 2 == 0 || hyper->conv_kernel_size[1] % 2 == 0 ||
-        hyper->conv_kernel_size[0] > 15 || hyper->conv_kernel_size[1] > 15)
-        return bad("conv_kernel_size must be odd and <= 15 (Learning.jl:164 asserts odd)");
-    if (hyper->num_filters < 1 || hyper->num_blocks < 0 || hyper->width_hidden < 1) return bad("bad ResNetHP");
-    if (max_games < 1) return bad("max_games must be >= 1");
-    if (hipSetDevice(device) != hipSuccess) return bad("hipSetDevice failed (no GPU?)");
-    const int W = c.observation_shape[0], Hh = c.observation_shape[1], C = c.observation_shape[2];
-    h->obs_feat = W * Hh * (C * (c.stacked_observations + 1) + c.stacked_observations);
-    h->rconf = c;
-    h->A = c.action_space_size; h->S = c.num_iters;
-    if (hyper->downsample) {
-        h->ds = 1;
-        h->ds_n = ds_build(h, h->dsplan);
-        if (h->dsplan.L[0].kw * h->dsplan.L[0].kh * 2 * h->dsplan.L[0].cin > 256)
-            return bad("downsampler: conv_kernel_size x 2C input channels exceeds 256 taps");
-        if (h->ds_lds > kLdsMax) return bad("downsampler activations exceed the LDS");
-    }
-    const int rW = h->rconf.observation_shape[0], rH = h->rconf.observation_shape[1];
-    h->rin_feat = h->ds ? h->dsplan.out_feat : h->obs_feat;
-    h->plane = rW * rH;
-    h->H = rW * rH * hyper->num_filters;
-    std::vector<RSpec> sp[3];
-    size_t off = 0;
-    for (int n = 0; n < 3; ++n) {
-        sp[n] = rn_specs(h->rconf, *hyper, n, &h->nparams[n]);
-        h->flat_off[n] = off;
-        if (n == MZ_NET_REPR) h->nparams[n] += h->ds_n;     // downsampler params first
-        off += h->nparams[n];
-    }
-    h->nflat = off;
-    // widest tile whose three plans fit the LDS
-    for (int ng = 16; ng >= 1 && !h->rn_ng; ng /= 2) {
-        int wi = 0;
-        bool fits = true;
-        for (int n = 0; n < 3; ++n) {
-            const RPlan R = rn_plan(h, sp[n], n, ng, h->flat_off[n] + (n == 0 ? h->ds_n : 0), wi, nullptr);
-            fits &= (size_t)R.lds_floats * 4 <= kLdsMax && rn_ktab_ok(R);
-        }
-        if (fits) h->rn_ng = ng;
-    }
-    if (!h->rn_ng)
-        return bad("ResNet activations exceed the LDS even for one game per tile (or a k table lies past LDS "
-                   "offset 32767)");
-    h->bn_s = sqrtf(1.0f + 1e-5f);
-    int rc = 0;
-#define CK(x) do { if ((rc = (x)) != 0) { g_create_error = h->err; mz_engine_destroy(h); return rc; } } while (0)
-    CK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess ? 0 : fail(h, "hipStreamCreate"));
-    std::vector<int> sw;
-    int wi = 0;
-    h->rplan.resize(3);
-    for (int n = 0; n < 3; ++n) {
-        {
-            int wt = wi;
-            const bool sep = (size_t)rn_plan(h, sp[n], n, h->rn_ng, 0, wt, nullptr, true).lds_floats * 4 <= kLdsMax;
-            h->rplan[n] = rn_plan(h, sp[n], n, h->rn_ng, h->flat_off[n] + (n == 0 ? h->ds_n : 0), wi, &sw, sep);
-        }
-        CK(h->rplan[n].n < 0 ? fail(h, "ResNet plan: a k-blocked output buffer") : 0);
-        CK(!rn_ktab_ok(h->rplan[n]) ? fail(h, "ResNet plan: a k table past LDS offset 32767") : 0);
-        h->rn_lds[n] = (size_t)h->rplan[n].lds_floats * 4;
-    }
-    for (int n = 1; n < 3; ++n)                          // mz_rsearch_nets has no k-table path (NOKK)
-        for (int i = 0; i < h->rplan[n].n; ++i) {
-            const RLayer& L = h->rplan[n].L[i];
-            CK(L.kk > 1 ? fail(h, "ResNet plan: a prediction / dynamics kernel > 1x1") : 0);
-            // and applies a tanh only where the read-out does (RAWTANH): on the outputs
-            CK(L.act == MZ_ACT_TANH && L.out_off != h->rplan[n].out0_off &&
-                       !(h->rplan[n].out1_n && L.out_off == h->rplan[n].out1_off)
-                   ? fail(h, "ResNet plan: a tanh layer that is not an output") : 0);
-        }
-    h->packed_w_n = sw.size(); h->packed_b_n = 0;
-    h->rn_dyn_split = (int)sp[MZ_NET_DYN].size();     // the reward head: the dynamics layers of chain 2
-    for (size_t i = 0; i < sp[MZ_NET_DYN].size(); ++i)
-        if (sp[MZ_NET_DYN][i].chain == 2) { h->rn_dyn_split = (int)i; break; }
-    {   // learner chain tiles: one sample wide
-        const int ngl = 1;
-        int wl = 0;
-        h->rplan_l.resize(3);
-        for (int n = 0; n < 3; ++n) {
-            int wt = wl;
-            const bool sep = (size_t)rn_plan(h, sp[n], n, ngl, 0, wt, nullptr, true).lds_floats * 4 <= kLdsMax;
-            h->rplan_l[n] = rn_plan(h, sp[n], n, ngl, h->flat_off[n] + (n == 0 ? h->ds_n : 0), wl, nullptr, sep,
-                                    &h->rtab);
-            CK(h->rplan_l[n].n < 0 ? fail(h, "ResNet plan: a k-blocked output buffer") : 0);
-            CK(!rn_ktab_ok(h->rplan_l[n]) ? fail(h, "ResNet learner plan: a k table past LDS offset 32767") : 0);
-            h->rn_lds_l = std::max(h->rn_lds_l, (size_t)h->rplan_l[n].lds_floats * 4);
-        }
-        h->rd_chain = rd_chain_ok(h);
-        h->rp_pred = rp_pred_ok(h);
-    }
-    h->inv_tile.assign(h->nflat, -1);
-    for (size_t i = 0; i < sw.size(); ++i) if (sw[i] >= 0) h->inv_tile[(size_t)sw[i]] = (int)i;
-    h->inv_small.assign(h->nflat, -1);
-    auto al = [&](auto** p, size_t n) -> int { MZ_TRY(h, dalloc(h, p, n)); return 0; };
-    auto al_i = [&](int** p, const std::vector<int>& v) -> int {
-        MZ_TRY(h, dalloc(h, p, v.size()));
-        MZ_TRY(h, hipMemcpy(*p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-        return 0;
-    };
-    CK(al_i(&h->d_srcW, sw));
-    CK(al_i(&h->d_inv_tile, h->inv_tile));
-    CK(al_i(&h->d_inv_small, h->inv_small));
-    CK(al(&h->d_rplan, 3));
-    CK(hipMemcpy(h->d_rplan, h->rplan.data(), 3 * sizeof(RPlan), hipMemcpyHostToDevice) == hipSuccess
-           ? 0 : fail(h, "copy"));
-    if (!h->rtab.empty()) CK(al_i(&h->d_rtab, h->rtab));
-    CK(al(&h->d_rplan_l, 3));
-    CK(hipMemcpy(h->d_rplan_l, h->rplan_l.data(), 3 * sizeof(RPlan), hipMemcpyHostToDevice) == hipSuccess
-           ? 0 : fail(h, "copy"));
-    CK(al(&h->d_flat, h->nflat));
-    CK(al(&h->d_Wp, h->packed_w_n));
-    if (h->rd_chain && h->rp_pred) {                // second image set of mz_runroll_fused_r's ADAM blocks
-        CK(al(&h->d_Wp2, h->packed_w_n));
-        CK(hipMemset(h->d_Wp2, 0, h->packed_w_n * 4) == hipSuccess ? 0 : fail(h, "memset"));
-    }
-    CK(hipMemset(h->d_flat, 0, h->nflat * 4) == hipSuccess ? 0 : fail(h, "memset"));
-    CK(repack(h));
-    CK(al(&h->d_m, h->nflat)); CK(al(&h->d_v, h->nflat)); CK(al(&h->d_grad, h->nflat));
-    CK(hipMemset(h->d_m, 0, h->nflat * 4) == hipSuccess ? 0 : fail(h, "memset"));
-    CK(hipMemset(h->d_v, 0, h->nflat * 4) == hipSuccess ? 0 : fail(h, "memset"));
-    CK(alloc_learner(h));
-    const size_t lmax = std::max(h->rn_lds[0], std::max(h->rn_lds[1], h->rn_lds[2]));
-    CK(hipFuncSetAttribute((const void*)mz_rnet_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                           (int)lmax) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute(rnet)"));
-    CK(rsearch_root_lds(h) > kLdsMax ? fail(h, "ResNet root tile exceeds the LDS") : 0);
-    CK(hipFuncSetAttribute((const void*)mz_rsearch_root, hipFuncAttributeMaxDynamicSharedMemorySize,
-                           (int)rsearch_root_lds(h)) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute(root)"));
-    CK(hipFuncSetAttribute((const void*)mz_rsearch_root32, hipFuncAttributeMaxDynamicSharedMemorySize,
-                           (int)rsearch_root_lds(h)) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute(root32)"));
-    if (h->ds) {
-        CK(hipFuncSetAttribute((const void*)mz_downsample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)h->ds_lds) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute(downsample)"));
-        CK(al(&h->d_dsplan, 1));
-        CK(hipMemcpy(h->d_dsplan, &h->dsplan, sizeof(DsPlan), hipMemcpyHostToDevice) == hipSuccess
-               ? 0 : fail(h, "copy"));
-        CK(al(&h->d_dsout, (size_t)max_games * h->rin_feat));
-    }
-    CK(hipFuncSetAttribute((const void*)mz_runroll_pred, hipFuncAttributeMaxDynamicSharedMemorySize,
-                           (int)lmax) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute(runroll_pred)"));
-    for (const void* k : {(const void*)mz_runroll_pred_n1, (const void*)mz_runroll_chain1})
-        CK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->rn_lds_l) == hipSuccess
-               ? 0 : fail(h, "hipFuncSetAttribute(runroll narrow)"));
-    if (h->rd_chain)
-        CK(hipFuncSetAttribute((const void*)mz_runroll_chain_r, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)rd_chain_lds(h)) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute(runroll_chain_r)"));
-    if (h->rp_pred)
-        CK(hipFuncSetAttribute((const void*)mz_runroll_pred_r, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)rp_pred_lds(h)) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute(runroll_pred_r)"));
-    if (h->rd_chain && h->rp_pred)
-        CK(hipFuncSetAttribute((const void*)mz_runroll_fused_r, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)std::max(rd_chain_lds(h), rp_pred_lds(h))) == hipSuccess
-               ? 0 : fail(h, "hipFuncSetAttribute(runroll_fused_r)"));
-    CK(hipFuncSetAttribute((const void*)mz_rsearch_nets, hipFuncAttributeMaxDynamicSharedMemorySize,
-                           (int)rsearch_nets_lds(h)) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute(nets)"));
-    // search buffers (trees and hidden states in HBM)
-    {
-        const size_t G = (size_t)max_games, S = (size_t)h->S, A = (size_t)h->A, H = (size_t)h->H;
-        h->tree_game_bytes = tree_game_bytes(h->S, h->A);
-        CK(alloc_search_tables(h));
-        // +64: the tree step copies the to_play bytes as dwords (up to 3 bytes past them)
-        CK(al(&h->d_tree, G * h->tree_game_bytes + 64));
-        CK(al(&h->d_hid, G * (S + 1) * H));
-        {
-            const int gw = h->A > 16 ? 32 : 16;
-            const RsTreeLds L = rs_tree_lds(h->S, h->tree_game_bytes, gw);
-            h->rtree_lds = (size_t)L.total <= kLdsMax && !std::getenv("MZ_RTREE_HBM") ? (size_t)L.total : 0;
-            if (h->rtree_lds)
-                CK(hipFuncSetAttribute(gw == 32 ? (const void*)mz_rsearch_tree_lds32 : (const void*)mz_rsearch_tree_lds,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->rtree_lds) == hipSuccess
-                       ? 0 : fail(h, "hipFuncSetAttribute(tree_lds)"));
-        }
-        CK(al(&h->d_rpath, G * 2 * (S + 2))); CK(al(&h->d_rgst, G * RG_INTS));
-        CK(al(&h->d_rcache, G * (S + 1))); CK(al(&h->d_rnN, G * (S + 1)));
-        CK(al(&h->d_rhk, G * (S + 1))); CK(al(&h->d_rov, G)); CK(al(&h->d_rologit, G * A)); CK(al(&h->d_ror, G));
-        CK(al(&h->d_obs, G * h->obs_feat)); CK(al(&h->d_legal, G * A)); CK(al(&h->d_tp, G));
-        CK(al(&h->d_cv, G * A)); CK(al(&h->d_rv, G)); CK(al(&h->d_act, G));
-    }
-    CK(hipStreamSynchronize(h->stream) == hipSuccess ? 0 : fail(h, "sync"));
-#undef CK
-    *out = h;
-    return 0;
-}
 
 // ---- RCCL, loaded on first use (dlopen: libmz has no link dependency on it;
 // RTLD_NOLOAD first so a process that already holds an RCCL — torch's — shares it)
@@ -1621,7 +585,6 @@ int mz_engine_create(const mz_config* conf, const mz_ffhp* hyper, int device, in
     h->lds_tree = search_lds_base(h) + (size_t)MZ_TILE * h->tree_game_bytes <= kLdsMax;
     if (search_lds_bytes(h) > kLdsMax) return bad("LDS budget exceeded (width/num_iters too large)");
     int rc = 0;
-#define CK(x) do { if ((rc = (x)) != 0) { g_create_error = h->err; mz_engine_destroy(h); return rc; } } while (0)
     CK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess ? 0 : fail(h, "hipStreamCreate"));
     CK(build_plans(h));
     CK(build_pack_index(h));
@@ -1721,7 +684,6 @@ int mz_engine_create(const mz_config* conf, const mz_ffhp* hyper, int device, in
                                    (int)search_lds_bytes(h)) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute"));
     }
     CK(hipStreamSynchronize(h->stream) == hipSuccess ? 0 : fail(h, "sync"));
-#undef CK
     *out = h;
     return 0;
 }
@@ -2092,7 +1054,7 @@ int mz_debug_select_stats(mz_handle* h, int G, int32_t* fast, int32_t* walked) {
 }
 
 // ------------------------------------------------------------- learner
-static int ensure_batch(mz_handle* h, int B) {
+int mz::ensure_batch(mz_handle* h, int B) {
     if (B <= h->bcap) return 0;
     const int K = h->conf.num_unroll_steps, A = h->A;
     float** bufs[] = {&h->d_bobs, &h->d_bact, &h->d_btv, &h->d_btr, &h->d_btp, &h->d_bgs, &h->d_pv, &h->d_pp, &h->d_pr};
@@ -2261,7 +1223,6 @@ static int rlearner_grad(mz_handle* h, const mz_batch* b, float* grad_dev, float
 }
 
 static int fc_unroll(mz_handle* h, const mz_batch* b, hipStream_t st, const RpSampleParams* rp);
-static int bp_grad(mz_handle* h, const mz_batch* b, float* grad_dev, float* losses_dev, hipStream_t st);
 static int small_unroll_ti(const mz_handle* h, int B);
 static int small_unroll_params(mz_handle* h, const mz_batch* b, int ti, const RpSampleParams* rp,
                                SmallUnrollParams* Uo);
@@ -2388,590 +1349,6 @@ static int learner_losses(mz_handle* h, const mz_batch* b, float* grad_dev, floa
     return 0;
 }
 
-// ---- corrected-gradient learner (MZ_LEARN_CORRECTED, FC nets; mz_backprop.hip)
-// The unrolled graph of Learning.jl:347-370: representation(obs); K dynamics
-// steps on sa_k = [2h_{k-1} ; a_{k-1}/|A|] (the state head skipped at k = K,
-// whose h_K no prediction reads; the reward heads only with
-// intermediate_rewards); K+1 predictions on h_0, h_0, h_1 .. h_{K-1} (Q10).
-static int build_bp(mz_handle* h) {
-    const int K = h->conf.num_unroll_steps, H = h->H;
-    std::vector<BpApp> apps;
-    std::vector<BpHead> heads;
-    int off = 0;
-    auto tensor = [&](int rows) { int o = off; off += ((rows + 3) & ~3) * 16; return o; };
-    const int obs_t = tensor(h->obs_feat);
-    auto dense = [&](int li, int x) {
-        const LayerSpec& L = h->layers[li];
-        BpApp a{};
-        a.op = BP_DENSE; a.w_off = (int)L.flux_w; a.b_off = (int)L.flux_b; a.in = L.in; a.out = L.out;
-        a.act = L.act; a.x = x; a.y = tensor(L.out); a.step = li;
-        a.bn_off = L.bn ? (int)L.flux_be : -1;                // make_dense's BatchNorm: t kept at z
-        a.z = L.bn ? tensor(L.out) : -1;
-        apps.push_back(a);
-        return a.y;
-    };
-    auto chain = [&](int net, int ch, int x) {
-        for (int li : h->chains[net][ch]) x = dense(li, x);
-        return x;
-    };
-    std::vector<int> hs(K + 1, -1);
-    hs[0] = chain(MZ_NET_REPR, CH_TRUNK, obs_t);                                // :347
-    for (int k = 1; k <= K; ++k) {                                              // :355-362
-        BpApp c{};
-        c.op = BP_CONCAT; c.in = H; c.out = H + h->plane; c.x = hs[k - 1]; c.y = tensor(c.out); c.step = k - 1;
-        c.bn_off = c.z = -1;
-        apps.push_back(c);
-        const int t = chain(MZ_NET_DYN, CH_TRUNK, c.y);
-        if (k < K) hs[k] = chain(MZ_NET_DYN, CH_HEAD1, t);
-        if (h->conf.intermediate_rewards) heads.push_back(BpHead{BP_HEAD_R, chain(MZ_NET_DYN, CH_HEAD2, t), k});
-    }
-    for (int k = 0; k <= K; ++k) {                                              // :351, :356 (Q10)
-        const int t = chain(MZ_NET_PRED, CH_TRUNK, hs[k <= 1 ? 0 : k - 1]);
-        heads.push_back(BpHead{BP_HEAD_V, chain(MZ_NET_PRED, CH_HEAD1, t), k});
-        heads.push_back(BpHead{BP_HEAD_P, chain(MZ_NET_PRED, CH_HEAD2, t), k});
-    }
-    // level schedule of the tile kernel (mz_bp_tile_lv).  Forward: an
-    // application's level is one past its input's producer (the observation:
-    // level 0).  Backward, in reverse application order: one past the latest
-    // consumer of its output (the applications reading it, which accumulate
-    // G[y]), and past every later application accumulating into the same G[x]
-    // (so no two units of a level add into one tensor, and the sequential
-    // kernel's accumulation order holds)
-    const int na = (int)apps.size();
-    std::vector<int> flv(na, 0), blv(na, 0);
-    int nfl = 0, nbl = 0;
-    for (int a = 0; a < na; ++a) {
-        int l = 0;
-        for (int p = 0; p < a; ++p) if (apps[p].y == apps[a].x) l = std::max(l, flv[p] + 1);
-        flv[a] = l; nfl = std::max(nfl, l + 1);
-    }
-    for (int a = na - 1; a >= 0; --a) {
-        int l = 0;
-        for (int c = a + 1; c < na; ++c) {
-            if (apps[c].x == apps[a].y) l = std::max(l, blv[c] + 1);           // consumers of y
-            if (apps[c].x == apps[a].x) l = std::max(l, blv[c] + 1);           // same G[x], earlier in backward
-        }
-        blv[a] = l; nbl = std::max(nbl, l + 1);
-    }
-    // ... then each backward application as late as those constraints allow
-    // (the same level count): ASAP piles every prediction head of the unroll
-    // into the first levels (~70 units on 16 waves, serialised), ahead of the
-    // dynamics chain they do not gate; ALAP spreads them along the chain.
-    // Application c must precede a (a < c) when a produces c's input or adds
-    // into the same G[x] after it.
-    for (int c = 0; c < na; ++c) {
-        int l = nbl - 1;
-        for (int a = 0; a < c; ++a)
-            if (apps[c].x == apps[a].y || apps[c].x == apps[a].x) l = std::min(l, blv[a] - 1);
-        blv[c] = l;
-    }
-    std::vector<int2> fun, bun;
-    std::vector<int> flev, blev;
-    for (int l = 0; l < nfl; ++l) {
-        flev.push_back((int)fun.size());
-        for (int a = 0; a < na; ++a)
-            if (flv[a] == l) {
-                const int nb = apps[a].op == BP_DENSE ? (apps[a].out + 15) / 16 : 1;
-                for (int b = 0; b < nb; ++b) fun.push_back(make_int2(a, b));
-            }
-    }
-    flev.push_back((int)fun.size());
-    for (int l = 0; l < nbl; ++l) {
-        blev.push_back((int)bun.size());
-        for (int a = na - 1; a >= 0; --a)
-            if (blv[a] == l) {
-                const int nb = apps[a].op == BP_DENSE ? (apps[a].in + 15) / 16 : 1;
-                for (int b = 0; b < nb; ++b) bun.push_back(make_int2(a, b));
-            }
-    }
-    blev.push_back((int)bun.size());
-    // mz_bp_tile_lv's LDS tensor cache: slots of the largest tensor.  Forward,
-    // level by level: a tensor read at later levels takes a free slot when it
-    // is produced (its readers read the copy) and frees it after its last
-    // reading level.  Backward: a ∂L/∂x takes a slot at its first contribution
-    // and frees it after its producer's level read it (and wrote it out for
-    // mz_bp_dw).  Everything else stays in the arena: the level that writes it
-    // ends with a barrier that drains the stores (fsync / bsync), as do the
-    // last forward level (the heads and the backward read the arena).
-    std::vector<int> fsync(nfl, 0), bsync(nbl, 0);
-    int cache_floats = 0, obs_s = -1;
-    for (BpApp& a : apps) { a.xs = a.ys = a.gys = a.gxs = -1; a.gxf = 0; }
-#if BP_LV_SIMPLE && !BP_LV_PREFETCH
-    {
-        auto rows16 = [](int r) { return ((r + 3) & ~3) * 16; };
-        int slot = rows16(h->obs_feat);
-        for (const BpApp& a : apps) slot = std::max(slot, rows16(a.out));
-        const size_t sched = (size_t)na * sizeof(BpApp) + (fun.size() + bun.size()) * sizeof(int2) +
-                             (size_t)(2 * (nfl + nbl) + 8) * sizeof(int);
-        // (a schedule that leaves no room for the cache runs without it, not with a wrapped count)
-        const int nslot = sched + 64 < kLdsMax
-                              ? (int)std::min<size_t>(64, (kLdsMax - sched - 64) / ((size_t)slot * 4)) : 0;
-        cache_floats = nslot * slot;
-        std::vector<int> free_s;
-        for (int i = nslot - 1; i >= 0; --i) free_s.push_back(i * slot);
-        // forward
-        std::map<int, int> last_read, fslot;                 // tensor -> last reading level, -> slot
-        for (int a = 0; a < na; ++a) last_read[apps[a].x] = std::max(last_read.count(apps[a].x) ? last_read[apps[a].x] : -1, flv[a]);
-        auto take = [&](int t) {
-            if (!last_read.count(t) || free_s.empty()) return -1;
-            const int o = free_s.back(); free_s.pop_back();
-            fslot[t] = o;
-            return o;
-        };
-        obs_s = take(obs_t);
-        for (int l = 0; l < nfl; ++l) {
-            for (auto it = fslot.begin(); it != fslot.end();) {
-                if (last_read[it->first] < l) { free_s.push_back(it->second); it = fslot.erase(it); }
-                else ++it;
-            }
-            for (int a = 0; a < na; ++a)
-                if (flv[a] == l) { auto f = fslot.find(apps[a].x); apps[a].xs = f != fslot.end() ? f->second : -1; }
-            for (int a = 0; a < na; ++a)
-                if (flv[a] == l) {
-                    apps[a].ys = take(apps[a].y);
-                    if (apps[a].ys < 0 && last_read.count(apps[a].y)) fsync[l] = 1;
-                }
-        }
-        fsync[nfl - 1] = 1;
-        // backward
-        free_s.clear();
-        for (int i = nslot - 1; i >= 0; --i) free_s.push_back(i * slot);
-        std::map<int, int> producer, where, gslot;            // tensor -> app, -> slot or -1 (decided), live slots
-        for (int a = 0; a < na; ++a) producer[apps[a].y] = a;
-        for (const BpHead& hd : heads) where[hd.y] = -1;      // bp_heads writes these to the arena
-        for (int l = 0; l < nbl; ++l) {
-            for (auto it = gslot.begin(); it != gslot.end();) {
-                if (blv[producer[it->first]] < l) { free_s.push_back(it->second); it = gslot.erase(it); }
-                else ++it;
-            }
-            for (int a = 0; a < na; ++a) {
-                if (blv[a] != l) continue;
-                auto g = gslot.find(apps[a].y);
-                apps[a].gys = g != gslot.end() ? g->second : -1;
-            }
-            for (int a = 0; a < na; ++a) {
-                if (blv[a] != l) continue;
-                const int t = apps[a].x;
-                auto w = where.find(t);
-                if (w == where.end()) {
-                    int o = -1;
-                    if (producer.count(t) && !free_s.empty()) {
-                        o = free_s.back(); free_s.pop_back();
-                        gslot[t] = o;
-                        apps[a].gxf = 1;
-                    }
-                    where[t] = o;
-                    apps[a].gxs = o;
-                } else {
-                    apps[a].gxs = w->second;
-                }
-                if (apps[a].gxs < 0) bsync[l] = 1;
-            }
-        }
-    }
-#endif
-    // dW: every layer's applications, one wave per 16x16 block (+ one per bias block)
-    std::vector<BpLayer> layers(h->layers.size());
-    std::vector<BpUse> uses;
-    std::vector<BpJob> jobs;
-    for (int n = 0; n < 4; ++n) h->bp_job0[n] = -1;
-    for (size_t li = 0; li < h->layers.size(); ++li) {
-        const LayerSpec& L = h->layers[li];
-        if (h->bp_job0[L.net] < 0) h->bp_job0[L.net] = (int)jobs.size();   // layers are in net order
-        BpLayer& bl = layers[li];
-        bl.w_off = (int)L.flux_w; bl.b_off = (int)L.flux_b; bl.in = L.in; bl.out = L.out; bl.act = L.act;
-        bl.bn_off = L.bn ? (int)L.flux_be : -1;
-        bl.use0 = (int)uses.size();
-        for (const BpApp& a : apps) if (a.op == BP_DENSE && a.step == (int)li) uses.push_back(BpUse{a.x, a.y, a.z});
-        bl.n_use = (int)uses.size() - bl.use0;
-        for (int ob = 0; ob < (L.out + 15) / 16; ++ob) {
-            for (int ib = 0; ib < (L.in + 15) / 16; ++ib) jobs.push_back(BpJob{(int)li, ob, ib});
-            jobs.push_back(BpJob{(int)li, ob, -1});
-        }
-    }
-    auto up = [&](auto** d, const auto& v) -> int {
-        MZ_TRY(h, dalloc(h, d, v.size()));
-        MZ_TRY(h, hipMemcpy(*d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-        return 0;
-    };
-    if (up(&h->d_bp_apps, apps) || up(&h->d_bp_heads, heads) || up(&h->d_bp_layers, layers) ||
-        up(&h->d_bp_uses, uses) || up(&h->d_bp_jobs, jobs) || up(&h->d_bp_funits, fun) ||
-        up(&h->d_bp_flev, flev) || up(&h->d_bp_bunits, bun) || up(&h->d_bp_blev, blev) ||
-        up(&h->d_bp_fsync, fsync) || up(&h->d_bp_bsync, bsync))
-        return -1;
-    h->bp_cache_floats = cache_floats; h->bp_obs_s = obs_s;
-    {
-        const size_t lv = (size_t)na * sizeof(BpApp) + (fun.size() + bun.size()) * sizeof(int2) +
-                          (size_t)(2 * (nfl + nbl) + 8) * sizeof(int) + 16 + (size_t)cache_floats * 4;
-        if (lv > kLdsMax) return fail(h, "corrected learner: the level schedule exceeds the LDS");
-        MZ_TRY(h, hipFuncSetAttribute((const void*)mz_bp_tile_lv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lv));
-        MZ_TRY(h, hipFuncSetAttribute((const void*)mz_bp_tile_lv_nobn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lv));
-    }
-    h->bp_n_flev = nfl; h->bp_n_blev = nbl; h->bp_n_funit = (int)fun.size(); h->bp_n_bunit = (int)bun.size();
-    h->bp_n_app = (int)apps.size(); h->bp_n_head = (int)heads.size(); h->bp_n_job = (int)jobs.size();
-    h->bp_job0[3] = (int)jobs.size();
-    for (int n = 2; n >= 0; --n) if (h->bp_job0[n] < 0) h->bp_job0[n] = h->bp_job0[n + 1];
-    MZ_TRY(h, dalloc(h, &h->d_bp_sq, jobs.size()));
-    h->bp_tile_floats = off; h->bp_obs_t = obs_t;
-    h->bp_built = true;
-    return 0;
-}
-
-// ---- the corrected learner for the ResNet nets (mz_backprop.hip mz_rbp_*):
-// the same unrolled graph as build_bp, on the layers of rn_specs (convs with
-// BatchNorm and residual blocks, the heads' 1x1 convs, Dense layers), one
-// arena per sample: conv tensors [channel][position], dense vectors.
-static int build_rbp(mz_handle* h) {
-    const int K = h->conf.num_unroll_steps, P = h->plane, H = h->H;
-    std::vector<RbpApp> apps;
-    std::vector<BpHead> heads;
-    int off = 0, dtf = 0, xsf = 0, max_units = 1;
-    auto tensor = [&](int n) { int o = off; off += (n + 3) & ~3; return o; };
-    const int obs_t = tensor(h->rin_feat);
-    std::vector<RSpec> sp[3];
-    size_t np[3];
-    for (int n = 0; n < 3; ++n) sp[n] = rn_specs(h->rconf, h->rhp, n, &np[n]);
-    // one RbpLayer per spec (nets in order) and its applications
-    int lbase[3], nl = 0;
-    for (int n = 0; n < 3; ++n) { lbase[n] = nl; nl += (int)sp[n].size(); }
-    std::vector<std::vector<RbpUse>> luse(nl);
-    const int npb = (P + 15) / 16;
-    // the representation's tail follows the downsampler's parameters in net 0
-    auto fo = [&](int net) { return h->flat_off[net] + (net == MZ_NET_REPR && h->ds ? h->ds_n : 0); };
-    auto chain = [&](int net, int ch, int x, bool first_obs) {
-        int saved = -1;
-        for (size_t si = 0; si < sp[net].size(); ++si) {
-            const RSpec& r = sp[net][si];
-            if (r.chain != ch) continue;
-            RbpApp a{};
-            a.op = r.conv ? RBP_CONV : RBP_DENSE;
-            a.w_off = (int)(fo(net) + r.woff); a.b_off = (int)(fo(net) + r.boff);
-            a.bn_off = r.conv && r.bn ? (int)(fo(net) + r.bnoff) : -1;
-            a.cin = r.cin; a.cout = r.cout; a.kw = r.kw; a.kh = r.kh; a.act = r.act;
-            a.x = x; a.y = tensor(r.conv ? r.cout * P : r.cout);
-            a.z = a.bn_off >= 0 ? tensor(r.cout * P) : -1;
-            a.res = r.res_add ? saved : -1;
-            if (r.res_save) saved = x;
-            a.step = first_obs ? 1 : 0;
-            first_obs = false;
-            dtf = std::max(dtf, r.conv ? r.cout * P : r.cout);
-            xsf = std::max(xsf, r.conv ? r.cin * P : r.cin);             // the staged input
-            if (r.conv && r.kw * r.kh > 1) {                                // padded (mz_backprop.hip rbp_taps)
-                const int Wb = h->rconf.observation_shape[0], Pp = (P / Wb + r.kh - 1) * (Wb + r.kw - 1);
-                xsf = std::max(xsf, r.cin * Pp);
-                dtf = std::max(dtf, r.cout * Pp);
-            }
-            if (r.conv) {
-                max_units = std::max(max_units, std::max((r.cout + 15) / 16, (r.cin + 15) / 16) * npb);
-            }
-            apps.push_back(a);
-            luse[lbase[net] + (int)si].push_back(RbpUse{a.x, a.y, a.z});
-            x = a.y;
-        }
-        return x;
-    };
-    std::vector<int> hs(K + 1, -1);
-    // :347; with the downsampler the first conv also produces ∂L/∂(its input) for mz_dsbp_bwd
-    hs[0] = chain(MZ_NET_REPR, 0, obs_t, !h->ds);
-    for (int k = 1; k <= K; ++k) {                                              // :355-362
-        RbpApp c{};
-        c.op = RBP_CONCAT; c.cin = H; c.cout = H + P; c.x = hs[k - 1]; c.y = tensor(c.cout); c.step = k - 1;
-        c.bn_off = -1; c.z = -1; c.res = -1;
-        dtf = std::max(dtf, c.cout);                                            // a ring slot holds it too
-        apps.push_back(c);
-        const int t = chain(MZ_NET_DYN, 0, c.y, false);
-        if (k < K) hs[k] = chain(MZ_NET_DYN, 1, t, false);
-        if (h->conf.intermediate_rewards) heads.push_back(BpHead{BP_HEAD_R, chain(MZ_NET_DYN, 2, t, false), k});
-    }
-    for (int k = 0; k <= K; ++k) {                                              // :351, :356 (Q10)
-        const int t = chain(MZ_NET_PRED, 0, hs[k <= 1 ? 0 : k - 1], false);
-        heads.push_back(BpHead{BP_HEAD_V, chain(MZ_NET_PRED, 1, t, false), k});
-        heads.push_back(BpHead{BP_HEAD_P, chain(MZ_NET_PRED, 2, t, false), k});
-    }
-    // mz_rbp_sample's forward LDS ring: application a's output also goes to slot
-    // a mod ns; an input or residual produced fewer than ns applications earlier
-    // is read there, anything else from the arena, after a barrier that drained
-    // the arena stores (fsync on the application before; the backward and the
-    // heads read the arena too)
-    const int ysz = (dtf + 3) & ~3, xsz = (xsf + 3) & ~3;
-    int ns = 4;
-    while (ns > 0 && (size_t)(ysz + xsz + ns * ysz) * 4 > kLdsMax) --ns;
-    {
-        std::map<int, int> producer;
-        for (int a = 0; a < (int)apps.size(); ++a) {
-            RbpApp& A_ = apps[a];
-            auto slot = [&](int t) {
-                auto it = producer.find(t);
-                return it != producer.end() && a - it->second < ns ? it->second % ns : -1;
-            };
-            A_.xb = slot(A_.x);
-            A_.rb = A_.res >= 0 ? slot(A_.res) : -1;
-            A_.yb = ns > 0 ? a % ns : -1;
-            A_.fsync = 0;
-            if ((A_.xb < 0 || (A_.res >= 0 && A_.rb < 0)) && a > 0) apps[a - 1].fsync = 1;
-            producer[A_.y] = a;
-        }
-        apps.back().fsync = 1;
-    }
-    // the backward ring (the same slots): in backward order, a tensor's ∂L/∂·
-    // takes a free slot at its first contribution when its producer follows
-    // within kGLife applications, and frees it when the producer has read it;
-    // otherwise it accumulates in the arena (zeroed first, bsync after each
-    // contribution).  The accumulation order is the arena's.
-    std::vector<int2> gz;
-    {
-        const int kGLife = 6;
-        std::map<int, int> producer, size_of;
-        for (int a = 0; a < (int)apps.size(); ++a) {
-            producer[apps[a].y] = a;
-            size_of[apps[a].y] = apps[a].op == RBP_CONV ? apps[a].cout * P : apps[a].cout;
-        }
-        std::map<int, int> slot_of;          // tensor -> slot (ring-resident, live)
-        std::map<int, int> where;            // tensor -> slot or -1 (decided at the first contribution)
-        std::vector<int> free_slots;
-        for (int i = ns - 1; i >= 0; --i) free_slots.push_back(i);
-        for (int a = (int)apps.size() - 1; a >= 0; --a) {
-            RbpApp& A_ = apps[a];
-            A_.gyb = A_.gxb = A_.grb = -1; A_.gxf = A_.grf = 0; A_.bsync = 0;
-            auto it = slot_of.find(A_.y);
-            if (it != slot_of.end()) A_.gyb = it->second;
-            auto contribute = [&](int t, int& sb, int& first) {
-                auto w = where.find(t);
-                if (w == where.end()) {
-                    auto pr = producer.find(t);
-                    int sl = -1;
-                    if (pr != producer.end() && a - pr->second <= kGLife && !free_slots.empty()) {
-                        sl = free_slots.back(); free_slots.pop_back();
-                        slot_of[t] = sl;
-                        first = 1;
-                    }
-                    where[t] = sl;
-                    sb = sl;
-                } else {
-                    sb = w->second;
-                }
-                if (sb < 0) A_.bsync = 1;
-            };
-            const bool dx = A_.op == RBP_CONCAT || !A_.step;
-            if (dx) contribute(A_.x, A_.gxb, A_.gxf);
-            if (A_.op == RBP_CONV && A_.res >= 0) contribute(A_.res, A_.grb, A_.grf);
-            if (A_.gyb >= 0) { free_slots.push_back(A_.gyb); slot_of.erase(A_.y); }
-        }
-        for (const auto& t : size_of)
-            if (where.find(t.first) == where.end() || where[t.first] < 0) gz.push_back(make_int2(t.first, t.second));
-        if (h->ds) gz.push_back(make_int2(obs_t, h->rin_feat));
-    }
-    h->rbp_ring = ns;
-    // mz_rbp_dw's jobs, net by net (mz_bp_fold sums each net's Σθ² over its job range):
-    // per layer its W blocks, then its bias (BatchNorm) blocks; every parameter once
-    std::vector<RbpLayer> layers(nl);
-    std::vector<RbpUse> uses;
-    std::vector<RbpJob> jobs;
-    std::vector<char> covered(h->nflat, 0);
-    for (int n = 0; n < 3; ++n) {
-        h->rbp_job0[n] = (int)jobs.size();
-        for (size_t si = 0; si < sp[n].size(); ++si) {
-            const RSpec& r = sp[n][si];
-            const int li = lbase[n] + (int)si;
-            RbpLayer& L = layers[li];
-            L.conv = r.conv; L.w_off = (int)(fo(n) + r.woff); L.b_off = (int)(fo(n) + r.boff);
-            L.bn_off = r.conv && r.bn ? (int)(fo(n) + r.bnoff) : -1;
-            L.cin = r.cin; L.cout = r.cout; L.kw = r.kw; L.kh = r.kh; L.act = r.act;
-            L.use0 = (int)uses.size(); L.n_use = (int)luse[li].size();
-            for (const RbpUse& u : luse[li]) uses.push_back(u);
-            const int Kw = r.conv ? r.kw * r.kh * r.cin : r.cin;
-            for (int ob = 0; ob < (r.cout + 15) / 16; ++ob)
-                for (int kb = 0; kb < (Kw + 15) / 16; ++kb) jobs.push_back(RbpJob{li, ob, kb});
-            for (int ob = 0; ob < (r.cout + 15) / 16; ++ob) jobs.push_back(RbpJob{li, ob, -1});
-            const size_t nw = (size_t)Kw * r.cout, nb = (size_t)r.cout * (L.bn_off >= 0 ? 3 : 1);
-            for (size_t i = 0; i < nw; ++i) covered[(size_t)L.w_off + i] = 1;
-            for (int o = 0; o < r.cout; ++o) covered[(size_t)L.b_off + o] = 1;
-            if (L.bn_off >= 0) for (size_t i = 0; i < (size_t)2 * r.cout; ++i) covered[(size_t)L.bn_off + i] = 1;
-            (void)nb;
-        }
-    }
-    h->rbp_job0[3] = (int)jobs.size();
-    // the downsampler (mz_dsbp_*): arena tensors per layer, one dW job per conv output channel
-    std::vector<DsBpLayer> dlay;
-    std::vector<DsDwJob> djobs;
-    if (h->ds) {
-        const DsPlan& D = h->dsplan;
-        int o = 0, maxdt = 0;
-        auto t = [&](int n) { const int r = o; o += (n + 3) & ~3; return r; };
-        dlay.resize(D.n);
-        for (int i = 0; i < D.n; ++i) {
-            const DsLayer& L = D.L[i];
-            const int n = L.cout * L.Wo * L.Ho;
-            dlay[i].x = i == 0 ? -1 : dlay[i - 1].y;
-            dlay[i].y = t(n);
-            dlay[i].z = L.kind == DS_CONV && L.bn ? t(n) : -1;
-            dlay[i].res = L.res_add ? dlay[i - 1].x : -1;
-            if (L.kind != DS_CONV) continue;
-            maxdt = std::max(maxdt, n);
-            const int K = L.kw * L.kh * L.cin;
-            if (L.kw * L.kh + 3 > DS_DW_THREADS) return fail(h, "corrected learner: a downsampler conv has too many taps");
-            for (int co = 0; co < L.cout; ++co)
-                for (int ci = 0; ci < L.cin; ++ci) djobs.push_back(DsDwJob{i, co, ci});
-            for (int e = 0; e < K * L.cout; ++e) covered[(size_t)L.woff + e] = 1;
-            for (int co = 0; co < L.cout; ++co) covered[(size_t)L.boff + co] = 1;
-            if (L.bn) for (int e = 0; e < 2 * L.cout; ++e) covered[(size_t)L.bnoff + e] = 1;
-        }
-        h->dsbp_dt = o;
-        h->dsbp_arena = o + ((maxdt + 3) & ~3);
-        h->dsbp_n_job = (int)djobs.size();
-    }
-    for (size_t i = 0; i < h->nflat; ++i)
-        if (!covered[i]) return fail(h, "corrected learner: a parameter no gradient job covers");
-    auto up = [&](auto** d, const auto& v) -> int {
-        MZ_TRY(h, dalloc(h, d, v.size()));
-        MZ_TRY(h, hipMemcpy(*d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-        return 0;
-    };
-    if (up(&h->d_rbp_apps, apps) || up(&h->d_rbp_heads, heads) || up(&h->d_rbp_layers, layers) ||
-        up(&h->d_rbp_uses, uses) || up(&h->d_rbp_jobs, jobs) || up(&h->d_rbp_gzero, gz))
-        return -1;
-    if (h->ds && (up(&h->d_dsbp_lay, dlay) || up(&h->d_dsbp_jobs, djobs))) return -1;
-    h->rbp_n_gzero = (int)gz.size();
-    // Σθ² per job: the downsampler's jobs first (net 0), then mz_rbp_dw's
-    MZ_TRY(h, dalloc(h, &h->d_rbp_sq, jobs.size() + djobs.size()));
-    h->rbp_n_app = (int)apps.size(); h->rbp_n_head = (int)heads.size(); h->rbp_n_job = (int)jobs.size();
-    h->rbp_arena = off; h->rbp_obs_t = obs_t; h->rbp_dt = (dtf + 3) & ~3; h->rbp_xs = (xsf + 3) & ~3;
-    // a wave per 16x16 conv block of a pass (mz_rbp_sample), 4 to 12 waves
-    h->rbp_threads = 64 * std::min(12, std::max(4, max_units));
-    const size_t lds = (size_t)(h->rbp_dt * (1 + h->rbp_ring) + h->rbp_xs) * 4;
-    if (lds > kLdsMax) return fail(h, "corrected learner: a conv's tensors exceed the LDS");
-    // above the 64 KB default (e.g. 256 filters on the 6x7 board: ~86 KB)
-    MZ_TRY(h, hipFuncSetAttribute((const void*)mz_rbp_sample, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    h->rbp_built = true;
-    return 0;
-}
-
-static int rbp_grad(mz_handle* h, const mz_batch* b, float* grad_dev, float* losses_dev, hipStream_t st) {
-    const int B = b->batch_size, K = h->conf.num_unroll_steps;
-    if (!h->rbp_built && build_rbp(h)) return -1;
-    if (ensure_batch(h, B)) return -1;
-    if (B > h->rbp_cap) {
-        MZ_TRY(h, dalloc(h, &h->d_rbp_act, (size_t)B * h->rbp_arena));
-        MZ_TRY(h, dalloc(h, &h->d_rbp_grad, (size_t)B * h->rbp_arena));
-        MZ_TRY(h, dalloc(h, &h->d_rbp_terms, (size_t)B * (K + 1) * 3));
-        h->rbp_cap = B;
-    }
-    if (h->ds && B > h->dsbp_cap) {
-        MZ_TRY(h, dalloc(h, &h->d_dsbp_act, (size_t)B * h->dsbp_arena));
-        MZ_TRY(h, dalloc(h, &h->d_dsbp_grad, (size_t)B * h->dsbp_arena));
-        h->dsbp_cap = B;
-    }
-    DsBpParams DP;
-    if (h->ds) {                                  // the downsampler's forward, its output the tail's input
-        if (ensure_dsb(h, B)) return -1;
-        DP.B = B; DP.arena = h->dsbp_arena; DP.bn_s = h->bn_s; DP.plan = h->d_dsplan; DP.lay = h->d_dsbp_lay;
-        DP.flat = h->d_flat; DP.obs = b->observation; DP.act = h->d_dsbp_act; DP.grad = h->d_dsbp_grad;
-        DP.out = h->d_dsb; DP.gout = h->d_rbp_grad; DP.gstride = h->rbp_arena; DP.goff = h->rbp_obs_t;
-        DP.dt_off = h->dsbp_dt;
-        hipLaunchKernelGGL(mz_dsbp_fwd, dim3(B), dim3(DS_THREADS), 0, st, DP);
-    }
-    if ((size_t)B * (size_t)std::max(1, K + 1) * (size_t)h->plane >= (1u << 20))
-        return fail(h, "corrected learner: batch x unroll x board too large for the dW index");
-    RbpParams Q;
-    Q.B = B; Q.K = K; Q.A = h->A; Q.H = h->H; Q.P = h->plane; Q.Wb = h->rconf.observation_shape[0];
-    Q.obs_feat = h->rin_feat; Q.arena = h->rbp_arena; Q.n_app = h->rbp_n_app; Q.n_head = h->rbp_n_head;
-    Q.obs_t = h->rbp_obs_t; Q.intermediate_rewards = h->conf.intermediate_rewards; Q.nflat = (int)h->nflat;
-    Q.dt_floats = h->rbp_dt; Q.xs_floats = h->rbp_xs; Q.gzero = h->d_rbp_gzero; Q.n_gzero = h->rbp_n_gzero;
-    Q.apps = h->d_rbp_apps; Q.heads = h->d_rbp_heads;
-    Q.act = h->d_rbp_act; Q.grad = h->d_rbp_grad; Q.flat = h->d_flat;
-    Q.obs = h->ds ? h->d_dsb : b->observation; Q.actions = b->actions; Q.tv = b->target_values;
-    Q.tr = b->target_rewards;
-    Q.tp = b->target_policies; Q.gscale = b->gradient_scale; Q.weights = b->weights; Q.terms = h->d_rbp_terms;
-    Q.pv = h->d_pv; Q.pp = h->d_pp; Q.pr = h->d_pr;
-    Q.stamps = nullptr;
-#ifdef MZ_STAMPS
-    if (!h->d_stamps) MZ_TRY(h, dalloc(h, &h->d_stamps, (size_t)8 * std::max(h->max_games, 128)));
-    Q.stamps = h->d_stamps;
-#endif
-    hipLaunchKernelGGL(mz_rbp_sample, dim3(B), dim3(h->rbp_threads),
-                       (size_t)(h->rbp_dt * (1 + h->rbp_ring) + h->rbp_xs) * 4, st, Q);
-    const int nds = h->ds ? h->dsbp_n_job : 0;
-    if (h->ds) {                                  // ∂L/∂(downsampler output) is the arena's obs tensor
-        hipLaunchKernelGGL(mz_dsbp_bwd, dim3(B), dim3(DS_THREADS), 0, st, DP);
-        DsDwParams DW;
-        DW.B = B; DW.arena = h->dsbp_arena; DW.n_job = nds; DW.bn_s = h->bn_s; DW.plan = h->d_dsplan;
-        DW.lay = h->d_dsbp_lay; DW.jobs = h->d_dsbp_jobs; DW.obs = b->observation; DW.act = h->d_dsbp_act;
-        DW.grad = h->d_dsbp_grad; DW.flat = h->d_flat; DW.out = grad_dev ? grad_dev : h->d_grad; DW.sq = h->d_rbp_sq;
-        hipLaunchKernelGGL(mz_dsbp_dw, dim3(nds), dim3(DS_DW_THREADS), 0, st, DW);
-    }
-    RbpDwParams D;
-    D.B = B; D.P = h->plane; D.Wb = h->rconf.observation_shape[0]; D.arena = h->rbp_arena;
-    D.jobs = h->d_rbp_jobs; D.layers = h->d_rbp_layers; D.uses = h->d_rbp_uses;
-    D.act = h->d_rbp_act; D.grad = h->d_rbp_grad; D.flat = h->d_flat;
-    D.out = grad_dev ? grad_dev : h->d_grad; D.sq = h->d_rbp_sq + nds;
-    hipLaunchKernelGGL(mz_rbp_dw, dim3(h->rbp_n_job), dim3(64 * RBP_DW_WAVES), 0, st, D);
-    BpFoldParams F;
-    F.B = B; F.K = K; F.terms = h->d_rbp_terms; F.gscale = b->gradient_scale; F.weights = b->weights;
-    F.flat = h->d_flat; F.netoff = h->d_netoff; F.losses = losses_dev ? losses_dev : h->d_loss;
-    F.sq = h->d_rbp_sq;
-    for (int n = 0; n < 4; ++n) F.job0[n] = n == 0 ? 0 : h->rbp_job0[n] + nds;
-    hipLaunchKernelGGL(mz_bp_fold, dim3(4), dim3(256), 0, st, F);
-    MZ_TRY(h, hipGetLastError());
-    h->last_lvariant = h->ds ? "mz_dsbp+mz_rbp_sample+mz_rbp_dw" : "mz_rbp_sample+mz_rbp_dw";
-    return 0;
-}
-
-// corrected step: gradient (data term + 2θ) into grad_dev, losses, read-outs
-static int bp_grad(mz_handle* h, const mz_batch* b, float* grad_dev, float* losses_dev, hipStream_t st) {
-    if (h->kind == 1) return rbp_grad(h, b, grad_dev, losses_dev, st);
-    const int B = b->batch_size, K = h->conf.num_unroll_steps;
-    if (!h->bp_built && build_bp(h)) return -1;
-    if (ensure_batch(h, B)) return -1;
-    const int tiles = (B + 15) / 16;
-    if (tiles > h->bp_tiles_cap) {
-        MZ_TRY(h, dalloc(h, &h->d_bp_act, (size_t)tiles * h->bp_tile_floats));
-        MZ_TRY(h, dalloc(h, &h->d_bp_grad, (size_t)tiles * h->bp_tile_floats));
-        MZ_TRY(h, dalloc(h, &h->d_bp_terms, (size_t)tiles * 16 * (K + 1) * 3));
-        h->bp_tiles_cap = tiles;
-    }
-    BpParams Q;
-    Q.B = B; Q.K = K; Q.A = h->A; Q.H = h->H; Q.plane = h->plane; Q.obs_feat = h->obs_feat;
-    Q.tile_floats = h->bp_tile_floats; Q.n_app = h->bp_n_app; Q.n_head = h->bp_n_head; Q.obs_t = h->bp_obs_t;
-    Q.intermediate_rewards = h->conf.intermediate_rewards;
-    Q.apps = h->d_bp_apps; Q.heads = h->d_bp_heads; Q.act = h->d_bp_act; Q.grad = h->d_bp_grad; Q.flat = h->d_flat;
-    Q.obs = b->observation; Q.actions = b->actions; Q.tv = b->target_values; Q.tr = b->target_rewards;
-    Q.tp = b->target_policies; Q.gscale = b->gradient_scale; Q.weights = b->weights; Q.terms = h->d_bp_terms;
-    Q.pv = h->d_pv; Q.pp = h->d_pp; Q.pr = h->d_pr;
-    Q.n_flev = h->bp_n_flev; Q.n_blev = h->bp_n_blev; Q.n_funit = h->bp_n_funit; Q.n_bunit = h->bp_n_bunit;
-    Q.fsync = h->d_bp_fsync; Q.bsync = h->d_bp_bsync; Q.cache_floats = h->bp_cache_floats; Q.obs_s = h->bp_obs_s;
-    Q.nflat = (int)h->nflat;
-    const size_t lv_lds = (size_t)Q.n_app * sizeof(BpApp) + (size_t)(Q.n_funit + Q.n_bunit) * sizeof(int2) +
-                          (size_t)(2 * (Q.n_flev + Q.n_blev) + 8) * sizeof(int) + 16 + (size_t)Q.cache_floats * 4;
-    Q.funits = h->d_bp_funits; Q.flev = h->d_bp_flev; Q.bunits = h->d_bp_bunits; Q.blev = h->d_bp_blev;
-    Q.stamps = nullptr;
-#ifdef MZ_STAMPS
-    if (!h->d_stamps) MZ_TRY(h, dalloc(h, &h->d_stamps, (size_t)8 * std::max(h->max_games, 128)));
-    Q.stamps = h->d_stamps;
-#endif
-    // the level schedule (default) or the one-application-per-barrier kernel
-    // (MZ_BP_SEQ=1, the same bits: tests/test_corrected_learner_gpu.py)
-    if (std::getenv("MZ_BP_SEQ")) hipLaunchKernelGGL(mz_bp_tile, dim3(tiles), dim3(256), 0, st, Q);
-    else if (lv_lds <= kLdsMax)                   // (no BatchNorm layer: the kernel without its per-layer test)
-        hipLaunchKernelGGL(h->hp.use_batch_norm ? mz_bp_tile_lv : mz_bp_tile_lv_nobn, dim3(tiles), dim3(BP_LV_THREADS),
-                           lv_lds, st, Q);
-    else return fail(h, "corrected learner: the level schedule exceeds the LDS");
-    BpDwParams D;
-    D.tiles = tiles; D.tile_floats = h->bp_tile_floats; D.n_job = h->bp_n_job; D.jobs = h->d_bp_jobs;
-    D.layers = h->d_bp_layers; D.uses = h->d_bp_uses; D.act = h->d_bp_act; D.grad = h->d_bp_grad; D.flat = h->d_flat;
-    D.out = grad_dev ? grad_dev : h->d_grad;
-    D.sq = h->d_bp_sq;
-    hipLaunchKernelGGL(mz_bp_dw, dim3(h->bp_n_job), dim3(64), 0, st, D);
-    BpFoldParams F;
-    F.B = B; F.K = K; F.terms = h->d_bp_terms; F.gscale = b->gradient_scale; F.weights = b->weights;
-    F.flat = h->d_flat; F.netoff = h->d_netoff; F.losses = losses_dev ? losses_dev : h->d_loss;
-    F.sq = h->d_bp_sq;
-    for (int n = 0; n < 4; ++n) F.job0[n] = h->bp_job0[n];
-    hipLaunchKernelGGL(mz_bp_fold, dim3(4), dim3(256), 0, st, F);
-    MZ_TRY(h, hipGetLastError());
-    return 0;
-}
-
 int mz_learner_set_mode(mz_handle* h, int mode) {
     if (!h) return -2;
     if (mode != MZ_LEARN_REF_SEMANTICS && mode != MZ_LEARN_CORRECTED) return fail(h, "unknown learner mode");
@@ -3060,7 +1437,7 @@ int mz_debug_unroll(mz_handle* h, int B, float* values, float* policies, float* 
 }
 
 // Diagnostic: per-workgroup phase cycles of the last search (stamp build only).
-int mz_debug_stamps(mz_handle* h, unsigned long long* out, int n_blocks) {
+extern "C" int mz_debug_stamps(mz_handle* h, unsigned long long* out, int n_blocks) {
     if (!h) return -2;
 #ifdef MZ_STAMPS
     if (!h->d_stamps) return fail(h, "no stamps recorded");
@@ -3085,9 +1462,6 @@ const char* mz_learner_variant(const mz_handle* h) {
 
 int mz_resnet_tile_games(const mz_handle* h) { return h && h->kind == 1 ? h->rn_ng : 0; }
 int mz_downsample_staged(const mz_handle* h) { return h && h->kind == 1 && h->ds ? h->dsplan.stage_in : -1; }
-
-// ------------------------------------------------ device self-play + replay
-}  // extern "C"
 
 // ------------------------------------------------ checkpoint interface (mz_ckpt_iface.h)
 static const char* kNetNames[3] = {"representation", "prediction", "dynamics"};
@@ -3195,16 +1569,6 @@ std::string mz_describe(const mz_handle* h) {
 
 int mz_set_error(mz_handle* h, const std::string& msg) { return fail(h, msg); }
 
-template <typename T>
-static hipError_t spalloc(mz_handle* h, T** p, size_t n, bool zero = true) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T) + 16);
-    if (e == hipSuccess) {
-        h->sp_allocs.push_back(*p);
-        if (zero) e = hipMemset(*p, 0, n * sizeof(T) + 16);
-    }
-    return e;
-}
-
 static int sp_alloc_hist(mz_handle* h, SpHist& r, size_t n) {
     const size_t T = (size_t)h->sp_T, A = (size_t)h->A;
     MZ_TRY(h, spalloc(h, &r.obs, n * T * h->sp_osz));
@@ -3221,7 +1585,7 @@ static int sp_alloc_hist(mz_handle* h, SpHist& r, size_t n) {
 
 // `test`: the rows are the test worker's slots (h->ts) in evaluation mode with mz_test_config's
 // opponent; the shard, the counters and the tally are not theirs (null: no launch of theirs reads them)
-static SpParams sp_params(mz_handle* h, bool test = false) {
+SpParams mz::sp_params(mz_handle* h, bool test) {
     SpParams S;
     std::memset(&S, 0, sizeof(S));
     const mz_config& c = h->conf;
@@ -3351,8 +1715,6 @@ static void mcts_launch(const SpParams& S, int sims, int rollouts, const double*
     hipLaunchKernelGGL(mz_mcts_move, dim3((S.G + X.games - 1) / X.games), dim3(64 * X.games), lds, st, S, X);
 }
 
-static void wset_swap(mz_handle* h, mz_handle::WSet& w);
-
 // MZ_OPP_NETWORK: the opponent search's outputs, part of the self-play state (a snapshot load
 // re-creates that state and keeps the mode, so the move asks again)
 static int opp_io(mz_handle* h) {
@@ -3406,20 +1768,6 @@ static int sp_move_body(mz_handle* h, const SpParams& S, float* cv2, float* rv2,
     hipLaunchKernelGGL(mz_sp_commit, waves, dim3(256), 0, st, S);
     return 0;
 }
-
-// the run log starts over on a new shard (mz_selfplay_init, a passing mz_snapshot_load, the log
-// switched on): zero accumulators, and the shard's `played` games so far are not this log's.  The
-// record ring and log_total stay.  The caller has drained the device.
-static int log_rebase(mz_handle* h, long long played) {
-    if (!h->d_log_acc) return 0;
-    LogAcc a;
-    std::memset(&a, 0, sizeof(a));
-    a.logged_upto = played;
-    MZ_TRY(h, hipMemcpy(h->d_log_acc, &a, sizeof(a), hipMemcpyHostToDevice));
-    return 0;
-}
-
-extern "C" {
 
 int mz_selfplay_init(mz_handle* h, int env_kind, int G, int replay_games) {
     if (!h) return -2;
@@ -4432,15 +2780,6 @@ static int ensure_multi(mz_handle* h, int B, int L) {
 static bool rmulti_ok(const mz_handle* h) {
     return h->kind == 1 && h->learn_mode == MZ_LEARN_REF_SEMANTICS && !h->conf.PER;
 }
-static int ensure_multi(mz_handle* h, int B, int L);
-// θ after up to two given steps, copied out by the chain launch that computes them (mz_train_run:
-// the actors' and the queued sets at refresh steps inside one learner chunk)
-struct MultiCap {
-    int64_t t[2];                                   // absolute learner steps (< 0: none)
-    float* dst[2];                                  // nflat floats each
-    const mz_handle::WSet* img0;                    // NULL or set 0's search images, written by the chain too
-    bool* imaged0;                                  // set when a chain launch wrote them
-};
 // mz_learn_chain's helper workgroups (ChainParams::nh) for the nets with more parameters than one pass
 // of the slices.  Measured against none (tools/gpu_r06t.sh): FC 32.1 -> 24.8 us per
 // 32-step chain, ResNet configs[2] 63.3 -> 44.2 us.  Returns the helper count.
@@ -4490,7 +2829,6 @@ static void rs_at(RpSampleParams& q, const RpSampleParams& Q, uint32_t step, int
 // half k mod 2, the steps' batches with chain_sample), each followed by its steps' sub-chunks of up to
 // Ls steps, body(c0, j0, n, ir, Qk, C): the unrolls and losses of the n steps from c0 + j0 on (ring
 // slots ir .., batches Qk, parameters at + j0 in C's banks).  Q: get_batch into ring slot 0.
-extern "C++" {                                   // (a template: not in the ABI block's linkage)
 template <class Body>
 static int multi_drive(mz_handle* h, uint32_t step0, int L, int Ls, const double* eta, float* theta_dev,
                        hipStream_t st, const MultiCap* cap, const RpSampleParams& Q, const MultiStrides& S,
@@ -4545,7 +2883,6 @@ static int multi_drive(mz_handle* h, uint32_t step0, int L, int Ls, const double
     h->ml_last_B = B; h->ml_last_L = L; h->ml_last_R = R;
     return 0;
 }
-}  // extern "C++"
 
 // ResNet nets (ref_semantics, no PER): per sub-chunk of Ls steps, the downsampler over the Ls·B
 // observations (Atari), the unroll launch(es) with the steps on gridDim.z (the fused form: step-major
@@ -4605,8 +2942,8 @@ static int rlearner_multi(mz_handle* h, int32_t B, uint32_t step0, int32_t L, co
 }
 
 // out_last: also (instead of losses[L-1]) the last step's losses there (mz_train_run)
-static int learner_multi(mz_handle* h, int32_t B, uint32_t step0, int32_t L, const double* eta, float* losses_dev,
-                         float* theta_dev, hipStream_t st, float* out_last = nullptr, const MultiCap* cap = nullptr) {
+int mz::learner_multi(mz_handle* h, int32_t B, uint32_t step0, int32_t L, const double* eta, float* losses_dev,
+                      float* theta_dev, hipStream_t st, float* out_last, const MultiCap* cap) {
     MZ_TRY(h, hipSetDevice(h->device));
     if (rmulti_ok(h)) return rlearner_multi(h, B, step0, L, eta, losses_dev, theta_dev, st, out_last, cap);
     int Ls = 0;
@@ -4732,7 +3069,7 @@ int mz_replay_get_game(mz_handle* h, int32_t i, int32_t* T, uint8_t* obs, int32_
 static const int kReanChunk = 4096;     // ResNet engines: positions per gather / nets / scatter round
 
 // what every reanalyse launch reads: the shard, its geometry and the counters
-static ReanParams rean_params(mz_handle* h) {
+ReanParams mz::rean_params(mz_handle* h) {
     ReanParams Q;
     std::memset(&Q, 0, sizeof(Q));
     Q.T = h->sp_T; Q.osz = h->sp_osz; Q.P = h->plane; Q.F = h->obs_feat; Q.stacked = h->conf.stacked_observations;
@@ -4858,7 +3195,7 @@ int mz_replay_get_reanalysed(mz_handle* h, int32_t i, int32_t* is_set, float* va
 // ---- Reanalyse by search: gather -> the batched search -> scatter per max_games rows
 // the search's io and the shard's reanalysed child_visits, allocated by the first call that has work,
 // and the search half of the parameters
-static int rean_search_io(mz_handle* h, ReanParams& Q) {
+int mz::rean_search_io(mz_handle* h, ReanParams& Q) {
     const size_t Gc = (size_t)h->max_games, A = (size_t)h->A;
     if (!h->d_rq_obs) {
         MZ_TRY(h, spalloc(h, &h->sp_ring.rcv, (size_t)h->sp_cap * h->sp_T * A, false));
@@ -4936,7 +3273,7 @@ int mz_replay_get_reanalysed_policies(mz_handle* h, int32_t i, int32_t* is_set, 
 // ---- The Reanalyse worker: one round of whole games from the device cursor, live rows only
 // (mz_reanalyse_pack), through either pass above.  The host knows neither how many games are held
 // nor which the round takes: every launch covers the round's capacity R and reads n_rows on the device.
-static int rean_next_check(mz_handle* h, int mode) {
+int mz::rean_next_check(mz_handle* h, int mode) {
     if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
     if (h->sp_frames > 0 || h->ds) return fail(h, "reanalyse: frame-stack env not built");
     if (mode != MZ_REAN_BY_VALUE && mode != MZ_REAN_BY_SEARCH)
@@ -5006,87 +3343,6 @@ int mz_replay_reanalyse_seek(mz_handle* h, int64_t game_number, void* stream) {
     return 0;
 }
 
-int mz_train_set_reanalyse(mz_handle* h, int mode, int rounds_per_move, int exploration) {
-    if (!h) return -2;
-    if (mode != MZ_REAN_OFF && mode != MZ_REAN_BY_VALUE && mode != MZ_REAN_BY_SEARCH)
-        return fail(h, "mz_train_set_reanalyse: mode must be MZ_REAN_OFF, MZ_REAN_BY_VALUE or MZ_REAN_BY_SEARCH");
-    if (rounds_per_move < 0) return fail(h, "mz_train_set_reanalyse: rounds_per_move must be >= 0");
-    if (mode != MZ_REAN_OFF && h->sp_env >= 0 && rean_next_check(h, mode)) return -1;
-    h->tr_rean_mode = mode; h->tr_rean_rounds = rounds_per_move; h->tr_rean_expl = exploration != 0;
-    return 0;
-}
-
-int mz_train_set_test(mz_handle* h, int64_t interval, uint32_t game_offset, float temperature) {
-    if (!h) return -2;
-    if (interval < 0) return fail(h, "mz_train_set_test: interval must be >= 0");
-    if (interval > 0 && h->test_E < 1)
-        return fail(h, "mz_train_set_test: no test slots (mz_test_config with games >= 1 first)");
-    h->test_interval = interval; h->test_goff = game_offset; h->test_temp = temperature;
-    return 0;
-}
-
-// ---- the run log's host side (the launches: log_games / log_steps / log_commit below)
-int mz_train_set_log(mz_handle* h, int64_t interval) {
-    if (!h) return -2;
-    if (interval < 0) return fail(h, "mz_train_set_log: interval must be >= 0");
-    if (interval > 0 && h->log_interval == 0) {     // switched on: the shard's games so far are not this log's
-        MZ_TRY(h, hipSetDevice(h->device));
-        MZ_SYNC(h);
-        if (!h->d_log_acc) {
-            MZ_TRY(h, dalloc(h, &h->d_log_acc, 1));
-            MZ_TRY(h, dalloc(h, &h->d_log_rows, (size_t)MZ_MULTI_LMAX * 8));
-            MZ_TRY(h, dalloc(h, &h->d_log_counts, (size_t)MZ_LOG_RECORDS * 16));
-            MZ_TRY(h, dalloc(h, &h->d_log_sums, (size_t)MZ_LOG_RECORDS * 16));
-        }
-        long long played = 0;
-        if (h->sp_env >= 0) MZ_TRY(h, hipMemcpy(&played, h->d_sp_counters, sizeof(played), hipMemcpyDeviceToHost));
-        if (log_rebase(h, played)) return -1;
-    }
-    h->log_interval = interval;
-    return 0;
-}
-
-static int log_commit(mz_handle* h, hipStream_t st);
-
-int mz_train_log_flush(mz_handle* h, void* stream) {
-    if (!h) return -2;
-    if (!h->tr_B) return fail(h, "mz_train_init first");
-    if (h->log_interval <= 0) return fail(h, "mz_train_log_flush: the run log is off (mz_train_set_log first)");
-    MZ_TRY(h, hipSetDevice(h->device));
-    return log_commit(h, stream_of(h, stream));
-}
-
-int mz_train_log_results(mz_handle* h, int64_t* total, int64_t* counts, double* sums, int32_t max_records) {
-    if (!h) return -2;
-    if (max_records < 0) return fail(h, "mz_train_log_results: max_records must be >= 0");
-    MZ_TRY(h, hipSetDevice(h->device));
-    MZ_SYNC(h);
-    if (total) *total = h->log_total;
-    const int64_t held = std::min<int64_t>(h->log_total, MZ_LOG_RECORDS);
-    const int64_t n = std::min<int64_t>(max_records, held);
-    for (int64_t i = 0; i < n; ++i) {
-        const size_t slot = (size_t)((h->log_total - n + i) % MZ_LOG_RECORDS);
-        long long c[16];
-        if (counts) {
-            MZ_TRY(h, hipMemcpy(c, h->d_log_counts + slot * 16, sizeof(c), hipMemcpyDeviceToHost));
-            for (int k = 0; k < 16; ++k) counts[i * 16 + k] = c[k];
-        }
-        if (sums) MZ_TRY(h, hipMemcpy(sums + i * 16, h->d_log_sums + slot * 16, 16 * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return 0;
-}
-
-int mz_train_log_clear(mz_handle* h) {
-    if (!h) return -2;
-    h->log_total = 0;
-    if (!h->d_log_acc) return 0;
-    MZ_TRY(h, hipSetDevice(h->device));
-    MZ_SYNC(h);
-    long long upto = 0;                             // the games folded so far stay folded
-    MZ_TRY(h, hipMemcpy(&upto, &h->d_log_acc->logged_upto, sizeof(upto), hipMemcpyDeviceToHost));
-    return log_rebase(h, upto);
-}
-
 int mz_selfplay_slots(mz_handle* h, int32_t* history_len, uint8_t* board, int32_t* player) {
     if (!h) return -2;
     if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
@@ -5101,289 +3357,8 @@ int mz_selfplay_slots(mz_handle* h, int32_t* history_len, uint8_t* board, int32_
     return 0;
 }
 
-// ---- actor–learner loop (self_play! ‖ learning!, Q16)
-// The actors search with their own weight set; the learner trains the
-// engine's weights.  The set is swapped in around each self-play move (the
-// search kernels read the images the handle points at).
-static void wset_swap(mz_handle* h, mz_handle::WSet& w) {
-    std::swap(h->d_flat, w.flat); std::swap(h->d_Wp, w.Wp); std::swap(h->d_Bp, w.Bp);
-    std::swap(h->d_sm_w, w.smw); std::swap(h->d_sm_bias, w.smb);
-}
-// flat -> the set's search images (the repack of the handle's current images)
-static int wset_repack(mz_handle* h, mz_handle::WSet& w, hipStream_t st) {
-    const int T = 256;
-    hipLaunchKernelGGL(mz_repack_kernel, dim3((unsigned)((h->packed_w_n + T - 1) / T)), dim3(T), 0, st,
-                       w.flat, h->d_srcW, w.Wp, h->packed_w_n);
-    if (h->packed_b_n)
-        hipLaunchKernelGGL(mz_repack_kernel, dim3((unsigned)((h->packed_b_n + T - 1) / T)), dim3(T), 0, st,
-                           w.flat, h->d_srcB, w.Bp, h->packed_b_n);
-    if (h->small_ok) {
-        hipLaunchKernelGGL(mz_repack_kernel, dim3((unsigned)((h->sm_w_n + T - 1) / T)), dim3(T), 0, st,
-                           w.flat, h->d_sm_srcw, w.smw, h->sm_w_n);
-        hipLaunchKernelGGL(mz_repack_kernel, dim3((unsigned)((h->sm_b_n + T - 1) / T)), dim3(T), 0, st,
-                           w.flat, h->d_sm_srcb, w.smb, h->sm_b_n);
-    }
-    MZ_TRY(h, hipGetLastError());
-    return 0;
-}
-// ParameterSchedulers 0.2.3 Cos(λ0 = 1e-4, λ1 = 1e-1, period = 10) under
-// Stateful, step t >= 1 (Learning.jl:319, 382)
-static double cos_schedule(int64_t t) {
-    const double l0 = 1e-4, l1 = 1e-1, range = std::fabs(l0 - l1), off = std::min(l0, l1);
-    const double a = 6.283185307179586 * (double)(t - 1) / 10.0;
-    return range * (1.0 + std::cos(a)) / 2.0 + off;
-}
-
-static float temp_fn(int64_t t) { return t < 500000 ? 1.0f : t < 750000 ? 0.5f : 0.25f; }   // SelfPlay.jl:48-56
-
-int mz_train_init(mz_handle* h, int32_t B) { return mz_train_init_at(h, B, 0); }
-
-int mz_train_set_networks_path(mz_handle* h, const char* networks_path) {
-    if (!h) return -2;
-    h->tr_ckpt_path = networks_path ? networks_path : "";
-    return 0;
-}
-
-// the actors' weight set, the queued nets and the move's pinned hand-back words (once per handle)
-static int train_alloc(mz_handle* h) {
-    mz_handle::WSet& w = h->tr_actor;
-    if (w.flat) return 0;
-    MZ_TRY(h, dalloc(h, &w.flat, h->nflat));
-    MZ_TRY(h, dalloc(h, &w.Wp, h->packed_w_n));
-    if (h->packed_b_n) MZ_TRY(h, dalloc(h, &w.Bp, h->packed_b_n));
-    if (h->small_ok) { MZ_TRY(h, dalloc(h, &w.smw, h->sm_w_n)); MZ_TRY(h, dalloc(h, &w.smb, h->sm_b_n)); }
-    MZ_TRY(h, dalloc(h, &h->d_tr_queued, h->nflat));
-    MZ_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->h_tr_cnt), 4 * sizeof(long long)));
-    MZ_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->h_tr_pub), 4 * sizeof(long long), hipHostMallocCoherent));
-    std::memset(h->h_tr_pub, 0, 4 * sizeof(long long));
-    h->tr_pub_seq = 0;
-    return 0;
-}
-
-int mz_train_init_at(mz_handle* h, int32_t B, int64_t t0) {
-    if (!h) return -2;
-    if (t0 < 0) return fail(h, "the starting training step must be >= 0");
-    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
-    if (B < 1) return fail(h, "batch_size must be >= 1");
-    if (h->conf.checkpoint_interval < 1) return fail(h, "checkpoint_interval must be >= 1");
-    MZ_TRY(h, hipSetDevice(h->device));
-    MZ_SYNC(h);
-    if (train_alloc(h)) return -1;
-    mz_handle::WSet& w = h->tr_actor;
-    // actors and the queue start from the learner's current (initial) nets (main.jl:23)
-    MZ_TRY(h, hipMemcpyAsync(w.flat, h->d_flat, h->nflat * 4, hipMemcpyDeviceToDevice, h->stream));
-    MZ_TRY(h, hipMemcpyAsync(h->d_tr_queued, h->d_flat, h->nflat * 4, hipMemcpyDeviceToDevice, h->stream));
-    if (wset_repack(h, w, h->stream)) return -1;
-    MZ_TRY(h, hipMemcpyAsync(h->h_tr_cnt, h->d_sp_counters, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-    MZ_TRY(h, hipStreamSynchronize(h->stream));
-    // games already in progress keep visit_softmax_temperature_fn(t0) to their end
-    std::vector<float> tg((size_t)h->sp_G, temp_fn(t0));
-    MZ_TRY(h, hipMemcpy(h->d_sp_tgame, tg.data(), tg.size() * 4, hipMemcpyHostToDevice));
-    h->tr_B = B; h->tr_t = t0; h->tr_refresh = 0;
-    h->tr_games = h->h_tr_cnt[0];
-    return 0;
-}
-
-// the move's hand-back to the host: the finished-game count and the fault word, then a sequence
-// number, stored into coherent pinned host memory at system scope; the host spins on the sequence
-// number instead of two copy launches and a stream synchronisation (measured in the trace: 30-60 us
-// from the copies' end to the next launch)
-extern "C" __global__ void mz_tr_publish(const long long* counters, const unsigned* fault, long long* host,
-                                         long long seq) {
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(host + 0, counters[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(host + 1, fault ? (long long)*fault : 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(host + 2, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-// wait for publish `seq` (bounded: after 60 s the stream is synchronised, which reports a launch error)
-static int tr_wait_publish(mz_handle* h, long long seq, hipStream_t st) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned n = 0; __atomic_load_n(h->h_tr_pub + 2, __ATOMIC_ACQUIRE) != seq; ++n) {
-        if ((n & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60)) {
-            MZ_TRY(h, hipStreamSynchronize(st));
-            if (__atomic_load_n(h->h_tr_pub + 2, __ATOMIC_ACQUIRE) == seq) break;
-            return fail(h, "mz_train: the move's publish never arrived");
-        }
-        __builtin_ia32_pause();
-    }
-    return 0;
-}
-
-// the move's reanalyse rounds (mz_train_set_reanalyse), with the learner's nets: round r has the
-// keys (move, game_offset + r * max_games)
-static int train_rean_rounds(mz_handle* h, uint32_t move, uint32_t game_offset, hipStream_t st) {
-    for (int r = 0; r < h->tr_rean_rounds; ++r)
-        if (mz_replay_reanalyse_next(h, h->tr_rean_mode, h->tr_rean_expl, move,
-                                     game_offset + (uint32_t)r * (uint32_t)h->max_games, st))
-            return -1;
-    return 0;
-}
-
-// ---- the run log: three tiny launches in stream order, nothing read back
-// behind a training move's mz_sp_store: the shard's new games
-static int log_games(mz_handle* h, hipStream_t st) {
-    hipLaunchKernelGGL(mz_log_games, dim3(1), dim3(1024), 0, st, sp_params(h), h->d_log_acc);
-    MZ_TRY(h, hipGetLastError());
-    return 0;
-}
-// behind a learner chunk: its n loss rows in d_log_rows
-static int log_steps(mz_handle* h, int n, hipStream_t st) {
-    LogArgs L;
-    std::memset(&L, 0, sizeof(L));
-    L.acc = h->d_log_acc; L.rows = h->d_log_rows; L.n = n;
-    hipLaunchKernelGGL(mz_log_steps, dim3(1), dim3(64), 0, st, L);
-    MZ_TRY(h, hipGetLastError());
-    return 0;
-}
-// record log_total from whatever is accumulated, with the learner at step tr_t
-static int log_commit(mz_handle* h, hipStream_t st) {
-    const size_t slot = (size_t)(h->log_total % MZ_LOG_RECORDS);
-    LogArgs L;
-    std::memset(&L, 0, sizeof(L));
-    L.acc = h->d_log_acc; L.counts = h->d_log_counts + slot * 16; L.sums = h->d_log_sums + slot * 16;
-    L.counters = h->d_sp_counters; L.cap = h->sp_cap;
-    L.t1 = h->tr_t; L.refreshes = h->tr_refresh; L.eta = cos_schedule(h->tr_t);
-    hipLaunchKernelGGL(mz_log_commit, dim3(1), dim3(64), 0, st, L);
-    MZ_TRY(h, hipGetLastError());
-    ++h->log_total;
-    return 0;
-}
-// the commit rule (the test worker's): the call's learner steps crossed a multiple of the interval
-static int log_crossed(mz_handle* h, int64_t t0, hipStream_t st) {
-    const int64_t iv = h->log_interval;
-    return iv > 0 && h->tr_t / iv > t0 / iv ? log_commit(h, st) : 0;
-}
-
-// 1. one self-play move with the actors' nets (SelfPlay.jl:343-380); temperature
-//    visit_softmax_temperature_fn(t) (:48-56, 396-397) for the games that start on
-//    this move (a game in progress keeps its own).  *nfin = the games save_game
-//    stored (slot order, inside the move).  The fault word rides along with the
-//    counter copy: one stream wait per move, no second blocking copy.
-//    `rean` (mz_train_run): the move's reanalyse rounds go on the stream behind the
-//    hand-back and before the host waits for it, so the wait overlaps them.
-static int train_move(mz_handle* h, uint32_t move, uint32_t game_offset, int64_t* nfin, hipStream_t st,
-                      bool rean = false) {
-    rean = rean && h->tr_rean_mode != MZ_REAN_OFF;
-    const float temp = temp_fn(h->tr_t);
-    wset_swap(h, h->tr_actor);
-    h->sp_latch = true;
-    const int rc = mz_selfplay_move(h, move, game_offset, temp, st);
-    h->sp_latch = false;
-    wset_swap(h, h->tr_actor);
-    if (rc) return rc;
-    const long long seq = ++h->tr_pub_seq;
-    hipLaunchKernelGGL(mz_tr_publish, dim3(1), dim3(64), 0, st, (const long long*)h->d_sp_counters,
-                       (const unsigned*)h->d_fault, h->h_tr_pub, seq);
-    MZ_TRY(h, hipGetLastError());
-    // the run log folds the shard's new games (the move's saves, and any a host put in since the last
-    // move) behind the hand-back, so the host's wait overlaps it
-    if (h->log_interval > 0 && !h->sp_eval && log_games(h, st)) return -1;
-    if (rean && train_rean_rounds(h, move, game_offset, st)) return -1;
-    if (tr_wait_publish(h, seq, st)) return -1;
-    h->h_tr_cnt[0] = h->h_tr_pub[0];
-    h->h_tr_cnt[1] = h->h_tr_pub[1];
-    if (h->h_tr_cnt[1] && check_fault(h)) return -1;
-    *nfin = h->h_tr_cnt[0] - h->tr_games;
-    h->tr_games = h->h_tr_cnt[0];
-    return 0;
-}
-
-// the actors take the queued nets, the learner's nets are queued (SelfPlay.jl:399-401 /
-// Learning.jl:416-418: one checkpoint behind); past round(0.9 training_steps) the nets
-// go to disk (Learning.jl:427-432, round half to even as Julia's round)
-static int train_refresh(mz_handle* h, int64_t t, hipStream_t st) {
-    MZ_TRY(h, hipMemcpyAsync(h->tr_actor.flat, h->d_tr_queued, h->nflat * 4, hipMemcpyDeviceToDevice, st));
-    if (wset_repack(h, h->tr_actor, st)) return -1;
-    MZ_TRY(h, hipMemcpyAsync(h->d_tr_queued, h->d_flat, h->nflat * 4, hipMemcpyDeviceToDevice, st));
-    ++h->tr_refresh;
-    if (!h->tr_ckpt_path.empty() && (double)t > std::nearbyint(0.9 * (double)h->conf.training_steps)) {
-        MZ_TRY(h, hipStreamSynchronize(st));
-        const std::string path = h->tr_ckpt_path + "/" + std::to_string(t) + ".safetensors";
-        if (mz_checkpoint_save(h, path.c_str(), t)) return -1;
-    }
-    return 0;
-}
-
-// 2. `nreq` learner steps while t <= training_steps (Learning.jl:327), get_batch keyed by
-//    the step number, eta = Cos(step); every checkpoint_interval steps (t % ci == 0, t > 1)
-//    an actor refresh.  Round 6: the steps of one call run as ONE mz_learner_train_multi_dev
-//    chunk across the refresh points (up to 256 steps per call): nothing
-//    reads the actors' or the queued nets between two learner steps of one move, so only
-//    the sets after the last refresh matter — θ of the last refresh step is queued, θ of the
-//    one before it (or, with one refresh, the previously queued nets) goes to the actors, and
-//    the chain launch that computes those θ copies them out (MultiCap).  With periodic
-//    checkpoint files (networks_path) the chunks end at every
-//    refresh step as in round 5 (the checkpoint writes the learner's nets of that step).
-static int train_learn(mz_handle* h, int64_t nreq, float* losses_dev, hipStream_t st, int64_t* done) {
-    const bool per_refresh = !h->tr_ckpt_path.empty();
-    const int64_t ci = h->conf.checkpoint_interval;
-    auto is_refresh = [&](int64_t t) { return t % ci == 0 && t > 1; };
-    const int64_t n_all = std::max<int64_t>(0, std::min<int64_t>(nreq, (int64_t)h->conf.training_steps + 1 - h->tr_t));
-    *done = 0;
-    if (n_all == 0) return 0;
-    // the actors' set: θ of the next-to-last refresh step, its search images written by the chain launch
-    // that computes it (else repacked after the call)
-    bool imaged = false;
-    MultiCap cap{{-1, -1}, {h->tr_actor.flat, h->d_tr_queued}, &h->tr_actor, &imaged};
-    int64_t nref = 0;
-    if (!per_refresh) {
-        // the refresh steps in (t, t + n]: the last two
-        const int64_t t_lo = h->tr_t, t_hi = h->tr_t + n_all;
-        for (int64_t r = t_hi / ci * ci; r > t_lo && nref < 2; r -= ci)
-            if (is_refresh(r)) { cap.t[1 - nref] = r; ++nref; }
-        const int64_t first = (t_lo / ci + 1) * ci;   // the total count
-        nref = 0;
-        for (int64_t r = first; r <= t_hi; r += ci) nref += is_refresh(r) ? 1 : 0;
-        if (nref == 1) {               // the actors take the nets queued before this call
-            MZ_TRY(h, hipMemcpyAsync(h->tr_actor.flat, h->d_tr_queued, h->nflat * 4, hipMemcpyDeviceToDevice, st));
-            cap.t[0] = -1;
-        }
-    }
-    double eta[MZ_MULTI_LMAX];
-    for (int64_t k = 0; k < n_all;) {
-        const int64_t t0 = h->tr_t + 1;
-        int64_t n = std::min<int64_t>(n_all - k, MZ_MULTI_LMAX);
-        if (per_refresh) {                                 // the chunk ends at the next refresh step
-            int64_t tb = (t0 + ci - 1) / ci * ci;
-            if (tb <= 1) tb += ci;
-            n = std::min<int64_t>(n, tb - t0 + 1);
-        }
-        const int64_t t = t0 + n - 1;
-        // the run log: every step's losses go to the handle's rows, mz_log_steps folds them behind the
-        // chunk, and the caller's losses_dev gets a copy of the last row.  Off: the pointers below are
-        // the caller's as ever and nothing more is issued.
-        float* rows = h->log_interval > 0 ? h->d_log_rows : nullptr;
-        if (n == 1) {
-            if (mz_learner_train_dev(h, h->tr_B, (uint32_t)t, cos_schedule(t), rows ? rows : losses_dev, st)) return -1;
-            for (int j = 0; j < 2; ++j)
-                if (cap.t[j] == t)
-                    MZ_TRY(h, hipMemcpyAsync(cap.dst[j], h->d_flat, h->nflat * 4, hipMemcpyDeviceToDevice, st));
-        } else {
-            for (int64_t i = 0; i < n; ++i) eta[i] = cos_schedule(t0 + i);
-            if (learner_multi(h, h->tr_B, (uint32_t)t0, (int32_t)n, eta, rows, nullptr, st, rows ? nullptr : losses_dev,
-                              per_refresh ? nullptr : &cap))
-                return -1;
-        }
-        if (rows) {
-            if (losses_dev)
-                MZ_TRY(h, hipMemcpyAsync(losses_dev, rows + 8 * (n - 1), 6 * 4, hipMemcpyDeviceToDevice, st));
-            if (log_steps(h, (int)n, st)) return -1;
-        }
-        h->tr_t = t;
-        *done += n;
-        k += n;
-        if (per_refresh && is_refresh(t) && train_refresh(h, t, st)) return -1;
-    }
-    if (!per_refresh && nref > 0) {
-        if (!(nref >= 2 && imaged) && wset_repack(h, h->tr_actor, st)) return -1;
-        h->tr_refresh += nref;
-    }
-    return 0;
-}
-
 // a count summed over the ranks of the handle's RCCL communicator (exact below 2^24)
-static int dp_sum_count(mz_handle* h, int64_t* v, hipStream_t st) {
+int mz::dp_sum_count(mz_handle* h, int64_t* v, hipStream_t st) {
     if (!h->d_dp_cnt) MZ_TRY(h, dalloc(h, &h->d_dp_cnt, 1));
     float f = (float)*v;
     MZ_TRY(h, hipMemcpyAsync(h->d_dp_cnt, &f, 4, hipMemcpyHostToDevice, st));
@@ -5395,133 +3370,6 @@ static int dp_sum_count(mz_handle* h, int64_t* v, hipStream_t st) {
     return 0;
 }
 
-int mz_train_move(mz_handle* h, uint32_t move, uint32_t game_offset, int64_t* nfin, void* stream) {
-    if (!h) return -2;
-    if (!h->tr_B) return fail(h, "mz_train_init first");
-    MZ_TRY(h, hipSetDevice(h->device));
-    int64_t n = 0;
-    if (train_move(h, move, game_offset, &n, stream_of(h, stream))) return -1;
-    if (nfin) *nfin = n;
-    return 0;
-}
-
-int mz_train_learn(mz_handle* h, int64_t steps, float* losses_dev, int64_t* state_out, void* stream) {
-    if (!h) return -2;
-    if (!h->tr_B) return fail(h, "mz_train_init first");
-    if (steps < 0) return fail(h, "steps must be >= 0");
-    MZ_TRY(h, hipSetDevice(h->device));
-    int64_t done = 0;
-    const int64_t t0 = h->tr_t;
-    if (train_learn(h, steps, losses_dev, stream_of(h, stream), &done)) return -1;
-    if (log_crossed(h, t0, stream_of(h, stream))) return -1;       // the run log's commit rule, per call
-    if (state_out) {
-        state_out[0] = h->tr_t; state_out[1] = h->tr_games; state_out[2] = h->tr_refresh; state_out[3] = done;
-    }
-    return 0;
-}
-
-int mz_train_run(mz_handle* h, int32_t moves, uint32_t move0, uint32_t game_offset, int64_t* state_out,
-                 float* losses_dev, void* stream) {
-    if (!h) return -2;
-    if (!h->tr_B) return fail(h, "mz_train_init first");
-    if (moves < 0) return fail(h, "moves must be >= 0");
-    MZ_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = stream_of(h, stream);
-    int64_t steps = 0;
-    for (int32_t mv = 0; mv < moves; ++mv) {
-        int64_t nfin = 0, done = 0;
-        if (train_move(h, move0 + (uint32_t)mv, game_offset, &nfin, st, true)) return -1;
-        // data parallel (mz_dp_init): every rank takes the learner steps of the games all
-        // ranks finished, so the replicas stay identical
-        if (h->dp_comm && h->dp_world > 1 && dp_sum_count(h, &nfin, st)) return -1;
-        const int64_t t0 = h->tr_t;
-        if (train_learn(h, nfin, losses_dev, st, &done)) return -1;
-        steps += done;
-        if (log_crossed(h, t0, st)) return -1;      // the run log's commit rule, per move (mz_train_set_log)
-        // the test worker (mz_train_set_test): the move's learner steps crossed a multiple of the
-        // interval -> one evaluation with the learner's nets after the move's last step (the chunk is
-        // not cut), where the next move's Reanalyse rounds search with them too
-        const int64_t iv = h->test_interval, t1 = h->tr_t;
-        if (iv > 0 && t1 / iv > t0 / iv &&
-            mz_test_play(h, t1, (uint32_t)t1 * (uint32_t)h->sp_T, h->test_goff, h->test_temp, st))
-            return -1;
-    }
-    if (state_out) {
-        state_out[0] = h->tr_t; state_out[1] = h->tr_games; state_out[2] = h->tr_refresh; state_out[3] = steps;
-    }
-    return 0;
-}
-
-int mz_train_weights_get(mz_handle* h, int which, int net, float* flat, size_t n) {
-    if (!h) return -2;
-    if (which == MZ_TRAIN_LEARNER) return mz_weights_get(h, net, flat, n);
-    if (!h->tr_B) return fail(h, "mz_train_init first");
-    if (which != MZ_TRAIN_ACTOR && which != MZ_TRAIN_QUEUED) return fail(h, "which: learner, actor or queued");
-    if (net < 0 || net > 2) return fail(h, "bad net id");
-    if (n != h->nparams[net]) return fail(h, "wrong parameter count");
-    MZ_TRY(h, hipSetDevice(h->device));
-    MZ_SYNC(h);
-    const float* src = which == MZ_TRAIN_ACTOR ? h->tr_actor.flat : h->d_tr_queued;
-    MZ_TRY(h, hipMemcpy(flat, src + h->flat_off[net], n * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// ---- the opponent's weight set (MZ_OPP_NETWORK): a handle setting like
-// mz_expert_depth; mz_selfplay_init, mz_snapshot_load and mz_weights_set leave it alone
-static int opp_alloc(mz_handle* h) {
-    if (h->opp.flat) return 0;
-    mz_handle::WSet w;
-    MZ_TRY(h, dalloc(h, &w.flat, h->nflat));
-    MZ_TRY(h, dalloc(h, &w.Wp, h->packed_w_n));
-    if (h->packed_b_n) MZ_TRY(h, dalloc(h, &w.Bp, h->packed_b_n));
-    if (h->small_ok) { MZ_TRY(h, dalloc(h, &w.smw, h->sm_w_n)); MZ_TRY(h, dalloc(h, &w.smb, h->sm_b_n)); }
-    h->opp = w;
-    return 0;
-}
-
-int mz_opponent_weights_set(mz_handle* h, int net, const float* flat, size_t n) {
-    if (!h) return -2;
-    if (net < 0 || net > 2) return fail(h, "bad net id");
-    if (!flat) return fail(h, "opponent_weights_set: null weights");
-    if (n != h->nparams[net]) return fail(h, "opponent_weights_set: wrong parameter count");
-    MZ_TRY(h, hipSetDevice(h->device));
-    MZ_SYNC(h);                  // no search still reads the old set
-    if (opp_alloc(h)) return -1;
-    MZ_TRY(h, hipMemcpyAsync(h->opp.flat + h->flat_off[net], flat, n * 4, hipMemcpyHostToDevice, h->stream));
-    h->opp_have |= 1u << net;
-    if (h->opp_have == 7u && wset_repack(h, h->opp, h->stream)) return -1;   // the images need all three nets
-    MZ_SYNC(h);
-    return 0;
-}
-
-int mz_opponent_weights_get(mz_handle* h, int net, float* flat, size_t n) {
-    if (!h) return -2;
-    if (net < 0 || net > 2) return fail(h, "bad net id");
-    if (!flat) return fail(h, "opponent_weights_get: null buffer");
-    if (n != h->nparams[net]) return fail(h, "opponent_weights_get: wrong parameter count");
-    if (!(h->opp_have >> net & 1u)) return fail(h, "opponent_weights_get: this net of the set was never given");
-    MZ_TRY(h, hipSetDevice(h->device));
-    MZ_SYNC(h);                  // a stream-ordered mz_opponent_from has landed
-    MZ_TRY(h, hipMemcpy(flat, h->opp.flat + h->flat_off[net], n * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int mz_opponent_from(mz_handle* h, int which, void* stream) {
-    if (!h) return -2;
-    if (which != MZ_TRAIN_LEARNER && which != MZ_TRAIN_ACTOR && which != MZ_TRAIN_QUEUED)
-        return fail(h, "opponent_from: which must be MZ_TRAIN_LEARNER, MZ_TRAIN_ACTOR or MZ_TRAIN_QUEUED");
-    if (which != MZ_TRAIN_LEARNER && !h->tr_B) return fail(h, "opponent_from: mz_train_init first");
-    MZ_TRY(h, hipSetDevice(h->device));
-    if (opp_alloc(h)) return -1;
-    hipStream_t st = stream_of(h, stream);
-    const float* src = which == MZ_TRAIN_LEARNER ? h->d_flat
-                       : which == MZ_TRAIN_ACTOR ? h->tr_actor.flat : h->d_tr_queued;
-    MZ_TRY(h, hipMemcpyAsync(h->opp.flat, src, h->nflat * 4, hipMemcpyDeviceToDevice, st));
-    if (wset_repack(h, h->opp, st)) return -1;
-    h->opp_have = 7u;
-    return 0;
-}
-
 int mz_sync(mz_handle* h) {
     if (!h) return -2;
     MZ_TRY(h, hipSetDevice(h->device));
@@ -5529,95 +3377,4 @@ int mz_sync(mz_handle* h) {
     // mz_set_sync_stream), so a fault of work queued on a caller stream is reported here
     MZ_SYNC(h);
     return 0;
-}
-
-}  // extern "C"
-
-// mz_opponent_load's engine side (mz_ckpt_iface.h): a validated file's three nets become the set
-int mz_opponent_put(mz_handle* h, const float* flat) {
-    MZ_TRY(h, hipSetDevice(h->device));
-    MZ_SYNC(h);
-    if (opp_alloc(h)) return -1;
-    MZ_TRY(h, hipMemcpyAsync(h->opp.flat, flat, h->nflat * 4, hipMemcpyHostToDevice, h->stream));
-    if (wset_repack(h, h->opp, h->stream)) return -1;
-    h->opp_have = 7u;
-    MZ_SYNC(h);
-    return 0;
-}
-
-// ---- snapshots (mz_snapshot.hip; mz_snap_iface.h): the engine's side
-// `train`: the weight sets of mz_train_init exist and belong to the view
-static void snap_fill_view(mz_handle* h, MzSnapView* v, bool train) {
-    v->device = h->device; v->stream = h->stream;
-    v->env = h->sp_env; v->G = h->sp_G; v->cap = h->sp_cap; v->T = h->sp_T; v->osz = h->sp_osz; v->A = h->A;
-    v->per = h->conf.PER != 0; v->seed = h->seed;
-    v->ring = h->sp_ring; v->hist = h->sp_hist; v->counters = h->d_sp_counters;
-    v->hist.prio = nullptr; v->hist.gprio = nullptr;      // allocated, never used: not state
-    if (!v->per) { v->ring.prio = nullptr; v->ring.gprio = nullptr; }
-    v->board = h->d_sp_board; v->player = h->d_sp_player; v->over = h->d_sp_over; v->ekey = h->d_sp_ekey;
-    v->tgame = h->d_sp_tgame; v->eval = h->d_eval;
-    v->reset_pending = h->sp_reset_pending;
-    v->train = train;
-    v->tr[0] = h->tr_B; v->tr[1] = h->tr_t; v->tr[2] = h->tr_refresh;
-    v->actor = h->tr_actor.flat; v->queued = h->d_tr_queued; v->nflat = h->nflat;
-    v->settings = "{\"reanalyse\":[" + std::to_string(h->tr_rean_mode) + "," + std::to_string(h->tr_rean_rounds) + "," +
-                  std::to_string(h->tr_rean_expl) + "],\"selfplay_mode\":[" + std::to_string(h->sp_eval) + "," +
-                  std::to_string(h->sp_opp) + "," + std::to_string(h->sp_mzp) + "],\"learner_mode\":" +
-                  std::to_string(h->learn_mode) + ",\"debug\":" +
-                  std::to_string(h->dump_tree | h->time_nets << 1 | h->time_unroll << 2) + ",\"networks_path\":" +
-                  (h->tr_ckpt_path.empty() ? "0" : "1") + "}";
-}
-
-int mz_snap_view(mz_handle* h, MzSnapView* v) {
-    if (h->sp_env < 0) return fail(h, "mz_selfplay_init first");
-    MZ_TRY(h, hipSetDevice(h->device));
-    MZ_SYNC(h);
-    snap_fill_view(h, v, h->tr_B > 0);
-    return 0;
-}
-
-void mz_snap_engine_geometry(const mz_handle* h, mzsnap::EngineGeometry* e) {
-    const mz_config& c = h->conf;
-    const int W = c.observation_shape[0], H = c.observation_shape[1], C = c.observation_shape[2];
-    e->network = mz_net_kind(h); e->config = mz_describe(h);
-    // the envs mz_selfplay_init accepts for this config, with their record bytes per move
-    e->env_osz[MZ_ENV_TICTACTOE] = W == 3 && H == 3 && C == 3 && h->A == 9 ? 27 : 0;
-    e->env_osz[MZ_ENV_CONNECT4] = W == 6 && H == 7 && C == 3 && h->A == 7 ? 126 : 0;
-    e->env_osz[MZ_ENV_ATARI] = W == 84 && H == 84 && C == 4 && h->A == 18 && c.stacked_observations == 0 ? 84 * 84 : 0;
-    e->max_games = h->max_games; e->T = (long long)c.max_moves + 1; e->A = h->A; e->per = c.PER != 0;
-    e->seed = h->seed;
-}
-
-int mz_snap_restore_begin(mz_handle* h, int env, int G, int cap, bool rcv, bool train, MzSnapView* v) {
-    const bool had = h->sp_env >= 0;
-    const int ev = h->sp_eval, opp = h->sp_opp, mzp = h->sp_mzp;
-    if (int rc = mz_selfplay_init(h, env, G, cap)) return rc;
-    if (had) { h->sp_eval = ev; h->sp_opp = opp; h->sp_mzp = mzp; }   // a setting of the loading host
-    if (rcv) {
-        ReanParams Q = rean_params(h);
-        if (rean_search_io(h, Q)) return -1;
-        MZ_TRY(h, hipMemset(h->sp_ring.rcv, 0, (size_t)h->sp_cap * h->sp_T * h->A * 4));
-    }
-    if (train) {
-        if (h->conf.checkpoint_interval < 1) return fail(h, "checkpoint_interval must be >= 1");
-        if (train_alloc(h)) return -1;       // tr_B stays 0 until mz_snap_restore_end sets the snapshot's
-    }
-    MZ_SYNC(h);
-    snap_fill_view(h, v, train);
-    return 0;
-}
-
-int mz_snap_restore_end(mz_handle* h, const long long* counters, int reset_pending, const long long* tr) {
-    MZ_TRY(h, hipSetDevice(h->device));
-    h->sp_reset_pending = reset_pending != 0;
-    h->sp_has_games = counters[0] > 0;
-    if (tr) {
-        if (wset_repack(h, h->tr_actor, h->stream)) return -1;
-        h->tr_B = (int)tr[0]; h->tr_t = tr[1]; h->tr_refresh = tr[2];
-        h->tr_games = counters[0];
-        h->h_tr_cnt[0] = counters[0];
-    }
-    ++h->pf_epoch;                           // no batch drawn ahead survives: the next step samples in place
-    MZ_SYNC(h);
-    return log_rebase(h, counters[0]);       // the run log: the file's games are not this log's
 }
