@@ -219,6 +219,23 @@ int mz_debug_unroll(mz_handle* h, int B, float* values, float* policies, float* 
  * so steps older than that are refused.                                     */
 int mz_debug_unroll_step(mz_handle* h, int i, int B, float* values, float* policies, float* rewards);
 
+/* Debug/parity: the plan of the FC corrected learner (MZ_LEARN_CORRECTED,
+ * mz_bp_tile_lv), built if it is not yet; nothing is launched.  A plan the
+ * engine refuses (its level schedule exceeds the LDS) is an error with that
+ * message, as from the learner calls; so is a ResNet engine, and n below
+ * MZ_BP_PLAN_FIELDS.  out[0..MZ_BP_PLAN_FIELDS):
+ *   0 applications (dense and concat) of the unroll
+ *   1 forward levels                  2 backward levels
+ *   3 floats of one LDS cache slot    4 cache slots (0: the kernel runs without the cache)
+ *   5 dynamic LDS bytes of the kernel
+ *   6 applications reading from the arena an input that an earlier application produced
+ *   7 produced tensors that are read later and got no forward slot
+ *   8 applications accumulating dL/dx in the arena for a tensor that has a producer
+ *   9 forward levels ending in a full barrier (the arena's stores drained)
+ *  10 backward levels ending in one                                          */
+enum { MZ_BP_PLAN_FIELDS = 11 };
+int mz_debug_bp_plan(mz_handle* h, int32_t* out, int n);
+
 /* One learner batch, the tuple returned by get_batch (ReplayBuffer.jl:216),
  * column-major as in the reference:
  *   observation (W,H,Cs,B), actions (K+1,B) as float action ids,

@@ -20,6 +20,9 @@ ENV_TICTACTOE, ENV_CONNECT4, ENV_ATARI = 0, 1, 2
 SP_TRAIN, SP_EVAL = 0, 1
 TRAIN_LEARNER, TRAIN_ACTOR, TRAIN_QUEUED = 0, 1, 2
 LEARN_REF_SEMANTICS, LEARN_CORRECTED = 0, 1
+# mz_debug_bp_plan's values, in order (include/mz.h)
+BP_PLAN_FIELDS = ("n_app", "fwd_levels", "bwd_levels", "slot_floats", "nslot", "lds_bytes", "arena_reads",
+                  "unslotted_outputs", "arena_accumulations", "fwd_flagged", "bwd_flagged")
 OPP_SELF, OPP_RANDOM, OPP_EXPERT, OPP_NETWORK, OPP_MCTS = 0, 1, 2, 3, 4
 REAN_OFF, REAN_BY_VALUE, REAN_BY_SEARCH = 0, 1, 2
 TEST_RECORDS = 1024                              # MZ_TEST_RECORDS: the test worker's record ring
@@ -123,6 +126,7 @@ SIGNATURES = {
     "mz_learner_train_multi_dev": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int32,
                                                   ctypes.POINTER(ctypes.c_double), _VP, _VP, _VP]),
     "mz_debug_unroll_step": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    "mz_debug_bp_plan": (ctypes.c_int, [_VP, _VP, ctypes.c_int]),
     "mz_replay_update_priorities": (ctypes.c_int, [_VP, _VP]),
     "mz_replay_get_priorities": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP]),
     "mz_replay_get_game": (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
@@ -356,6 +360,13 @@ class Engine:
         pr = np.empty((B, K1), np.float32)
         self._check(self.lib.mz_debug_unroll_step(self.h, i, B, _p(pv), _p(pp), _p(pr)), "mz_debug_unroll_step")
         return pv, pp, pr
+
+    def debug_bp_plan(self):
+        """The FC corrected learner's plan (mz_debug_bp_plan; built if needed, nothing launched) as a
+        dict of BP_PLAN_FIELDS; a plan the engine refuses raises MzError."""
+        out = np.zeros(len(BP_PLAN_FIELDS), np.int32)
+        self._check(self.lib.mz_debug_bp_plan(self.h, _p(out), out.size), "mz_debug_bp_plan")
+        return dict(zip(BP_PLAN_FIELDS, (int(x) for x in out)))
 
     # ---- learner
     def learner_step(self, batch, eta):

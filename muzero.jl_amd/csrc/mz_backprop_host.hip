@@ -119,12 +119,12 @@ static int build_bp(mz_handle* h) {
     // ends with a barrier that drains the stores (fsync / bsync), as do the
     // last forward level (the heads and the backward read the arena).
     std::vector<int> fsync(nfl, 0), bsync(nbl, 0);
-    int cache_floats = 0, obs_s = -1;
+    int cache_floats = 0, obs_s = -1, slot = 0;
     for (BpApp& a : apps) { a.xs = a.ys = a.gys = a.gxs = -1; a.gxf = 0; }
 #if BP_LV_SIMPLE && !BP_LV_PREFETCH
     {
         auto rows16 = [](int r) { return ((r + 3) & ~3) * 16; };
-        int slot = rows16(h->obs_feat);
+        slot = rows16(h->obs_feat);
         for (const BpApp& a : apps) slot = std::max(slot, rows16(a.out));
         const size_t sched = (size_t)na * sizeof(BpApp) + (fun.size() + bun.size()) * sizeof(int2) +
                              (size_t)(2 * (nfl + nbl) + 8) * sizeof(int);
@@ -195,6 +195,23 @@ static int build_bp(mz_handle* h) {
         }
     }
 #endif
+    // what the plan leaves to the arena (mz_debug_bp_plan): hand-offs between
+    // applications that go through HBM and the flagged barriers that order them
+    {
+        std::map<int, int> producer, readers;
+        for (int a = 0; a < na; ++a) { producer[apps[a].y] = a; ++readers[apps[a].x]; }
+        int* c = h->bp_plan;
+        c[0] = c[1] = c[2] = c[3] = c[4] = 0;
+        for (const BpApp& a : apps) {
+            if (a.xs < 0 && producer.count(a.x)) ++c[0];      // a produced input read from the arena
+            if (a.ys < 0 && readers.count(a.y)) ++c[1];       // an output read later, without a forward slot
+            if (a.gxs < 0 && producer.count(a.x)) ++c[2];     // ∂L/∂x added in the arena, its producer reads it there
+        }
+        for (int f : fsync) c[3] += f;
+        for (int f : bsync) c[4] += f;
+        h->bp_slot_floats = slot;
+        h->bp_nslot = slot ? cache_floats / slot : 0;
+    }
     // dW: every layer's applications, one wave per 16x16 block (+ one per bias block)
     std::vector<BpLayer> layers(h->layers.size());
     std::vector<BpUse> uses;
@@ -229,6 +246,7 @@ static int build_bp(mz_handle* h) {
         const size_t lv = (size_t)na * sizeof(BpApp) + (fun.size() + bun.size()) * sizeof(int2) +
                           (size_t)(2 * (nfl + nbl) + 8) * sizeof(int) + 16 + (size_t)cache_floats * 4;
         if (lv > kLdsMax) return fail(h, "corrected learner: the level schedule exceeds the LDS");
+        h->bp_lds_bytes = (int)lv;
         MZ_TRY(h, hipFuncSetAttribute((const void*)mz_bp_tile_lv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lv));
         MZ_TRY(h, hipFuncSetAttribute((const void*)mz_bp_tile_lv_nobn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)lv));
@@ -539,6 +557,20 @@ static int rbp_grad(mz_handle* h, const mz_batch* b, float* grad_dev, float* los
     hipLaunchKernelGGL(mz_bp_fold, dim3(4), dim3(256), 0, st, F);
     MZ_TRY(h, hipGetLastError());
     h->last_lvariant = h->ds ? "mz_dsbp+mz_rbp_sample+mz_rbp_dw" : "mz_rbp_sample+mz_rbp_dw";
+    return 0;
+}
+
+// the FC plan's read-out (include/mz.h): built if needed, nothing launched
+int mz_debug_bp_plan(mz_handle* h, int32_t* out, int n) {
+    if (!h || !out) return -2;
+    if (h->kind == 1) return fail(h, "mz_debug_bp_plan: the ResNet learner has no level schedule");
+    if (n < MZ_BP_PLAN_FIELDS) return fail(h, "mz_debug_bp_plan: out holds fewer than MZ_BP_PLAN_FIELDS values");
+    MZ_TRY(h, hipSetDevice(h->device));
+    if (!h->bp_built && build_bp(h)) return -1;
+    const int v[MZ_BP_PLAN_FIELDS] = {h->bp_n_app, h->bp_n_flev, h->bp_n_blev, h->bp_slot_floats, h->bp_nslot,
+                                      h->bp_lds_bytes, h->bp_plan[0], h->bp_plan[1], h->bp_plan[2], h->bp_plan[3],
+                                      h->bp_plan[4]};
+    for (int i = 0; i < MZ_BP_PLAN_FIELDS; ++i) out[i] = v[i];
     return 0;
 }
 

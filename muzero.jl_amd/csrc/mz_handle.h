@@ -234,6 +234,8 @@ struct mz_handle {
     int2* d_bp_funits = nullptr; int* d_bp_flev = nullptr; int2* d_bp_bunits = nullptr; int* d_bp_blev = nullptr;
     int bp_n_flev = 0, bp_n_blev = 0, bp_n_funit = 0, bp_n_bunit = 0;
     int* d_bp_fsync = nullptr; int* d_bp_bsync = nullptr; int bp_cache_floats = 0, bp_obs_s = -1;
+    // mz_debug_bp_plan: the cache's slots, the kernel's dynamic LDS, and what the plan leaves to the arena
+    int bp_slot_floats = 0, bp_nslot = 0, bp_lds_bytes = 0, bp_plan[5] = {0, 0, 0, 0, 0};
     double* d_bp_sq = nullptr; int bp_job0[4] = {0, 0, 0, 0};
     float* d_bp_act = nullptr; float* d_bp_grad = nullptr; float* d_bp_terms = nullptr;
     // ---- self-play slots, opponents, the test worker (mz_selfplay_host.hip)

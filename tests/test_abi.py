@@ -18,7 +18,7 @@ def _declared():
 def test_header_declares_the_boundary():
     names = _declared()
     for n in ("mz_engine_create", "mz_mcts_search", "mz_mcts_search_dev", "mz_net_forward",
-              "mz_learner_step", "mz_learner_grad_dev", "mz_learner_apply_dev", "mz_weights_set"):
+              "mz_learner_step", "mz_learner_grad_dev", "mz_learner_apply_dev", "mz_weights_set", "mz_debug_bp_plan"):
         assert n in names
 
 

@@ -160,8 +160,13 @@ def corrected_loss_and_grads(conf, hyper, nets, batch, weights=None, dtype=torch
     data = vloss + ploss + rloss
     l2 = [(p ** 2).sum() for p in params]
     total = data + sum(l2)
+    # the data term alone (what mz_learner_grad_dev returns): not grads − 2θ, whose rounding in
+    # float32 is an ulp of θ, not of the term; a net the unroll does not apply gets exact zeros
+    dgrads = torch.autograd.grad(data, params, retain_graph=True, allow_unused=True)
+    dgrads = [torch.zeros_like(p) if g is None else g for g, p in zip(dgrads, params)]
     grads = torch.autograd.grad(total, params)
     vloss, ploss, rloss = vloss.detach(), ploss.detach(), rloss.detach()
-    return dict(grads=[g.detach().numpy() for g in grads], value=float(vloss), policy=float(ploss),
+    return dict(grads=[g.detach().numpy() for g in grads], data_grads=[g.detach().numpy() for g in dgrads],
+                value=float(vloss), policy=float(ploss),
                 reward=float(rloss), l2=[float(x.detach()) for x in l2], values=v.detach().numpy(),
                 policies=torch.softmax(lg, -1).detach().numpy(), rewards=r.detach().numpy())
