@@ -486,6 +486,58 @@ int mz_mcts_opponent(mz_handle* h, int sims, int rollouts);
 int mz_mcts_eval(mz_handle* h, int env_kind, int G, const uint8_t* boards, const int32_t* players, int sims,
                  int rollouts, uint32_t rng_step, uint32_t game_offset, int32_t* n_out, int32_t* w_out);
 
+/* ---- The network-only player (AlphaZero.jl's NetworkOnly) -------
+ * A row's move from the policy head alone, with no tree.  For a row with
+ * observation obs, a non-empty legal set, temperature T and the Philox key
+ * (seed, game_offset + row, rng_step):
+ *   (v, p) = prediction(representation(obs)), bit for bit what
+ *     mz_net_forward(MZ_NET_REPR) then mz_net_forward(MZ_NET_PRED) return: v
+ *     the value head's post-activation, p the policy head's softmax over all A
+ *     actions (the distribution the learner trains; not the Q3 double softmax);
+ *   s = the ascending f32 sum of p[a] over the legal a; π[a] = p[a] / s for a
+ *     legal a and 0 for an illegal one; with s == 0, π[a] = 1 / n_legal;
+ *   the action follows select_action on π with the draw r select_action takes
+ *     for the same row (the ACTION stream; no new stream): T == 0 the first
+ *     maximum of π, T == +inf the mz_rng_below(r, n_legal)-th legal action,
+ *     else weights w[a] = π[a] (T == 1) or (float)det_exp(det_log((double)π[a])
+ *     · (double)(1.0f / T)) where π[a] > 0, else 0; S = their ascending f32 sum,
+ *     u = (float)(r >> 8) · 2^-24 · S, the first legal b whose running f32 sum
+ *     exceeds u, else the last legal action.
+ * The row's result (π, v, action) stands where a search row has (child_visits,
+ * root_value, action).  Serial restatement: csrc/mz_prior_rules.h (mzp_row);
+ * Python mirror: selfplay.prior_move.
+ *   mz_eval_players: which player produces a network side's rows in evaluation
+ *     play.  muzero_kind: the rows with to_play == muzero_player, on the
+ *     handle's nets.  other_kind: the other rows where the other side is a
+ *     network player (MZ_OPP_SELF: the same nets; MZ_OPP_NETWORK: the opponent
+ *     weight set); the rules opponents (RANDOM, EXPERT, MCTS) do not consult
+ *     it.  A handle setting like mz_expert_depth, default (SEARCH, SEARCH):
+ *     mz_selfplay_init and mz_snapshot_load keep it, snapshots do not carry
+ *     it.  Read by mz_selfplay_move in MZ_SP_EVAL and by mz_test_play (so by
+ *     the test worker inside mz_train_run); MZ_SP_TRAIN never consults it.
+ *     Every env.  Each move issues MuZero's kind on the handle's nets first
+ *     (into the engine's search io), then, only where it differs in kind or in
+ *     weights, the other side's kind into second outputs followed by
+ *     mz_sp_pick.  With (PRIOR, ·) against a rules opponent, or (PRIOR, PRIOR)
+ *     with MZ_OPP_SELF, a move launches no search.  Refused: a kind outside
+ *     {0, 1} ("eval players: ...").
+ *   mz_prior_eval: G rows (0..max_games) on host buffers, as mz_mcts_search's:
+ *     obs [G][stacked features], legal_mask [G][A] -> policy [G][A] = π, value
+ *     [G] = v, action [G] (1-based).  opponent_set 0: the handle's nets; 1: the
+ *     opponent weight set (refused until it is complete).  Refused: a row
+ *     without a legal action, a temperature that is negative or NaN.
+ *     Synchronises; needs no mz_selfplay_init.
+ *   mz_prior_eval_dev: the same on device pointers, stream-ordered on
+ *     `stream`, no validation of the rows.                                     */
+enum { MZ_PLAYER_SEARCH = 0, MZ_PLAYER_PRIOR = 1 };
+int mz_eval_players(mz_handle* h, int muzero_kind, int other_kind);
+int mz_prior_eval(mz_handle* h, int G, const float* obs, const uint8_t* legal_mask, int opponent_set,
+                  uint32_t rng_step, uint32_t game_offset, float temperature, float* policy, float* value,
+                  int32_t* action);
+int mz_prior_eval_dev(mz_handle* h, int G, const float* obs, const uint8_t* legal_mask, int opponent_set,
+                      uint32_t rng_step, uint32_t game_offset, float temperature, float* policy, float* value,
+                      int32_t* action, void* stream);
+
 /* Evaluation tally since mz_selfplay_init: {games finished, MuZero wins,
  * opponent wins, draws}; the winner is read from the last move's reward
  * (TicTacToe with quirk Q14: the player to move after it; Connect4: the

@@ -44,6 +44,7 @@ const ENV_TICTACTOE, ENV_CONNECT4, ENV_ATARI = Cint(0), Cint(1), Cint(2)   # ENV
 const SP_TRAIN, SP_EVAL, OPP_SELF, OPP_RANDOM, OPP_EXPERT = Cint(0), Cint(1), Cint(0), Cint(1), Cint(2)
 const OPP_NETWORK = Cint(3)
 const OPP_MCTS = OPP_NETWORK + Cint(1)          # 4 = MZ_OPP_MCTS: the next opponent id
+const PLAYER_SEARCH, PLAYER_PRIOR = Cint(0), Cint(1)   # mz_eval_players: the search, the network-only player
 const LEARN_REF_SEMANTICS, LEARN_CORRECTED = Cint(0), Cint(1)
 const TRAIN_LEARNER, TRAIN_ACTOR, TRAIN_QUEUED = Cint(0), Cint(1), Cint(2)
 const REAN_OFF, REAN_BY_VALUE, REAN_BY_SEARCH = Cint(0), Cint(1), Cint(2)
@@ -228,6 +229,23 @@ function mcts_eval(e::Engine, env::Cint, boards::Matrix{UInt8}, players::Vector{
                    (Ptr{Cvoid}, Cint, Cint, Ptr{UInt8}, Ptr{Int32}, Cint, Cint, UInt32, UInt32, Ptr{Int32}, Ptr{Int32}),
                    e.h, env, size(boards, 2), boards, players, sims, rollouts, rng_step, game_offset, n, w))
     (n, w)
+end
+# The network-only player (DESIGN §24; AlphaZero.jl's NetworkOnly): a handle setting like expert_depth!; which
+# player (PLAYER_SEARCH / PLAYER_PRIOR) produces MuZero's rows and the other network side's rows in evaluation play
+eval_players!(e::Engine, muzero_kind::Cint=PLAYER_SEARCH, other_kind::Cint=PLAYER_SEARCH) =
+    check(e, ccall((:mz_eval_players, libmz), Cint, (Ptr{Cvoid}, Cint, Cint), e.h, muzero_kind, other_kind))
+"""prior_eval(e, obs (features, G), legal (A, G) UInt8; opponent_set, rng_step, game_offset, temperature) — the
+policy head's move with no tree: (policy (A, G) = its softmax renormalised over the legal actions, value (G),
+action (G) 1-based).  opponent_set = 1: the opponent weight set's nets."""
+function prior_eval(e::Engine, obs::Matrix{Float32}, legal::Matrix{UInt8}; opponent_set=0, rng_step=0,
+                    game_offset=0, temperature=0f0)
+    A, G = size(legal)
+    policy = Matrix{Float32}(undef, A, G); value = Vector{Float32}(undef, G); action = Vector{Int32}(undef, G)
+    check(e, ccall((:mz_prior_eval, libmz), Cint,
+                   (Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{UInt8}, Cint, UInt32, UInt32, Float32, Ptr{Float32},
+                    Ptr{Float32}, Ptr{Int32}),
+                   e.h, G, obs, legal, opponent_set, rng_step, game_offset, temperature, policy, value, action))
+    (policy, value, action)
 end
 # Board-symmetry augmentation of the device get_batch (DESIGN §23): a handle setting like expert_depth!;
 # on: every sample of every device get_batch is drawn under a random element of the env's symmetry group

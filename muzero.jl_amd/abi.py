@@ -24,6 +24,7 @@ LEARN_REF_SEMANTICS, LEARN_CORRECTED = 0, 1
 BP_PLAN_FIELDS = ("n_app", "fwd_levels", "bwd_levels", "slot_floats", "nslot", "lds_bytes", "arena_reads",
                   "unslotted_outputs", "arena_accumulations", "fwd_flagged", "bwd_flagged")
 OPP_SELF, OPP_RANDOM, OPP_EXPERT, OPP_NETWORK, OPP_MCTS = 0, 1, 2, 3, 4
+PLAYER_SEARCH, PLAYER_PRIOR = 0, 1               # mz_eval_players: the search, the network-only player
 REAN_OFF, REAN_BY_VALUE, REAN_BY_SEARCH = 0, 1, 2
 TEST_RECORDS = 1024                              # MZ_TEST_RECORDS: the test worker's record ring
 # one record of the test worker (mz_test_results): counts[8] then sums[3]
@@ -98,6 +99,11 @@ SIGNATURES = {
     "mz_mcts_opponent": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int]),
     "mz_mcts_eval": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP, ctypes.c_int, ctypes.c_int,
                                     ctypes.c_uint32, ctypes.c_uint32, _VP, _VP]),
+    "mz_eval_players": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int]),
+    "mz_prior_eval": (ctypes.c_int, [_VP, ctypes.c_int, _VP, _VP, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
+                                     ctypes.c_float, _VP, _VP, _VP]),
+    "mz_prior_eval_dev": (ctypes.c_int, [_VP, ctypes.c_int, _VP, _VP, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
+                                         ctypes.c_float, _VP, _VP, _VP, _VP]),
     "mz_opponent_weights_set": (ctypes.c_int, [_VP, ctypes.c_int, _VP, ctypes.c_size_t]),
     "mz_opponent_weights_get": (ctypes.c_int, [_VP, ctypes.c_int, _VP, ctypes.c_size_t]),
     "mz_opponent_from": (ctypes.c_int, [_VP, ctypes.c_int, _VP]),
@@ -514,6 +520,28 @@ class Engine:
         self._check(self.lib.mz_expert_judge(self.h, env_kind, b.shape[0], _p(b), _p(p), _p(a), depth, _p(out)),
                     "mz_expert_judge")
         return tuple(int(x) for x in out)
+
+    def eval_players(self, muzero_kind=PLAYER_SEARCH, other_kind=PLAYER_SEARCH):
+        """Which player produces a network side's rows in evaluation play: PLAYER_SEARCH or
+        PLAYER_PRIOR (the policy head's move, no tree) for MuZero's turns and for the other turns where the other
+        side is a network player (OPP_SELF, OPP_NETWORK).  A handle setting like expert_depth; training
+        self-play never consults it."""
+        self._check(self.lib.mz_eval_players(self.h, muzero_kind, other_kind), "mz_eval_players")
+
+    def prior_eval(self, obs, legal_mask, opponent_set=0, rng_step=0, game_offset=0, temperature=0.0):
+        """The network-only player on G rows (mz_prior_eval): (policy (G, A) = the policy head's softmax
+        renormalised over the legal actions, value (G,), action (G,) 1-based).  opponent_set 1: the opponent
+        weight set's nets."""
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        G = obs.shape[0]
+        legal = np.ascontiguousarray(legal_mask, dtype=np.uint8)
+        assert obs.ndim == 2 and legal.shape == (G, self.A), "prior_eval: obs (G, features), legal_mask (G, A)"
+        pol = np.empty((G, self.A), np.float32)
+        val = np.empty(G, np.float32)
+        act = np.empty(G, np.int32)
+        self._check(self.lib.mz_prior_eval(self.h, G, _p(obs), _p(legal), opponent_set, rng_step & 0xffffffff,
+                                           game_offset, temperature, _p(pol), _p(val), _p(act)), "mz_prior_eval")
+        return pol, val, act
 
     def mcts_opponent(self, sims=0, rollouts=0):
         """Budget of the OPP_MCTS rules MCTS: sims 1..1024 simulations a move, rollouts 1..64 random

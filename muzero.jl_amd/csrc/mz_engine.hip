@@ -503,6 +503,9 @@ static size_t search_lds_bytes(const mz_handle* h) {
     return search_lds_base(h) + (h->lds_tree ? (size_t)MZ_TILE * h->tree_game_bytes : 0);
 }
 
+// mz_prior_fc: the activation layout, [16][16] floats of staging, 16 legal masks
+static size_t prior_lds_bytes(const mz_handle* h) { return ((size_t)h->lay.total + MZ_TILE * 16 + MZ_TILE) * 4; }
+
 typedef void (*search_fn)(SearchParams);
 static search_fn search_kernel(const mz_handle* h) {
     if (h->use_res) return h->lds_tree ? mz_search_kernel_lds_res : mz_search_kernel_hbm_res;
@@ -682,6 +685,9 @@ int mz_engine_create(const mz_config* conf, const mz_ffhp* hyper, int device, in
         for (auto k : ks)
             CK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)search_lds_bytes(h)) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute"));
+        // the network-only player's tile: less than any search tile's (no per-game state, no tree)
+        CK(hipFuncSetAttribute((const void*)mz_prior_fc, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)prior_lds_bytes(h)) == hipSuccess ? 0 : fail(h, "hipFuncSetAttribute(prior)"));
     }
     CK(hipStreamSynchronize(h->stream) == hipSuccess ? 0 : fail(h, "sync"));
     *out = h;
@@ -1726,21 +1732,143 @@ static int opp_io(mz_handle* h) {
     return 0;
 }
 
+// ---- the network-only player
+// G rows' (π, v, action) with the nets the handle points at, stream-ordered; temp_g as search_dev's.
+// FC engines: one mz_prior_fc launch.  ResNet engines: the downsampler where the engine has one, the two
+// forward launches of rean_values' ResNet branch into the handle's buffers, then mz_prior_pick.
+static int prior_dev(mz_handle* h, int G, const float* obs, const uint8_t* legal_mask, uint32_t rng_step,
+                     uint32_t game_offset, float temperature, float* policy, float* value, int32_t* action,
+                     hipStream_t st, const float* temp_g) {
+    if (G < 0 || G > h->max_games) return fail(h, "G exceeds max_games");
+    if (G == 0) return 0;
+    PriorParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.G = G; Q.A = h->A; Q.obs_feat = h->obs_feat; Q.rng_step = rng_step; Q.game_offset = game_offset;
+    Q.seed = h->seed; Q.temperature = temperature; Q.temp_g = temp_g;
+    Q.obs = obs; Q.legal = legal_mask; Q.policy = policy; Q.value = value; Q.action = action;
+    void* args[] = {&Q};
+    if (h->kind != 1) {
+        Q.plan_root = h->d_plan[3]; Q.Wp = h->d_Wp; Q.Bp = h->d_Bp;
+        Q.x_rep = h->lay.x_rep; Q.v_out = h->lay.v_out; Q.p_out = h->lay.p_out; Q.v_act = h->lay.v_act;
+        Q.lds_total = h->lay.total;
+        MZ_TRY(h, hipLaunchKernel((const void*)mz_prior_fc, dim3((G + MZ_TILE - 1) / MZ_TILE), dim3(MZ_THREADS), args,
+                                  prior_lds_bytes(h), st));
+        return 0;
+    }
+    const RPlan& Rr = h->rplan[MZ_NET_REPR];
+    const RPlan& Rp = h->rplan[MZ_NET_PRED];
+    if (Rp.in_feat != Rr.out0_n || Rp.out0_n != 1 || Rp.out1_n != h->A)
+        return fail(h, "prior: unexpected ResNet plan shapes");
+    const float* x = obs;
+    if (h->ds) {                                    // representation: downsampler, then the tail
+        if (ds_launch(h, obs, h->d_dsout, G, st)) return -1;
+        x = h->d_dsout;
+    }
+    for (int net = MZ_NET_REPR; net <= MZ_NET_PRED; ++net) {
+        RNetParams N;
+        N.ng = h->rn_ng; N.W = h->rconf.observation_shape[0]; N.H = h->rconf.observation_shape[1];
+        N.P = N.W * N.H; N.n_items = G; N.softmax1 = net == MZ_NET_PRED; N.bn_s = h->bn_s;
+        N.plan = h->d_rplan + net; N.Wimg = h->d_Wp; N.flat = h->d_flat;
+        N.x = net == MZ_NET_REPR ? x : h->d_pr_h;
+        N.out0 = net == MZ_NET_REPR ? h->d_pr_h : h->d_pr_v;
+        N.out1 = h->d_pr_p;
+        void* nargs[] = {&N};
+        MZ_TRY(h, hipLaunchKernel((const void*)mz_rnet_forward_kernel, dim3((G + N.ng - 1) / N.ng), dim3(RN_THREADS),
+                                  nargs, h->rn_lds[net], st));
+    }
+    Q.p = h->d_pr_p; Q.v = h->d_pr_v;
+    const int gw = h->A > 16 ? 32 : 16;
+    MZ_TRY(h, hipLaunchKernel(gw == 32 ? (const void*)mz_prior_pick32 : (const void*)mz_prior_pick,
+                              dim3((G + 256 / gw - 1) / (256 / gw)), dim3(256), args, 0, st));
+    return 0;
+}
+
+static const char* const kOppNetsMissing =
+    "opponent: MZ_OPP_NETWORK needs the opponent's nets (mz_opponent_weights_set / _from / _load first)";
+
+int mz_prior_eval_dev(mz_handle* h, int G, const float* obs, const uint8_t* legal_mask, int opponent_set,
+                      uint32_t rng_step, uint32_t game_offset, float temperature, float* policy, float* value,
+                      int32_t* action, void* stream) {
+    if (!h) return -2;
+    if (opponent_set != 0 && opponent_set != 1) return fail(h, "prior: opponent_set must be 0 or 1");
+    if (opponent_set && h->opp_have != 7u) return fail(h, kOppNetsMissing);
+    if (!(temperature >= 0.0f)) return fail(h, "prior: temperature must be >= 0 (+inf allowed)");
+    if (opponent_set) wset_swap(h, h->opp);
+    const int rc = prior_dev(h, G, obs, legal_mask, rng_step, game_offset, temperature, policy, value, action,
+                             stream_of(h, stream), nullptr);
+    if (opponent_set) wset_swap(h, h->opp);
+    return rc;
+}
+
+int mz_prior_eval(mz_handle* h, int G, const float* obs, const uint8_t* legal_mask, int opponent_set, uint32_t rng_step,
+                  uint32_t game_offset, float temperature, float* policy, float* value, int32_t* action) {
+    if (!h) return -2;
+    if (G < 0 || G > h->max_games) return fail(h, "G exceeds max_games");
+    if (opponent_set != 0 && opponent_set != 1) return fail(h, "prior: opponent_set must be 0 or 1");
+    if (opponent_set && h->opp_have != 7u) return fail(h, kOppNetsMissing);
+    if (!(temperature >= 0.0f)) return fail(h, "prior: temperature must be >= 0 (+inf allowed)");
+    if (G == 0) return 0;
+    const int A = h->A;
+    for (int g = 0; g < G; ++g) {
+        int any = 0;
+        for (int a = 0; a < A; ++a) any |= legal_mask[(size_t)g * A + a] != 0;
+        if (!any) return fail(h, "Legal actions should not be an empty array (game " + std::to_string(g) + ")");
+    }
+    MZ_TRY(h, hipSetDevice(h->device));
+    MZ_SYNC(h);                  // `_dev` work on other streams first
+    MZ_TRY(h, hipMemcpyAsync(h->d_obs, obs, (size_t)G * h->obs_feat * 4, hipMemcpyHostToDevice, h->stream));
+    MZ_TRY(h, hipMemcpyAsync(h->d_legal, legal_mask, (size_t)G * A, hipMemcpyHostToDevice, h->stream));
+    int rc = mz_prior_eval_dev(h, G, h->d_obs, h->d_legal, opponent_set, rng_step, game_offset, temperature, h->d_cv,
+                               h->d_rv, h->d_act, h->stream);
+    if (rc) return rc;
+    MZ_TRY(h, hipMemcpyAsync(policy, h->d_cv, (size_t)G * A * 4, hipMemcpyDeviceToHost, h->stream));
+    MZ_TRY(h, hipMemcpyAsync(value, h->d_rv, (size_t)G * 4, hipMemcpyDeviceToHost, h->stream));
+    MZ_TRY(h, hipMemcpyAsync(action, h->d_act, (size_t)G * 4, hipMemcpyDeviceToHost, h->stream));
+    MZ_SYNC(h);
+    return 0;
+}
+
+// one side's rows of an evaluation move: its kind on the nets the handle points at
+static int player_dev(mz_handle* h, int kind, const SpParams& S, float* cv, float* rv, int32_t* act, hipStream_t st) {
+    if (kind == MZ_PLAYER_PRIOR)
+        return prior_dev(h, S.G, h->d_obs, h->d_legal, S.step, S.game_offset, S.temperature, cv, rv, act, st, S.temp_g);
+    return search_dev(h, S.G, h->d_obs, h->d_legal, h->d_tp, 1, S.step, S.game_offset, S.temperature, cv, rv, act, st,
+                      S.temp_g);
+}
+
+// Does an evaluation move against `opponent` issue a secondary launch (the other side's kind on its
+// weights, into second outputs)?  Only a network player on the other side can differ from the primary:
+// in weights (MZ_OPP_NETWORK) or in kind (MZ_OPP_SELF with two different kinds).
+static bool eval_secondary(const mz_handle* h, int opponent) {
+    return opponent == MZ_OPP_NETWORK || (opponent == MZ_OPP_SELF && h->ev_kind[0] != h->ev_kind[1]);
+}
+
 // One move of S's rows up to the commit, shared by mz_selfplay_move (the self-play slots) and
-// mz_test_play (the test slots): mz_sp_prepare -> the search on the engine's io with the handle's
-// current nets -> mz_expert_move, or the opponent's search (outputs cv2 / rv2 / act2) and mz_sp_pick
-// -> mz_sp_commit.  The keys, the temperature and the mode are S's.  `judge` (a judging evaluation of
-// mz_test_play; null everywhere else): the audit row, which the expert's launch feeds on MuZero's turns
-// from the action the search left in d_act; with another opponent that launch is made for the judge alone.
+// mz_test_play (the test slots): mz_sp_prepare -> the primary launch on the engine's io with the handle's
+// current nets (the search; in evaluation play MuZero's kind, mz_eval_players) -> the secondary launch
+// where the other side is a network player that differs in kind or in weights (outputs cv2 / rv2 / act2)
+// and mz_sp_pick -> the rules opponents' launches -> mz_sp_commit.  The keys, the temperature and the
+// mode are S's.  `judge` (a judging evaluation of mz_test_play; null everywhere else): the audit row,
+// which the expert's launch feeds on MuZero's turns from the action the primary left in d_act; with
+// another opponent that launch is made for the judge alone.
 static int sp_move_body(mz_handle* h, const SpParams& S, float* cv2, float* rv2, int32_t* act2, hipStream_t st,
                         long long* judge = nullptr) {
     const int G = S.G;
     const dim3 waves((G + 3) / 4);
     hipLaunchKernelGGL(mz_sp_prepare, waves, dim3(256), 0, st, S);
     MZ_TRY(h, hipGetLastError());
-    int rc = search_dev(h, G, h->d_obs, h->d_legal, h->d_tp, 1, S.step, S.game_offset, S.temperature, h->d_cv,
-                        h->d_rv, h->d_act, st, S.temp_g);
+    int rc = player_dev(h, S.eval ? h->ev_kind[0] : MZ_PLAYER_SEARCH, S, h->d_cv, h->d_rv, h->d_act, st);
     if (rc) return rc;
+    if (S.eval && eval_secondary(h, S.opponent)) {   // the other side's own player; its turns take that whole result
+        if (!act2) return fail(h, "eval players: the second outputs are not allocated");
+        const bool theirs = S.opponent == MZ_OPP_NETWORK;
+        if (theirs) wset_swap(h, h->opp);
+        rc = player_dev(h, h->ev_kind[1], S, cv2, rv2, act2, st);
+        if (theirs) wset_swap(h, h->opp);
+        if (rc) return rc;
+        PickArgs X{h->d_cv, h->d_rv, h->d_act, cv2, rv2, act2};
+        hipLaunchKernelGGL(mz_sp_pick, waves, dim3(256), 0, st, S, X);
+    }
     if ((S.eval && S.opponent == MZ_OPP_EXPERT) || judge) {   // the expert's turns: its move replaces the search's action
         ExpertArgs X{expert_depth_of(h, h->sp_env), h->d_act, nullptr, nullptr, judge};
         if (expert_table_in_use(h)) {                // the solved table: a lookup in place of the search
@@ -1755,15 +1883,6 @@ static int sp_move_body(mz_handle* h, const SpParams& S, float* cv2, float* rv2,
         mcts_launch(S, h->sp_mcts_sims ? h->sp_mcts_sims : MZM_DEF_SIMS,
                     h->sp_mcts_rollouts ? h->sp_mcts_rollouts : MZM_DEF_ROLLOUTS, h->d_mcts_sqrt, h->d_act, nullptr,
                     nullptr, st);
-    }
-    if (S.eval && S.opponent == MZ_OPP_NETWORK) {    // the same search with the opponent's nets; its turns take
-        wset_swap(h, h->opp);                        // that search's whole result
-        rc = search_dev(h, G, h->d_obs, h->d_legal, h->d_tp, 1, S.step, S.game_offset, S.temperature, cv2, rv2, act2,
-                        st, S.temp_g);
-        wset_swap(h, h->opp);
-        if (rc) return rc;
-        PickArgs X{h->d_cv, h->d_rv, h->d_act, cv2, rv2, act2};
-        hipLaunchKernelGGL(mz_sp_pick, waves, dim3(256), 0, st, S, X);
     }
     hipLaunchKernelGGL(mz_sp_commit, waves, dim3(256), 0, st, S);
     return 0;
@@ -1852,8 +1971,9 @@ int mz_selfplay_move(mz_handle* h, uint32_t rng_step, uint32_t game_offset, floa
     S.tgame = h->sp_latch ? h->d_sp_tgame : nullptr;
     const int G = h->sp_G;
     const dim3 waves((G + 3) / 4);
-    // the opponent's nets play its turns (mz_selfplay_mode checked the set and the env; both stay)
-    const bool arena = h->sp_eval && h->sp_opp == MZ_OPP_NETWORK;
+    // the other side has a player of its own: the opponent's nets (mz_selfplay_mode checked the set and
+    // the env; both stay), or another kind on the same nets (mz_eval_players).  A no-op once allocated.
+    const bool arena = h->sp_eval && eval_secondary(h, h->sp_opp);
     if (arena && opp_io(h)) return -1;
     if (h->sp_reset_pending) {                      // the initial Atari-like games (mz_selfplay_init)
         SpParams R = S;
@@ -1886,10 +2006,28 @@ int mz_selfplay_mode(mz_handle* h, int mode, int opponent, int muzero_player) {
         if (h->opp_have != 7u)
             return fail(h, "opponent: MZ_OPP_NETWORK needs the opponent's nets (mz_opponent_weights_set / _from / "
                            "_load first)");
+    }
+    // the second outputs: the opponent's nets, or two kinds on one set of nets (mz_eval_players)
+    if (mode == MZ_SP_EVAL && eval_secondary(h, opponent)) {
         MZ_TRY(h, hipSetDevice(h->device));
-        if (mode == MZ_SP_EVAL && opp_io(h)) return -1;
+        if (opp_io(h)) return -1;
     }
     h->sp_eval = mode == MZ_SP_EVAL; h->sp_opp = opponent; h->sp_mzp = muzero_player;
+    return 0;
+}
+
+int mz_eval_players(mz_handle* h, int muzero_kind, int other_kind) {
+    if (!h) return -2;
+    for (int k : {muzero_kind, other_kind})
+        if (k != MZ_PLAYER_SEARCH && k != MZ_PLAYER_PRIOR)
+            return fail(h, "eval players: a kind must be MZ_PLAYER_SEARCH or MZ_PLAYER_PRIOR");
+    h->ev_kind[0] = muzero_kind; h->ev_kind[1] = other_kind;
+    // the second outputs of the mode in force, where the new kinds make a secondary launch necessary
+    // (mz_selfplay_mode and the first mz_test_play after it do the same for theirs)
+    if (h->sp_env >= 0 && h->sp_eval && eval_secondary(h, h->sp_opp)) {
+        MZ_TRY(h, hipSetDevice(h->device));
+        if (opp_io(h)) return -1;
+    }
     return 0;
 }
 
@@ -2145,7 +2283,7 @@ static int test_alloc(mz_handle* h) {
         MZ_TRY(h, spalloc(h, &t.temp, E, false));
         t.E = h->test_E;
     }
-    if (h->test_opp == MZ_OPP_NETWORK && !t.act2) {
+    if (eval_secondary(h, h->test_opp) && !t.act2) {
         MZ_TRY(h, spalloc(h, &t.cv2, E * A, false));
         MZ_TRY(h, spalloc(h, &t.rv2, E, false));
         MZ_TRY(h, spalloc(h, &t.act2, E, false));

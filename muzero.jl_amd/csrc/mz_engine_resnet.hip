@@ -662,6 +662,9 @@ int mz_engine_create_resnet(const mz_config* conf, const mz_resnet_hp* hyper, in
         CK(al(&h->d_rhk, G * (S + 1))); CK(al(&h->d_rov, G)); CK(al(&h->d_rologit, G * A)); CK(al(&h->d_ror, G));
         CK(al(&h->d_obs, G * h->obs_feat)); CK(al(&h->d_legal, G * A)); CK(al(&h->d_tp, G));
         CK(al(&h->d_cv, G * A)); CK(al(&h->d_rv, G)); CK(al(&h->d_act, G));
+        // the network-only player's two forward launches write here (mz_prior_eval_dev)
+        CK(al(&h->d_pr_h, G * (size_t)h->rplan[MZ_NET_REPR].out0_n)); CK(al(&h->d_pr_v, G));
+        CK(al(&h->d_pr_p, G * A));
     }
     CK(hipStreamSynchronize(h->stream) == hipSuccess ? 0 : fail(h, "sync"));
     *out = h;

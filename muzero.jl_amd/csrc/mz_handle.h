@@ -256,6 +256,10 @@ struct mz_handle {
     int sp_expert_depth = 0;                              // mz_expert_depth (0: the env's default)
     int sp_mcts_sims = 0, sp_mcts_rollouts = 0;           // mz_mcts_opponent (0: the defaults)
     double* d_mcts_sqrt = nullptr;                        // [MZM_MAX_SIMS + 1] sqrt(k) (the first MZ_OPP_MCTS use)
+    // the network-only player (mz_eval_players): the kinds of MuZero's and the other side's rows,
+    // and on ResNet engines the two forward launches' outputs [max_games][H | 1 | A] (mz_engine_create_resnet)
+    int ev_kind[2] = {MZ_PLAYER_SEARCH, MZ_PLAYER_SEARCH};
+    float* d_pr_h = nullptr; float* d_pr_v = nullptr; float* d_pr_p = nullptr;
     // the solved TicTacToe table (mz_expert_table): the handle's, built by the first on = 1
     bool xtable_on = false;
     int8_t* d_xtable = nullptr;                           // [MZX_TTT_CODES][MZX_TTT_ENTRY]

@@ -183,6 +183,25 @@ struct PickArgs {
     const float* cv2; const float* rv2; const int32_t* act2;    // ... the opponent's nets' search of the same rows
 };
 
+// mz_prior_fc / mz_prior_pick (mz_prior.hip): the network-only player.  Row g's result
+// (π, v, action) goes where a search row has its visit fractions, root value and action.
+struct PriorParams {
+    int G, A, obs_feat;
+    uint32_t rng_step, game_offset;
+    uint64_t seed;
+    float temperature;
+    const float* temp_g;        // [G] per-row temperatures (self-play temperature_threshold) or null
+    const float* obs;           // mz_prior_fc: [G][obs_feat] stacked observations
+    const uint8_t* legal;       // [G][A]
+    float* policy; float* value; int32_t* action;               // [G][A], [G], [G] (1-based)
+    // mz_prior_fc: the root plan (representation, then prediction from h_out) on the tile16 images
+    const int* plan_root; const float* Wp; const float* Bp;
+    int x_rep, v_out, p_out, v_act, lds_total;
+    // mz_prior_pick: what the two mz_rnet_forward_kernel launches wrote
+    const float* p;             // [G][A] the policy head's softmax
+    const float* v;             // [G] the value head's output
+};
+
 // get_batch + make_target (ReplayBuffer.jl:5-50, 73-107, 188-217) on the shard
 struct RpSampleParams {
     int B, K, A, osz, P, F, stacked, T, td, cap;
@@ -235,6 +254,9 @@ extern "C" __global__ void mz_expert_table_rows(uint8_t* boards, int32_t* player
 extern "C" __global__ void mz_expert_table_pack(const int32_t* scores, int8_t* table, int c0, int n);
 extern "C" __global__ void mz_mcts_move(SpParams S, MctsArgs X);
 extern "C" __global__ void mz_sp_pick(SpParams S, PickArgs X);
+extern "C" __global__ void mz_prior_fc(PriorParams Q);
+extern "C" __global__ void mz_prior_pick(PriorParams Q);
+extern "C" __global__ void mz_prior_pick32(PriorParams Q);
 extern "C" __global__ void mz_test_begin(SpParams S, TestRec R);
 extern "C" __global__ void mz_test_tally(SpParams S, TestRec R);
 extern "C" __global__ void mz_log_games(SpParams S, LogAcc* acc);

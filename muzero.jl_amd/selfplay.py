@@ -19,6 +19,8 @@ from .games.mcts_rules import DEFAULT_ROLLOUTS, DEFAULT_SIMS, mcts_pick, mcts_ro
 from .rng import rng_below, rng_u32
 
 MZ_RNG_OPPONENT = 7                                               # include/mz_detmath.h
+MZ_RNG_ACTION = 3
+NET_REPR, NET_PRED = 0, 1
 
 
 def game_winner(env_name, last_reward, last_mover):
@@ -87,11 +89,94 @@ def get_stacked_observations(obs_hist, action_hist, index, num_stacked, plane):
     return np.concatenate(parts)
 
 
+# ---- the network-only player (csrc/mz_prior_rules.h): every operation in float32, in the
+# header's order
+def prior_policy(p, legal):
+    """π of one row: the policy head's softmax p (A,) renormalised over the legal actions — s = the ascending
+    float32 sum of the legal p (an illegal action adds +0), π = p / s on legal actions and 0 elsewhere; with
+    s == 0 (every legal p underflowed) π = 1 / n_legal on legal actions."""
+    p = np.asarray(p, np.float32)
+    legal = np.asarray(legal).astype(bool)
+    assert p.ndim == 1 and legal.shape == p.shape and legal.any(), "prior: one row with a legal action"
+    s = np.float32(0.0)
+    for a in range(p.size):
+        s = np.float32(s + (p[a] if legal[a] else np.float32(0.0)))
+    pi = np.zeros(p.size, np.float32)
+    n = int(legal.sum())
+    for a in np.flatnonzero(legal):
+        pi[a] = np.float32(1.0) / np.float32(n) if s == 0 else np.float32(p[a] / s)
+    return pi
+
+
+def prior_pick(pi, legal, temperature, r, detmath=None):
+    """The 0-based action the network-only player draws from π with the row's ACTION draw r (the rule of
+    select_action): temperature 0 the first maximum over the legal actions, +inf the rng_below(r, n_legal)-th
+    legal action, else weights w = π (temperature 1) or float32(det_exp(det_log(float64(π)) * float64(
+    float32(1) / temperature))) where π > 0 (0 elsewhere; detmath supplies det_exp / det_log, the engine's
+    deterministic float64 exp / log), S = their ascending float32 sum over the legal actions, u =
+    float32(r >> 8) * 2^-24 * S, the first legal action whose running float32 sum exceeds u, else the last."""
+    pi = np.asarray(pi, np.float32)
+    acts = np.flatnonzero(np.asarray(legal).astype(bool))
+    T = np.float32(temperature)
+    assert len(acts) and T >= 0, "prior: a legal action and a temperature >= 0"
+    if T == 0:
+        best = acts[0]
+        for a in acts[1:]:
+            if pi[a] > pi[best]:
+                best = a
+        return int(best)
+    if np.isinf(T):
+        return int(acts[rng_below(r, len(acts))])
+    if T == 1:
+        w = pi
+    else:
+        assert detmath is not None, "prior: a temperature outside {0, 1, inf} needs detmath (det_exp, det_log)"
+        inv = np.float64(np.float32(1.0) / T)
+        w = np.zeros(pi.size, np.float32)
+        for a in acts:
+            if pi[a] > 0:
+                w[a] = np.float32(detmath.det_exp(np.float64(detmath.det_log(np.float64(pi[a]))) * inv))
+    S = np.float32(0.0)
+    for a in acts:
+        S = np.float32(S + w[a])
+    u = np.float32(np.float32(np.float32(r >> 8) * np.float32(5.9604644775390625e-08)) * S)
+    cum = np.float32(0.0)
+    for a in acts:
+        cum = np.float32(cum + w[a])
+        if cum > u:
+            return int(a)
+    return int(acts[-1])
+
+
+def prior_move(engine, obs, legal, temperature, seed, game_offset, step, detmath=None):
+    """The network-only player's result of G rows on `engine`'s nets: (π (G, A), v (G,), 1-based actions (G,)),
+    where a search has (child visits, root values, actions).  (v, p) = prediction(representation(obs)) from the
+    engine's batched forward; row g draws with the ACTION stream's key (game_offset + g, step).  temperature:
+    one value or one per row."""
+    obs = np.ascontiguousarray(obs, np.float32)
+    legal = np.asarray(legal).astype(bool)
+    G = obs.shape[0]
+    h = engine.forward(NET_REPR, obs)
+    v, p = engine.forward(NET_PRED, h)
+    temps = np.broadcast_to(np.asarray(temperature, np.float32), (G,))
+    pi = np.zeros((G, legal.shape[1]), np.float32)
+    act = np.zeros(G, np.int32)
+    for g in range(G):
+        pi[g] = prior_policy(p[g], legal[g])
+        r = rng_u32(seed, MZ_RNG_ACTION, game_offset + g, step, 0)
+        act[g] = prior_pick(pi[g], legal[g], temps[g], r, detmath) + 1
+    return pi, np.asarray(v, np.float32).reshape(G).copy(), act
+
+
+KINDS = ("search", "prior")
+
+
 class BatchedSelfPlay:
     """G TicTacToe games played in lockstep on one engine (one GPU)."""
 
     def __init__(self, engine, env_cls, G, game_offset=0, step0=0, opponent="self", muzero_player=1,
-                 expert_depth=None, opponent_engine=None, mcts_sims=None, mcts_rollouts=None):
+                 expert_depth=None, opponent_engine=None, mcts_sims=None, mcts_rollouts=None,
+                 muzero_kind="search", other_kind="search", detmath=None):
         """opponent "self" (self_play!, SelfPlay.jl:384-419) or "random": the
         player != muzero_player plays a uniform legal action
         (select_opponent_action, :311-325) — competitive_play! (:421-435);
@@ -101,8 +186,14 @@ class BatchedSelfPlay:
         under the same config and rng_seed), and the history holds the mover's
         own search statistics; "mcts": that player plays the rules MCTS of
         games/mcts_rules.py with mcts_sims simulations of mcts_rollouts
-        rollouts (None: the defaults)."""
+        rollouts (None: the defaults).
+        muzero_kind / other_kind (mz_eval_players): "search" or "prior" (the network-only player,
+        prior_move) for the turns of muzero_player on `engine` and for the other turns where the other side is
+        a network player ("self": the same engine, "network": opponent_engine); the rules opponents ignore
+        other_kind.  detmath: prior_pick's, for temperatures outside {0, 1, inf}."""
         assert opponent in ("self", "random", "expert", "network", "mcts") and muzero_player in (1, 2)
+        assert muzero_kind in KINDS and other_kind in KINDS, "eval players: a kind must be \"search\" or \"prior\""
+        self.muzero_kind, self.other_kind, self.detmath = muzero_kind, other_kind, detmath
         assert (opponent == "network") == (opponent_engine is not None), "network: needs opponent_engine (only)"
         self.opponent = opponent
         self.opponent_engine = opponent_engine
@@ -153,6 +244,17 @@ class BatchedSelfPlay:
                 act = np.where(cold, act0, act)
         return cv, rv, act
 
+    def _player(self, kind, eng, obs, legal, tp, temperature):
+        """One side's result of the move's rows on `eng`: the search, or the network-only player with the
+        rows' own temperatures (a game with >= temperature_threshold moves picks at 0, as _search's does)."""
+        if kind == "search":
+            return self._search(eng, obs, legal, tp, temperature)
+        temps = np.full(self.G, temperature, np.float32)
+        if self.conf.temperature_threshold is not None:
+            moves = np.array([len(h.action_history) for h in self.histories])
+            temps[moves >= self.conf.temperature_threshold] = 0.0
+        return prior_move(eng, obs, legal, temps, self.eng.rng_seed, self.game_offset, self.step, self.detmath)
+
     def play_move(self, temperature=1.0):
         """One move of every game (play_game's loop body, SelfPlay.jl:343-380)."""
         c = self.conf
@@ -162,10 +264,13 @@ class BatchedSelfPlay:
                                          self.env.board[g].astype(np.float32))   # :352
         obs = self._stacked()                                                 # :355
         legal = self.env.legal_mask()
-        cv, rv, act = self._search(self.eng, obs, legal, tp, temperature)
-        if self.opponent == "network":            # the same search with the opponent's nets: its turns take
-            theirs = tp != self.muzero_player     # that search's whole result (mz_sp_pick)
-            cv2, rv2, act2 = self._search(self.opponent_engine, obs, legal, tp, temperature)
+        cv, rv, act = self._player(self.muzero_kind, self.eng, obs, legal, tp, temperature)
+        # the other side's own player where it differs in weights ("network") or in kind ("self"): its turns
+        # take that whole result (mz_sp_pick)
+        if self.opponent == "network" or (self.opponent == "self" and self.other_kind != self.muzero_kind):
+            theirs = tp != self.muzero_player
+            cv2, rv2, act2 = self._player(self.other_kind, self.opponent_engine or self.eng, obs, legal, tp,
+                                          temperature)
             cv = np.where(theirs[:, None], cv2, cv)
             rv = np.where(theirs, rv2, rv)
             act = np.where(theirs, act2, act)
@@ -284,13 +389,15 @@ def env_name_of(env_cls):
 
 def evaluate(engine, env_cls, E, opponent="self", muzero_player=1, rng_step0=0, game_offset=0, temperature=0.0,
              training_step=0, expert_depth=None, opponent_engine=None, audit=False, mcts_sims=None,
-             mcts_rollouts=None):
+             mcts_rollouts=None, muzero_kind="search", other_kind="search", detmath=None):
     """One evaluation of the test worker on the host: E slots play one game each (move m keyed
     rng_step0 + m, game_offset); returns (the histories in slot order, their evaluation_record), and
-    with audit=True their evaluation_audit at expert_depth as a third item."""
+    with audit=True their evaluation_audit at expert_depth as a third item.  muzero_kind / other_kind:
+    BatchedSelfPlay's (mz_eval_players)."""
     sp = BatchedSelfPlay(engine, env_cls, E, game_offset=game_offset, step0=rng_step0, opponent=opponent,
                          muzero_player=muzero_player, expert_depth=expert_depth, opponent_engine=opponent_engine,
-                         mcts_sims=mcts_sims, mcts_rollouts=mcts_rollouts)
+                         mcts_sims=mcts_sims, mcts_rollouts=mcts_rollouts, muzero_kind=muzero_kind,
+                         other_kind=other_kind, detmath=detmath)
     histories = sp.play_games(temperature)
     players = engine.conf.players                      # Config.players lists the player ids
     name = env_name_of(env_cls)
